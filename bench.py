@@ -28,6 +28,8 @@ Prints ONE JSON line (rank 0).  Extra objects:
   cpu_baseline — the oracle (fp32 PyTorch-CPU restatement; kind "port") timed on this host's cores on
                  one full image of the workload (20 U-Net forwards @64x64, ~45 s).
 `--workload dift|xray` print the same keys for BASELINE configs[3] / [4].
+`--dump-outputs DIR` writes what the last timed step returned (loss grids, typicality maps, scores; for `--workload` its output) as
+DIR/<name>.npy in float32 after the run; the inputs are fixed by seeds, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -275,10 +277,15 @@ def main():
     ap.add_argument("--workload", choices=["typicality", "dift", "xray", "vae", "pixels"], default="typicality",
                     help="typicality = BASELINE configs[1]/[2] (the graded line); dift = configs[3]; xray = configs[4]; "
                          "vae = SURVEY 8f rank 2 (VAE encode of 8 images @512px); pixels = vae + typicality from images")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32; an array over "
+                         f"{DUMP_MAX_ELEMS} elements as a fixed seeded sample of them), for comparing two builds output for output")
     ap.add_argument("--dift-dtype", choices=["f32", "f16"], default="f32",
                     help="--workload dift: f32 = the reference's arithmetic (dift.py:197-199: no torch_dtype, no autocast) on the fp32 "
                          "matrix cores (the gradable line); f16 = the fp16 engine (reduced precision, labelled so)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ:
         if args.gpus > 1:
@@ -374,14 +381,14 @@ def main():
             # the product surface: D.compute_losses for the 8 images of the work-list slice in ONE engine call; the same N draws for
             # every image (manual_seed(42) precedes each image's draws, compute.py:139-141)
             grids = scorer.compute_losses_batch(x, emb, noises=eps, timesteps=t, to_host=False)    # [n_img, 10, 2, 4, 64, 64] fp16
-            _, scores = eng.reduce_typicality_batched(grids, n_img, N_DRAWS, N_COND)               # one launch, no torch glue
+            maps, scores = eng.reduce_typicality_batched(grids, n_img, N_DRAWS, N_COND)            # one launch, no torch glue
             if d2h["on"]:
                 copy_stream.wait_stream(torch.cuda.current_stream(dev))
                 with torch.cuda.stream(copy_stream):
                     host_grids[last["k"] & 1].copy_(grids, non_blocking=True)
                 grids.record_stream(copy_stream)         # the allocator must not hand the block to step k + 1 before the copy has read it
                 last["k"] += 1
-            last["grids"], last["loss"] = grids, scorer.last_loss32
+            last["grids"], last["loss"], last["maps"] = grids, scorer.last_loss32, maps
             return gather_scores(scores, n_img * world, rank, world)     # world 1: the tensor itself (no kernel)
 
     if world > 1 and not STUB:
@@ -411,6 +418,9 @@ def main():
         dist.barrier()
     sync()
     dt = time.perf_counter() - t0
+    # what the last timed step handed its caller (the legs below run the step again): this rank's loss grids and typicality maps,
+    # and every image's score
+    outputs = {"scores": all_scores} if eng is None else {"loss_grids": last["grids"], "typicality_maps": last["maps"], "scores": all_scores}
     smi = sampler.stop() if sampler else {"sclk_mhz_mean": None, "power_w_mean": None, "clock_samples": 0, "clock_source": None,
                                            "clock_note": "stub run"}
     prof = eng.prof_read() if eng is not None else {"igemm_ms": 0.0, "igemm_flops": 0.0, "igemm_launches": 0,
@@ -583,7 +593,7 @@ def main():
             out["side_workloads"] = {}
             for w, e_ in (("dift", net32), ("xray", eng)):
                 a2 = argparse.Namespace(**vars(args))
-                a2.workload, a2.dift_dtype, a2.steps, a2.warmup, a2.no_cpu_baseline = w, "f32", 3, 1, True
+                a2.workload, a2.dift_dtype, a2.steps, a2.warmup, a2.no_cpu_baseline, a2.dump_outputs = w, "f32", 3, 1, True, None
                 ln = side_workload(a2, e_, dev, sd)
                 out["side_workloads"][w] = {"metric": ln["metric"], "value": ln["value"], "unit": ln["unit"], "ms_per_step": ln["ms_per_step"],
                                             "steps": 3, "dtype": ln["dtype"], "config": ln["config"]["workload"],
@@ -594,6 +604,8 @@ def main():
             net32.close()
         if not args.no_cpu_baseline and world == 1 and not STUB:
             out["cpu_baseline"] = cpu_baseline(sd)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, outputs)
         print(json.dumps(out), flush=True)
         # north_star: "<= 1e-3 score deviation from reference" — a line whose own deviation leg exceeds it is printed and FAILS
         dev_bad = "score_deviation" in out and out["score_deviation"]["loss_grid_rel_l2"] > SCORE_DEVIATION_MAX
@@ -747,6 +759,8 @@ def side_workload(args, eng, dev, sd):
     smi = sampler.stop()
     prof = eng.prof_read()
     eng.prof_enable(False)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"output": out})
     val = units * args.steps / dt
     ig_tf = prof["igemm_flops"] / (prof["igemm_ms"] * 1e-3) / 1e12 if prof["igemm_ms"] > 0 else 0.0
     at_tf = prof["attn_flops"] / (prof["attn_ms"] * 1e-3) / 1e12 if prof["attn_ms"] > 0 else 0.0
@@ -771,6 +785,29 @@ def side_workload(args, eng, dev, sd):
     if not args.no_cpu_baseline and args.workload in ("dift", "xray"):
         line["cpu_baseline"] = cpu_baseline_side(sd, args.workload)
     return line
+
+
+DUMP_MAX_ELEMS = 1 << 22                # 16 MB of float32 per array; the step's outputs are at most 3 arrays
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each array as <out_dir>/<name>.npy in float32.  An array of more than DUMP_MAX_ELEMS elements is written as
+    the DUMP_MAX_ELEMS elements of its flattened order at indices drawn without replacement by numpy's PCG64 seeded 0, ascending:
+    the same positions for the same shape, so two builds compare element for element."""
+    assert len(arrays) * DUMP_MAX_ELEMS * 4 <= 64 << 20
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        shape = list(t.shape)
+        if flat.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(flat.numel(), DUMP_MAX_ELEMS, replace=False))
+            a = flat[torch.from_numpy(idx).to(flat.device)].float().cpu().numpy()
+            what = f"{DUMP_MAX_ELEMS} sampled elements of {shape}"
+        else:
+            a = t.detach().float().cpu().numpy()
+            what = str(shape)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        print(f"bench.py: wrote {name}.npy ({what}, float32) to {out_dir}", file=sys.stderr, flush=True)
 
 
 def _oracle_threads():

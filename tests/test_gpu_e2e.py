@@ -568,7 +568,7 @@ def test_compute_losses_batch_is_bit_equal_to_the_per_image_calls(engine, h, w, 
             assert torch.equal(g_pd[j], sc.compute_losses(x[j:j + 1].to(d), emb[j].to(d), noises=noises[j], timesteps=ts[j], to_host=False))
 
 
-def test_full_size_properties(engine):
+def test_full_size_properties(engine, tmp_path):
     """BASELINE config 2 shape (64x64 latent, 10 t x 2 prompts): size-independent properties."""
     x, eps, t, c = _inputs(64, 64, 10)
     nb, tb, cc, slots = _tile(eps, t, c)
@@ -584,7 +584,7 @@ def test_full_size_properties(engine):
     assert torch.equal(engine.score_conds(x, eps, t, 2), loss2)     # shared-draw path at the full shape
     m = loss2.mean().item()
     assert 0.1 < m < 10.0, m
-    json.dump({"mean_loss_64x64": m}, open(os.path.join(os.environ.get("GRAFT_OUT", "/tmp"), "full_size.json"), "w"))
+    json.dump({"mean_loss_64x64": m}, open(os.path.join(os.environ.get("DM_TEST_OUT", str(tmp_path)), "full_size.json"), "w"))
 
 
 def test_dift_patch_embeddings(engine):
@@ -636,7 +636,7 @@ def test_chunked_calls_are_batch_independent(engine):
     assert a.shape == (200, 4, 64, 64) and torch.equal(a, b)
 
 
-def test_dift_descriptor_deviation_vs_fp32_oracle(engine, sd15_weights_torch):
+def test_dift_descriptor_deviation_vs_fp32_oracle(engine, sd15_weights_torch, tmp_path):
     """The reference's DIFT U-Net is fp32 (dift.py:197-199: no torch_dtype, no autocast); the engine is fp16 storage /
     fp32 accumulate.  What that costs where it matters: the L2-normalised patch descriptors `cluster.py:291-299` feeds
     KMeans, at 32x32 latents (256 px images), ensemble 2 — cosine between engine and fp32-oracle descriptors."""
@@ -663,7 +663,7 @@ def test_dift_descriptor_deviation_vs_fp32_oracle(engine, sd15_weights_torch):
     assert rf < TOL_DIFT                                   # measured 1.21e-3
     assert cos.min().item() > 1 - 1e-6                     # measured 1 - 5e-7
     json.dump({"dift_descriptor_cos_min": cos.min().item(), "dift_feature_rel_l2": rf},
-              open(os.path.join(os.environ.get("GRAFT_OUT", "/tmp"), "dift_dev.json"), "w"))
+              open(os.path.join(os.environ.get("DM_TEST_OUT", str(tmp_path)), "dift_dev.json"), "w"))
 
 
 def test_dift_full_size_properties(engine):
