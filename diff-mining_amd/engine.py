@@ -33,6 +33,7 @@ SYMBOLS = [
     "dm_f32_unet_forward", "dm_f32_dift", "dm_f32_prof_enable", "dm_f32_prof_read", "dm_f32_memory", "dm_f32_op_gemm",
     "dm_f32_op_attention", "dm_f32_op_groupnorm", "dm_f32_op_layernorm", "dm_f32_load_vae_weight", "dm_f32_finalize_vae",
     "dm_f32_vae_encode", "dm_f32_score", "dm_f32_load_clip_weight", "dm_f32_finalize_clip", "dm_f32_clip_encode",
+    "dm_resize_lanczos",
 ]
 
 
@@ -108,6 +109,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.dm_engine_load_vae_weight.argtypes = [vp, C.c_char_p, vp, i32, C.POINTER(i64), i32]
     lib.dm_engine_finalize_vae.argtypes = [vp]
     lib.dm_vae_encode.argtypes = [vp, vp, vp, i32, i32, i32, i32, C.c_float, vp, vp, vp, vp]
+    lib.dm_resize_lanczos.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]
     lib.dm_patch_embed.argtypes = [vp, vp, i32, i32, i32, vp, i32, vp, vp]
     lib.dm_op_ln_stats.argtypes = [vp, vp, i32, i32, C.c_float, vp]
     lib.dm_op_igemm_ln.argtypes = [vp] * 7 + [i32] * 4
@@ -309,6 +311,34 @@ class UNetEngine:
                                            C.c_void_p(mom.data_ptr()) if mom is not None else None, self._stream()),
                     "dm_vae_encode")
         return (lat, mom) if return_moments else lat
+
+    def resize_lanczos(self, images, out_w: int, out_h: int, resample: bool = True):
+        """`PIL.Image.resize((out_w, out_h), LANCZOS)` + `to_tensor(x) * 2 - 1` (D.rescale + D.load_image, compute.py:126-132,
+        165-180) of uint8 HWC RGB arrays of any sizes in ONE launch of dm_resize_lanczos -> [n,3,out_h,out_w] fp32 on the
+        device, bit-equal to `load_image(img.resize(..., LANCZOS))`.  The coefficient tables are PIL's, built on the host
+        (resample.lanczos_axis).  resample=False: the images already have the size; only the normalisation runs."""
+        torch = self._torch
+        from . import resample as RS
+        imgs = [np.ascontiguousarray(a) for a in images]
+        for a in imgs:
+            assert a.dtype == np.uint8 and a.ndim == 3 and a.shape[2] == 3, (a.dtype, a.shape)
+            assert resample or a.shape[:2] == (out_h, out_w), (a.shape, out_h, out_w)
+        n = len(imgs)
+        assert n >= 1 and out_w >= 1 and out_h >= 1
+        desc, tables, tmp_rows = RS.resize_plan([(a.shape[1], a.shape[0]) for a in imgs], out_w, out_h)
+        src = torch.from_numpy(np.concatenate([a.reshape(-1) for a in imgs])).to(self.device)
+        desc_d = torch.from_numpy(desc.view(np.uint8)).to(self.device)
+        out = torch.empty(n, 3, out_h, out_w, dtype=torch.float32, device=self.device)
+        tab_d = tmp = None
+        if resample:
+            tab_d = torch.from_numpy(tables).to(self.device)
+            tmp = torch.empty(n * 3 * tmp_rows * out_w, dtype=torch.uint8, device=self.device)
+        rc = self.lib.dm_resize_lanczos(C.c_void_p(src.data_ptr()), C.c_void_p(desc_d.data_ptr()),
+                                        C.c_void_p(tab_d.data_ptr()) if resample else None, n, out_w, out_h, tmp_rows if resample else 0,
+                                        C.c_void_p(tmp.data_ptr()) if resample else None, C.c_void_p(out.data_ptr()), self._stream())
+        if rc:
+            raise EngineError(f"dm_resize_lanczos: {'bad argument' if rc == 1 else 'HIP launch failed'} (rc {rc})")
+        return out
 
     def load_safetensors(self, path: str, check_config: bool = True):
         """`unet/diffusion_pytorch_model.safetensors` of a diffusers pipeline directory (the format

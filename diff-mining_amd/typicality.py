@@ -9,7 +9,8 @@
     D.noising                compute.py:115-124       TypicalityScorer.noising / draw
     D.compute_losses         compute.py:134-160       TypicalityScorer.compute_losses
     compute_submission loop  compute.py:284-290       TypicalityScorer.compute_submission -> compute_losses_batch (n images, each under
-                                                      its own category, one engine call)
+                                                      its own category, one engine call); compute_worklist (the same files for
+                                                      mixed-size lists: shape buckets, LANCZOS rescale on the GPU)
     D.get_path / np.save     compute.py:162-163,192   TypicalityScorer.save_grid (same .npy layout)
     D.rescale                compute.py:165-180       TypicalityScorer.rescale
     D.compute / __call__ / exists  compute.py:182-202 TypicalityScorer.compute / __call__ / exists
@@ -415,6 +416,113 @@ class TypicalityScorer:
                 flush()
             run.append((path, country, x))
         flush()
+        return out_paths
+
+    # -- compute_submission over a whole mixed-size work list ---------------------------------------
+    batched_vae_encode = True          # one dm_vae_encode per (call, pixel size); tests/test_gpu_worklist.py checks it is bit-equal
+
+    @staticmethod
+    def worklist_plan(latent_shapes, images_per_call: int = 8):
+        """The calls `compute_worklist` makes: line indices grouped by latent shape (buckets in order of first appearance, list
+        order inside a bucket), each bucket cut into calls of at most `images_per_call`.  Returns [[index, ...], ...]."""
+        buckets = {}
+        for i, s in enumerate(latent_shapes):
+            buckets.setdefault(tuple(s), []).append(i)
+        p = max(1, int(images_per_call))
+        return [idx[k:k + p] for idx in buckets.values() for k in range(0, len(idx), p)]
+
+    @staticmethod
+    def decode_threads() -> int:
+        """Size of `compute_worklist`'s decode pool: OMP_NUM_THREADS if set (the CPUs a rank may use), else 4."""
+        try:
+            return max(1, int(os.environ.get("OMP_NUM_THREADS", "")))
+        except ValueError:
+            return 4
+
+    def _decode(self, path: str):
+        """Pixels of one work-list image: (uint8 HWC RGB array, None) for the device resize, or (None, [1,3,H,W] fp32) for the
+        modes PIL does not resample like RGB ("P" and "1" take NEAREST, "RGBA"/"LA" premultiply alpha, CMYK and the wide
+        modes resample before their conversion): those keep the host path of `compute` exactly.  "L" is resampled per
+        channel with the same integer arithmetic, so converting it to RGB first gives the same bytes."""
+        import PIL.Image
+        with PIL.Image.open(path) as im:
+            if im.mode in ("RGB", "L"):
+                return np.asarray(im if im.mode == "RGB" else im.convert("RGB")), None
+            return None, self.load_image(self.rescale(im))
+
+    @torch.no_grad()
+    def compute_worklist(self, lines, images_per_call: int = 8, vae_noise=None, prefetch: int = 1):
+        """`compute_submission` for real work lists, whose lines rarely share a latent shape (the reference writes them round-robin
+        over categories, compute.py:300-341, and rescales cars / places to a fixed short side with a free long side,
+        compute.py:165-180).  Writes the same `<typicality_path>/<stem>.npy` files, bit-equal to `compute`'s; returns their
+        paths in list order.
+          1. a header pass (PIL reads no pixels) gives every line's rescaled size and latent shape;
+          2. lines are grouped by latent shape and every bucket is flushed in calls of at most `images_per_call` through
+             `compute_losses_batch` (`worklist_plan`); the output order is free: every image has its own file and its own
+             `manual_seed(seed)` draws (compute.py:139-141);
+          3. per call, the images are decoded on the host by a pool of `decode_threads()` threads (PIL releases the GIL), one
+             `dm_resize_lanczos` launch per pixel size does the LANCZOS rescale + `to_tensor * 2 - 1` on the GPU (bit-equal to
+             `load_image(rescale(img))`; datasets without a rescale rule run only the normalisation), and one `dm_vae_encode`
+             per pixel size encodes them (two widths can share a latent shape through int()/ceil).
+        Memory: decoded pixels of at most 1 + `prefetch` calls are held on the host (the call being prepared and the calls
+        decoding ahead); one call's images and latents on the device; nothing else outlives its call.
+        `vae_noise`: {path: posterior draw [1,4,h,w]}, as `compute`'s.  Without it the draws come from the global RNG image by
+        image in the order of the calls (bucket order), not the list order `compute_submission` uses; the reference's draw is
+        unseeded anyway (compute.py:137).  `last_worklist_calls` keeps the plan of the last run (line indices per call)."""
+        import PIL.Image
+        from concurrent.futures import ThreadPoolExecutor
+        assert self.typicality_path is not None and self.country_embeds is not None, "scorer built without D's arguments"
+        items = [tuple(l.strip().split(",")) if isinstance(l, str) else tuple(l) for l in lines]
+        sizes = []
+        for path, _ in items:
+            with PIL.Image.open(path) as im:
+                sizes.append(self.rescale_size(self.which, im.width, im.height) if self.which in ("cars", "places") else im.size)
+        calls = self.worklist_plan([(h // 8, w // 8) for w, h in sizes], images_per_call)
+        resample = self.which in ("cars", "places")
+        out_paths = [None] * len(items)
+        self.last_worklist_calls = [list(c) for c in calls]
+        prefetch = max(0, int(prefetch))
+        with ThreadPoolExecutor(max_workers=self.decode_threads()) as pool:
+            pending = []
+            for ci, call in enumerate(calls):
+                while len(pending) < 1 + prefetch and ci + len(pending) < len(calls):
+                    pending.append([pool.submit(self._decode, items[i][0]) for i in calls[ci + len(pending)]])
+                decoded = [f.result() for f in pending.pop(0)]
+                by_size = {}
+                for j, i in enumerate(call):
+                    by_size.setdefault(sizes[i], []).append(j)
+                lat = [None] * len(call)
+                for (w, h), js in by_size.items():
+                    on_dev = [j for j in js if decoded[j][0] is not None]
+                    px = {}
+                    if on_dev:
+                        x = self.engine.resize_lanczos([decoded[j][0] for j in on_dev], w, h, resample=resample)
+                        px.update({j: x[k:k + 1] for k, j in enumerate(on_dev)})
+                    px.update({j: decoded[j][1] for j in js if decoded[j][0] is None})
+                    noises = []
+                    for j in js:
+                        path = items[call[j]][0]
+                        nz = None if vae_noise is None else vae_noise.get(path)
+                        noises.append(nz if nz is not None else
+                                      torch.randn(1, 4, h // 8, w // 8, dtype=torch.float32).to(torch.float16))
+                    if self.batched_vae_encode:
+                        x = torch.cat([px[j].to(self.device) for j in js])
+                        z = self.encode_vae(x, torch.cat([nz.to(self.device, torch.float16) for nz in noises]))
+                        for k, j in enumerate(js):
+                            lat[j] = z[k:k + 1]
+                    else:
+                        for j, nz in zip(js, noises):
+                            lat[j] = self.encode_vae(px[j], nz)
+                decoded = px = None
+                xs = torch.cat(lat)
+                emb = torch.stack([torch.stack([self.country_embeds[items[i][1]], self.country_embeds[""]]) for i in call])   # 0 = c, 1 = null
+                grids = self.compute_losses_batch(xs, emb)                             # [n, N, 2, 4, h, w] fp16 on the host
+                for i, g in zip(call, grids):
+                    out = self.get_path(self.typicality_path, items[i][0])
+                    os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
+                    with open(out, "wb") as f:
+                        np.save(f, g.numpy())
+                    out_paths[i] = out
         return out_paths
 
     def __call__(self, path: str):

@@ -159,6 +159,27 @@ enum { DM_NORM_SIGNED = 1, DM_NORM_MAXABS = 2, DM_NORM_POSITIVE = 3, DM_NORM_SPL
 int dm_normalize_map(dm_engine* e, const void* map_dev, int64_t n, int mode, void* work_dev, void* out_dev,
                      void* out_neg_dev, void* stream);
 
+/* ---- Image rescale + normalisation (D.rescale + D.load_image, compute.py:126-132,165-180) --------------
+ * dm_resize_lanczos: `PIL.Image.resize((out_w, out_h), LANCZOS)` of `batch` uint8 RGB images followed by `to_tensor(x) * 2 - 1`,
+ *   bit-equal to PIL + TypicalityScorer.load_image.  src_dev: the images' uint8 HWC pixels (image b at desc[b].src_offset, any
+ *   source size per image); out_dev: fp32 [batch][3][out_h][out_w] in [-1,1].  tables_dev: int32, per image a horizontal and a
+ *   vertical table, each = bounds [out][2] (window start, window length) at *b_off and fixed-point weights [out][k] (22 fraction
+ *   bits, PIL's 8-bit precision) at *k_off, built on the host in float64 by PIL's precompute_coeffs + normalize_coeffs_8bpc
+ *   (typicality.lanczos_axis).  The vertical table's window starts are relative to ybox_first: the horizontal pass resamples
+ *   only source rows [ybox_first, ybox_first + tmp_rows) into tmp_dev, uint8 [batch][3][tmp_rows_max][out_w]
+ *   (tmp_rows <= tmp_rows_max).  tables_dev = NULL: no resampling, only the normalisation (every src size must equal
+ *   out_w x out_h; tmp_dev unused).  No engine handle: returns 0, 1 on a bad argument, 2 on a HIP launch error. */
+typedef struct dm_resize_desc {
+    int64_t src_offset;                 /* bytes from src_dev to the image's first pixel */
+    int32_t src_w, src_h;
+    int32_t ybox_first, tmp_rows;       /* source rows the vertical pass reads */
+    int32_t kx, ky;                     /* table row strides (max taps) of the horizontal / vertical weights */
+    int32_t xb_off, xk_off;             /* int32 offsets into tables_dev: horizontal bounds, weights */
+    int32_t yb_off, yk_off;             /* vertical bounds, weights */
+} dm_resize_desc;
+int dm_resize_lanczos(const void* src_dev, const dm_resize_desc* desc_dev, const int32_t* tables_dev, int batch, int out_w,
+                      int out_h, int tmp_rows_max, void* tmp_dev, float* out_dev, void* stream);
+
 /* Profiling support for bench.py: when enabled, every launch of the dominant (implicit-GEMM)
  * kernel is bracketed by hipEvents on the launch stream.  dm_prof_read synchronises and returns
  * the accumulated kernel milliseconds, launch count and algorithmic FLOPs since the last reset. */
