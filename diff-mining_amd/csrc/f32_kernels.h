@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+struct dm_clip_pre_desc;          // include/dm_engine.h
+
 namespace dm32 {
 
 // modes as dm::IGemmMode: 0 dense, 1 conv3x3 stride 1, 2 conv3x3 stride 2 (pad 1), 3 nearest-upsample to (OH, OW) then conv3x3,
@@ -49,6 +51,17 @@ hipError_t launch_layernorm(const float* X, int rows, int C, const float* gamma,
 hipError_t launch_clip_embed(const int32_t* ids, const float* tok, const float* pos, int rows, int T, int C, int vocab, float* out, hipStream_t s);
 hipError_t launch_clip_attention(const float* qkv, int n, int T, int heads, float* out, hipStream_t s);
 hipError_t launch_quick_gelu(float* x, long long n, hipStream_t s);
+// CLIP ViT-B/32 image tower glue (clip_vision.hip): the processor's BICUBIC resize + center crop + rescale + normalise of uint8 HWC crops
+// (layout 0: [n][3][224][224], 1: patch rows [n*49][3072] with k = (c, ky, kx)); pixel_values -> patch rows; class token + patch embeddings +
+// position embedding [n*50][C]; bidirectional attention over 50 tokens x heads of 64 on q|k|v rows [n*50][3*heads*64] (q scaled by 1/8
+// inside); the CLS rows [n][C]; row-wise x / ||x||
+hipError_t launch_clip_preprocess(const uint8_t* images, const dm_clip_pre_desc* desc, const int32_t* tables, int n, int layout, float* out,
+                                  hipStream_t s);
+hipError_t launch_clip_patchify(const float* pix, int n, float* rows, hipStream_t s);
+hipError_t launch_clip_tokens(const float* pe, const float* cls, const float* pos, int n, int C, float* x, hipStream_t s);
+hipError_t launch_clipvis_attention(const float* qkv, int n, int heads, float* out, hipStream_t s);
+hipError_t launch_clip_cls(const float* x, int n, int C, float* y, hipStream_t s);
+hipError_t launch_clip_l2norm(const float* x, int n, int C, float* y, hipStream_t s);
 hipError_t launch_silu(const float* in, float* out, long long n, hipStream_t s);
 // Timesteps(dim, flip_sin_to_cos=True, downscale_freq_shift=0): out [B][dim] = [cos | sin]
 hipError_t launch_timestep_embed(const int64_t* t, int B, int dim, float* out, hipStream_t s);

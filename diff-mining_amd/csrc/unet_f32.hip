@@ -66,6 +66,10 @@ constexpr int CL_LAYERS = 12, CL_H = 768, CL_F = 3072, CL_HEADS = 12, CL_T = 77,
 struct ClipLayer32 { Norm ln1, ln2; Conv qkv, o, fc1, fc2; };
 struct Clip32 { size_t tok = NONE, pos = NONE; ClipLayer32 layer[CL_LAYERS]; Norm final_ln; };
 
+// CLIP ViT-B/32 image tower (`CLIPModel.get_image_features` of the clustering stage, cluster.py:224-231): same layer as the text tower
+constexpr int CV_T = 50, CV_NPATCH = 49, CV_KP = 3 * 32 * 32, CV_PROJ = 512, CV_TENSORS = 200, CV_CHUNK = 512;
+struct ClipVis32 { size_t cls = NONE, pos = NONE; Conv patch; Norm pre_ln; ClipLayer32 layer[CL_LAYERS]; Norm post_ln; Conv proj; };
+
 struct T32 {                // NHWC fp32 activation in the arena
     size_t off = NONE; float* p = nullptr; int N = 0, H = 0, W = 0, C = 0;
     long long rows() const { return (long long)N * H * W; }
@@ -92,6 +96,10 @@ struct dm_f32_net {
     std::map<std::string, HostT> host_clip;
     float* cslab = nullptr; size_t cslab_floats = 0;
     Clip32 clip; bool clip_ready = false;
+    // optional CLIP ViT-B/32 image tower (dm_f32_load_clip_vision_weight / dm_f32_finalize_clip_vision)
+    std::map<std::string, HostT> host_clipv;
+    float* cvslab = nullptr; size_t cvslab_floats = 0;
+    ClipVis32 clipv; bool clipv_ready = false;
     Conv conv_in, conv_out, time1, time2, tproj_all;
     Norm norm_out;
     DownB down[NB]; Res mid_res[2]; Tfm mid_tf; UpB up[NB];
@@ -577,6 +585,74 @@ int run_clip32(dm_f32_net* e, const int32_t* ids, int n, float* out, hipStream_t
     return 0;
 }
 
+// ---- CLIP ViT-B/32 image tower: pixel_values (or uint8 crops) -> image embeds, CLIPVisionModelWithProjection op by op in fp32 -------------
+// (patch rows -> patch embedding GEMM; class token + positions; pre_layrnorm; 12 x [LN1 -> q|k|v -> attention over 50 tokens -> out_proj
+// + residual -> LN2 -> fc1 -> quick_gelu -> fc2 + residual]; CLS row -> post_layernorm -> visual_projection [-> / ||.||])
+struct ClipVisArgs {
+    const float* pix = nullptr;                                                    // [n][3][224][224], or
+    const uint8_t* images = nullptr; const dm_clip_pre_desc* desc = nullptr; const int32_t* tables = nullptr;     // crops to preprocess
+    int n = 0, normalize = 0;
+    float* embeds = nullptr;                                                       // [n][512] or nullptr
+    float* hidden = nullptr;                                                       // last_hidden_state [n][50][768] or nullptr
+};
+
+int run_clipvis32(dm_f32_net* e, const ClipVisArgs& A, hipStream_t s, bool dry) {
+    Fwd32 F{e, s, dry, e->cvslab};
+    const ClipVis32& c = e->clipv;
+    const int n = A.n, M = n * CV_T;
+    T32 rows, pe, x;
+    F_TRY(F.alloc(&rows, 1, 1, n * CV_NPATCH, CV_KP));
+    if (!dry) {
+        if (A.pix) F_HIP(e, launch_clip_patchify(A.pix, n, rows.p, s));
+        else F_HIP(e, launch_clip_preprocess(A.images, A.desc, A.tables, n, 1, rows.p, s));
+    }
+    F_TRY(F.dense(c.patch, rows, nullptr, nullptr, &pe));          // the stride-32 convolution, no bias
+    F.free(rows);
+    F_TRY(F.alloc(&x, 1, 1, M, CL_H));
+    if (!dry) F_HIP(e, launch_clip_tokens(pe.p, F.P(c.cls), F.P(c.pos), n, CL_H, x.p, s));
+    F.free(pe);
+    T32 x0;
+    F_TRY(F.layernorm(c.pre_ln, x, &x0));
+    F.free(x);
+    x = x0;
+    for (int l = 0; l < CL_LAYERS; ++l) {
+        const ClipLayer32& L = c.layer[l];
+        T32 h, qkv, a, x1, f, x2;
+        F_TRY(F.layernorm(L.ln1, x, &h));
+        F_TRY(F.dense(L.qkv, h, nullptr, nullptr, &qkv));
+        F.free(h);
+        F_TRY(F.alloc(&a, 1, 1, M, CL_H));
+        if (!dry) F_HIP(e, launch_clipvis_attention(qkv.p, n, CL_HEADS, a.p, s));
+        F.free(qkv);
+        F_TRY(F.dense(L.o, a, nullptr, &x, &x1));
+        F.free(a); F.free(x);
+        F_TRY(F.layernorm(L.ln2, x1, &h));
+        F_TRY(F.dense(L.fc1, h, nullptr, nullptr, &f));
+        F.free(h);
+        if (!dry) F_HIP(e, launch_quick_gelu(f.p, (long long)M * CL_F, s));
+        F_TRY(F.dense(L.fc2, f, nullptr, &x1, &x2));
+        F.free(f); F.free(x1);
+        x = x2;
+    }
+    if (A.hidden && !dry) F_HIP(e, hipMemcpyAsync(A.hidden, x.p, (size_t)M * CL_H * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (A.embeds) {
+        T32 cls, pooled, emb;
+        F_TRY(F.alloc(&cls, 1, 1, n, CL_H));
+        if (!dry) F_HIP(e, launch_clip_cls(x.p, n, CL_H, cls.p, s));
+        F_TRY(F.layernorm(c.post_ln, cls, &pooled));
+        F.free(cls);
+        F_TRY(F.dense(c.proj, pooled, nullptr, nullptr, &emb));
+        F.free(pooled);
+        if (!dry) {
+            if (A.normalize) F_HIP(e, launch_clip_l2norm(emb.p, n, CV_PROJ, A.embeds, s));
+            else F_HIP(e, hipMemcpyAsync(A.embeds, emb.p, (size_t)n * CV_PROJ * sizeof(float), hipMemcpyDeviceToDevice, s));
+        }
+        F.free(emb);
+    }
+    F.free(x);
+    return 0;
+}
+
 template <class RunDry>
 int ensure_arena_for32(dm_f32_net* e, hipStream_t s, const std::vector<long long>& key, RunDry run_dry) {
     size_t need;
@@ -606,6 +682,27 @@ int chunk32(int h, int w) {
 
 int ensure_arena32(dm_f32_net* e, const Args32& A, hipStream_t s) {
     return ensure_arena_for32(e, s, {0, A.B, A.H, A.W, A.up_ft_index}, [&]() { return run_forward32(e, A, s, true); });
+}
+
+// runs of at most CV_CHUNK images: the fc1 output is 614 KB per image, so the workspace is bounded whatever the call's size;
+// every row's arithmetic is independent of the rows around it, so the split does not change a bit
+int run_clipvis_chunked32(dm_f32_net* e, ClipVisArgs A, void* stream, const char* what) {
+    if (!e->clipv_ready) F_FAIL(e, "%s: CLIP vision weights not loaded (dm_f32_load_clip_vision_weight / dm_f32_finalize_clip_vision)", what);
+    if (A.n <= 0) F_FAIL(e, "%s: bad image count %d", what, A.n);
+    F_HIP(e, hipSetDevice(e->device));
+    hipStream_t s = (hipStream_t)stream;
+    const ClipVisArgs full = A;
+    for (int n0 = 0; n0 < full.n; n0 += CV_CHUNK) {
+        ClipVisArgs C = full;
+        C.n = (full.n - n0 < CV_CHUNK) ? full.n - n0 : CV_CHUNK;
+        if (full.pix) C.pix = full.pix + (size_t)n0 * CV_KP * CV_NPATCH;
+        if (full.desc) C.desc = full.desc + n0;
+        if (full.embeds) C.embeds = full.embeds + (size_t)n0 * CV_PROJ;
+        if (full.hidden) C.hidden = full.hidden + (size_t)n0 * CV_T * CL_H;
+        F_TRY(ensure_arena_for32(e, s, {3, C.n, C.pix ? 1 : 0, C.hidden ? 1 : 0, C.embeds ? 1 : 0}, [&]() { return run_clipvis32(e, C, s, true); }));
+        F_TRY(run_clipvis32(e, C, s, false));
+    }
+    return 0;
 }
 
 int run_chunked32(dm_f32_net* e, Args32 A, void* stream) {
@@ -658,6 +755,7 @@ void dm_f32_destroy(dm_f32_net* e) {
     if (e->slab) (void)hipFree(e->slab);
     if (e->vslab) (void)hipFree(e->vslab);
     if (e->cslab) (void)hipFree(e->cslab);
+    if (e->cvslab) (void)hipFree(e->cvslab);
     if (e->sched_tab) (void)hipFree(e->sched_tab);
     if (e->score_tmp) (void)hipFree(e->score_tmp);
     if (e->arena_base) (void)hipFree(e->arena_base);
@@ -1027,6 +1125,115 @@ int dm_f32_clip_encode(dm_f32_net* e, const int32_t* input_ids_dev, int n_prompt
     return 0;
 }
 
+int dm_f32_load_clip_vision_weight(dm_f32_net* e, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim) {
+    if (!e || !name || !host_ptr || !shape || ndim < 0 || ndim > 8) return 1;
+    if (e->clipv_ready) F_FAIL(e, "load_clip_vision_weight after finalize_clip_vision");
+    std::string nm(name);
+    // a full CLIPModel state dict: the text half and the logit scale are not on this path; position_ids is an index buffer
+    if (nm.rfind("text_model.", 0) == 0 || nm == "text_projection.weight" || nm == "logit_scale") return 0;
+    if (nm.size() >= 12 && nm.compare(nm.size() - 12, 12, "position_ids") == 0) return 0;
+    if (nm.rfind("vision_model.", 0) == 0) nm = nm.substr(strlen("vision_model."));
+    HostT t;
+    t.shape.assign(shape, shape + ndim);
+    size_t n = 1;
+    for (int i = 0; i < ndim; ++i) n *= (size_t)shape[i];
+    t.data.resize(n);
+    if (dtype == DM_F32) memcpy(t.data.data(), host_ptr, n * sizeof(float));
+    else if (dtype == DM_F16) { const _Float16* h = (const _Float16*)host_ptr; for (size_t i = 0; i < n; ++i) t.data[i] = (float)h[i]; }
+    else F_FAIL(e, "unsupported dtype %d for %s", dtype, name);
+    e->host_clipv[nm] = std::move(t);
+    return 0;
+}
+
+int dm_f32_finalize_clip_vision(dm_f32_net* e) {
+    if (!e) return 1;
+    if (e->clipv_ready) return 0;
+    F_HIP(e, hipSetDevice(e->device));
+    e->cur_host = &e->host_clipv;
+    e->blob.clear();
+    struct Reset { dm_f32_net* e; ~Reset() { e->cur_host = nullptr; } } reset{e};
+    ClipVis32& c = e->clipv;
+    {
+        HostT* cls = get(e, "embeddings.class_embedding", {CL_H});
+        HostT* pos = get(e, "embeddings.position_embedding.weight", {CV_T, CL_H});
+        HostT* pw = get(e, "embeddings.patch_embedding.weight", {CL_H, 3, 32, 32});      // [768][(c, ky, kx)]: the patch rows' k order
+        if (!cls || !pos || !pw) return 1;
+        c.cls = put(e, cls->data.data(), cls->data.size());
+        c.pos = put(e, pos->data.data(), pos->data.size());
+        c.patch.w = put(e, pw->data.data(), pw->data.size());
+        c.patch.cin = CV_KP; c.patch.cout = CL_H; c.patch.k = 1; c.patch.b = NONE;
+    }
+    F_TRY(pack_norm(e, "pre_layrnorm", CL_H, &c.pre_ln));
+    for (int l = 0; l < CL_LAYERS; ++l) {
+        ClipLayer32& L = c.layer[l];
+        const std::string b = "encoder.layers." + std::to_string(l);
+        F_TRY(pack_norm(e, b + ".layer_norm1", CL_H, &L.ln1));
+        F_TRY(pack_stack(e, {b + ".self_attn.q_proj", b + ".self_attn.k_proj", b + ".self_attn.v_proj"}, CL_H, CL_H, &L.qkv));
+        std::vector<float> qb;
+        for (const char* leaf : {".self_attn.q_proj", ".self_attn.k_proj", ".self_attn.v_proj"}) {
+            HostT* bt = get(e, b + leaf + ".bias", {CL_H});
+            if (!bt) return 1;
+            qb.insert(qb.end(), bt->data.begin(), bt->data.end());
+        }
+        L.qkv.b = put(e, qb.data(), qb.size());
+        F_TRY(pack_dense(e, b + ".self_attn.out_proj", CL_H, CL_H, false, true, &L.o));
+        F_TRY(pack_norm(e, b + ".layer_norm2", CL_H, &L.ln2));
+        F_TRY(pack_dense(e, b + ".mlp.fc1", CL_F, CL_H, false, true, &L.fc1));
+        F_TRY(pack_dense(e, b + ".mlp.fc2", CL_H, CL_F, false, true, &L.fc2));
+    }
+    F_TRY(pack_norm(e, "post_layernorm", CL_H, &c.post_ln));
+    F_TRY(pack_dense(e, "visual_projection", CV_PROJ, CL_H, false, false, &c.proj));
+    for (auto& kv : e->host_clipv)
+        if (!kv.second.used) F_FAIL(e, "unexpected tensor in the CLIP vision state dict: %s", kv.first.c_str());
+    if (e->host_clipv.size() != CV_TENSORS) F_FAIL(e, "expected %d CLIP vision tensors, got %zu", CV_TENSORS, e->host_clipv.size());
+    e->cvslab_floats = e->blob.size();
+    F_HIP(e, hipMalloc((void**)&e->cvslab, e->cvslab_floats * sizeof(float)));
+    F_HIP(e, hipMemcpy(e->cvslab, e->blob.data(), e->cvslab_floats * sizeof(float), hipMemcpyHostToDevice));
+    e->blob.clear(); e->blob.shrink_to_fit();
+    e->host_clipv.clear();
+    e->clipv_ready = true;
+    return 0;
+}
+
+int dm_f32_clip_preprocess(dm_f32_net* e, const void* images_u8_dev, const dm_clip_pre_desc* descs_dev, const int32_t* tables_dev,
+                           int n_patches, void* out_pixel_values_dev, void* stream) {
+    if (!e) return 1;
+    if (!images_u8_dev || !descs_dev || !tables_dev || !out_pixel_values_dev || n_patches <= 0) F_FAIL(e, "dm_f32_clip_preprocess: bad argument");
+    F_HIP(e, hipSetDevice(e->device));
+    for (int n0 = 0; n0 < n_patches; n0 += 65535) {
+        const int n = (n_patches - n0 < 65535) ? n_patches - n0 : 65535;
+        F_HIP(e, launch_clip_preprocess((const uint8_t*)images_u8_dev, descs_dev + n0, tables_dev, n, 0,
+                                        (float*)out_pixel_values_dev + (size_t)n0 * CV_KP * CV_NPATCH, (hipStream_t)stream));
+    }
+    return 0;
+}
+
+int dm_f32_clip_image_features(dm_f32_net* e, const void* pixel_values_dev, int n, int normalize, void* out_f32_dev, void* stream) {
+    if (!e) return 1;
+    if (!pixel_values_dev || !out_f32_dev) F_FAIL(e, "dm_f32_clip_image_features: bad argument");
+    ClipVisArgs A;
+    A.pix = (const float*)pixel_values_dev; A.n = n; A.normalize = normalize != 0; A.embeds = (float*)out_f32_dev;
+    return run_clipvis_chunked32(e, A, stream, "dm_f32_clip_image_features");
+}
+
+int dm_f32_clip_vision_hidden(dm_f32_net* e, const void* pixel_values_dev, int n, void* out_f32_dev, void* stream) {
+    if (!e) return 1;
+    if (!pixel_values_dev || !out_f32_dev) F_FAIL(e, "dm_f32_clip_vision_hidden: bad argument");
+    ClipVisArgs A;
+    A.pix = (const float*)pixel_values_dev; A.n = n; A.hidden = (float*)out_f32_dev;
+    return run_clipvis_chunked32(e, A, stream, "dm_f32_clip_vision_hidden");
+}
+
+int dm_f32_clip_patch_features(dm_f32_net* e, const void* images_u8_dev, const dm_clip_pre_desc* descs_dev, const int32_t* tables_dev,
+                               int n_patches, int normalize, void* out_f32_dev, void* stream) {
+    if (!e) return 1;
+    if (!images_u8_dev || !descs_dev || !tables_dev || !out_f32_dev) F_FAIL(e, "dm_f32_clip_patch_features: bad argument");
+    ClipVisArgs A;
+    A.images = (const uint8_t*)images_u8_dev; A.desc = descs_dev; A.tables = tables_dev;
+    A.n = n_patches; A.normalize = normalize != 0; A.embeds = (float*)out_f32_dev;
+    return run_clipvis_chunked32(e, A, stream, "dm_f32_clip_patch_features");
+}
+
 int dm_f32_prof_enable(dm_f32_net* e, int on) {
     if (!e) return 1;
     e->prof = on != 0;
@@ -1061,7 +1268,7 @@ int dm_f32_prof_read(dm_f32_net* e, double* gemm_ms, double* gemm_flops, int64_t
 
 int dm_f32_memory(dm_f32_net* e, size_t* weights_bytes, size_t* arena_bytes) {
     if (!e) return 1;
-    if (weights_bytes) *weights_bytes = (e->slab_floats + e->vslab_floats + e->cslab_floats) * sizeof(float);
+    if (weights_bytes) *weights_bytes = (e->slab_floats + e->vslab_floats + e->cslab_floats + e->cvslab_floats) * sizeof(float);
     if (arena_bytes) *arena_bytes = e->arena_cap;
     return 0;
 }

@@ -10,7 +10,8 @@ argument meaning and its output `[1, C, H/16, W/16]` (for up_ft_index=1):
     padding="max_length", CLIP text tower, last hidden state) when the featurizer was built with a tokenizer and the
     engine holds CLIP text weights, or the CLIP hidden states `[1,77,768]` themselves.
 `patch_embeddings` is the DIFT branch of `Cluster.compute_embeddings` (cluster.py:288-299) with a
-per-image cache of the feature map.
+per-image cache of the feature map; `patch_features` mirrors its whole `feature_which` dispatch ('clip', 'dift-T',
+'clip+dift-T'), the CLIP branch on the fp32 net's ViT-B/32 image tower.
 
 Arithmetic: the reference's featuriser is fp32 end to end (dift.py:197-199: no torch_dtype; :191: no autocast).  Built over a
 `UNetEngineF32` the U-Net runs in that arithmetic (`self.dtype == torch.float32`, matches the CPU oracle in fp32 mode to ~1e-6); built over
@@ -194,3 +195,53 @@ class SDFeaturizer:
         if self.aux is None:
             raise ValueError("patch_embeddings needs the fp16 engine's patch kernel: SDFeaturizer(f32_net, aux=fp16_engine)")
         return self.aux.patch_embed(feat, feature_boxes(boxes_px, image_hw, (fh, fw)))
+
+
+def parse_feature_which(feature_which: str) -> Tuple[bool, bool, Optional[int]]:
+    """`Cluster.compute_embeddings`' reading of feature_which (cluster.py:245-253): 'clip', 'dift-T' or 'clip+dift-T' ->
+    (clip, dift, T)."""
+    parts = feature_which.split("+")
+    clip = "clip" in parts
+    difts = [p for p in parts if p.startswith("dift-")]
+    if len(parts) != int(clip) + len(difts) or len(difts) > 1 or (clip and parts[0] != "clip") or not (clip or difts):
+        raise ValueError(f"feature_which must be 'clip', 'dift-T' or 'clip+dift-T', got {feature_which!r}")
+    t = None
+    if difts:
+        try:
+            t = int(difts[0].split("-", 1)[1])
+        except ValueError:
+            raise ValueError(f"bad DIFT timestep in {feature_which!r}") from None
+    return clip, bool(difts), t
+
+
+@torch.no_grad()
+def patch_features(feature_which: str, image, boxes, prompt=None, featurizer: Optional[SDFeaturizer] = None,
+                   clip_net: Optional[UNetEngineF32] = None, feat=None, ensemble_size: int = 8, generator=None) -> torch.Tensor:
+    """The per-patch features of `Cluster.compute_embeddings` (cluster.py:243-310) for all boxes of ONE image, fp32 on the GPU:
+      * 'clip'        [P, 512]:  `embed(image.convert('RGB').crop(box))`, the L2-normalised CLIP ViT-B/32 image features
+                                 (clip_net.clip_patch_features; needs load_clip_vision_state_dict on clip_net);
+      * 'dift-T'      [P, 1280]: the DIFT map of the whole image at timestep T, window mean, L2-normalised (featurizer.patch_embeddings);
+      * 'clip+dift-T' [P, 1792]: the two concatenated, CLIP first (cluster.py:282).
+    image: uint8 HWC RGB array or PIL image (`Cluster.load_image`'s output); boxes: (x_start, y_start, x_end, y_end) with x = rows.
+    `feat` may carry the image's DIFT map [1, C, h, w] when the caller holds it; otherwise it is computed from the image with
+    `prompt` (the featurizer's forward: VAE encode, `ensemble_size` draws, up_ft_index 1)."""
+    clip, dift, t = parse_feature_which(feature_which)
+    from . import resample as RS
+    img = RS.check_clip_image(image)
+    boxes = [tuple(int(v) for v in b) for b in boxes]
+    for b in boxes:
+        RS.clip_crop_box(img.shape[:2], b)
+    out = []
+    if clip:
+        if clip_net is None:
+            raise ValueError(f"{feature_which!r} needs clip_net: a UNetEngineF32 holding the CLIP vision weights")
+        out.append(clip_net.clip_patch_features([img], [boxes]))
+    if dift:
+        if featurizer is None:
+            raise ValueError(f"{feature_which!r} needs an SDFeaturizer")
+        if feat is None:
+            x = torch.from_numpy(img).permute(2, 0, 1).to(torch.float32)
+            x = (x / 255.0 - 0.5) * 2                                   # dift_pre (dift.py:19-21)
+            feat = featurizer.forward(x[None], prompt, t=t, up_ft_index=1, ensemble_size=ensemble_size, generator=generator)
+        out.append(featurizer.patch_embeddings(feat, boxes, img.shape[:2]).to(torch.float32))
+    return out[0] if len(out) == 1 else torch.cat(out, dim=1)

@@ -33,7 +33,8 @@ SYMBOLS = [
     "dm_f32_unet_forward", "dm_f32_dift", "dm_f32_prof_enable", "dm_f32_prof_read", "dm_f32_memory", "dm_f32_op_gemm",
     "dm_f32_op_attention", "dm_f32_op_groupnorm", "dm_f32_op_layernorm", "dm_f32_load_vae_weight", "dm_f32_finalize_vae",
     "dm_f32_vae_encode", "dm_f32_score", "dm_f32_load_clip_weight", "dm_f32_finalize_clip", "dm_f32_clip_encode",
-    "dm_resize_lanczos",
+    "dm_resize_lanczos", "dm_f32_load_clip_vision_weight", "dm_f32_finalize_clip_vision", "dm_f32_clip_preprocess",
+    "dm_f32_clip_image_features", "dm_f32_clip_vision_hidden", "dm_f32_clip_patch_features",
 ]
 
 
@@ -160,6 +161,13 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         lib.dm_f32_finalize_clip.argtypes = [vp]
         lib.dm_f32_clip_encode.argtypes = [vp, vp, i32, i32, vp, vp]
         lib.dm_f32_score.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
+    if hasattr(lib, "dm_f32_clip_image_features"):
+        lib.dm_f32_load_clip_vision_weight.argtypes = [vp, C.c_char_p, vp, i32, C.POINTER(i64), i32]
+        lib.dm_f32_finalize_clip_vision.argtypes = [vp]
+        lib.dm_f32_clip_preprocess.argtypes = [vp, vp, vp, vp, i32, vp, vp]
+        lib.dm_f32_clip_image_features.argtypes = [vp, vp, i32, i32, vp, vp]
+        lib.dm_f32_clip_vision_hidden.argtypes = [vp, vp, i32, vp, vp]
+        lib.dm_f32_clip_patch_features.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp]
     if path is None:
         _lib = lib
     return lib
@@ -701,6 +709,110 @@ class UNetEngineF32:
         out = torch.empty(ids.shape[0], 77, 768, dtype=torch.float32, device=self.device)
         self._check(self.lib.dm_f32_clip_encode(self._h, C.c_void_p(ids.data_ptr()), ids.shape[0], 77, C.c_void_p(out.data_ptr()),
                                                 self._stream()), "dm_f32_clip_encode")
+        return out
+
+    # -- CLIP ViT-B/32 image tower: the CLIP branch of Cluster.compute_embeddings (cluster.py:224-231, 243-310) ----------------------
+    def load_clip_vision_state_dict(self, sd: Dict[str, "np.ndarray"]):
+        """sd: `CLIPVisionModelWithProjection.state_dict()` or a full `CLIPModel.state_dict()` (`openai/clip-vit-base-patch32`; the text
+        half, `logit_scale` and `position_ids` are skipped).  Checked against clip_spec.clip_vision_tensor_spec; kept in fp32."""
+        from .clip_spec import map_clip_vision_state_dict
+        try:
+            canon = map_clip_vision_state_dict(sd)
+        except ValueError as e:
+            raise EngineError(f"CLIP vision state dict: {e}") from None
+        names = {k: (k if k == "visual_projection.weight" else "vision_model." + k) for k in canon}
+        UNetEngine._load(self, self.lib.dm_f32_load_clip_vision_weight, {names[k]: v for k, v in canon.items()}, "f32_load_clip_vision_weight")
+        self._check(self.lib.dm_f32_finalize_clip_vision(self._h), "f32_finalize_clip_vision")
+        self._clip_vision_ready = True
+
+    def load_clip_vision_dir(self, path: str):
+        """A local `openai/clip-vit-base-patch32` (CLIPModel) or CLIPVisionModelWithProjection directory: `config.json` is checked
+        (clip_spec.check_clip_vision_config), then `model.safetensors` or `pytorch_model.bin` is loaded."""
+        import json
+        from .clip_spec import check_clip_vision_config
+        cfg = os.path.join(path, "config.json")
+        if not os.path.isfile(cfg):
+            raise EngineError(f"{cfg} not found")
+        try:
+            with open(cfg) as f:
+                check_clip_vision_config(json.load(f))
+        except ValueError as e:
+            raise EngineError(f"{cfg}: {e}") from None
+        st, pt = os.path.join(path, "model.safetensors"), os.path.join(path, "pytorch_model.bin")
+        if os.path.isfile(st):
+            from safetensors.numpy import load_file
+            sd = load_file(st)
+        elif os.path.isfile(pt):
+            sd = self._torch.load(pt, map_location="cpu", weights_only=True)
+        else:
+            raise EngineError(f"{path}: neither model.safetensors nor pytorch_model.bin")
+        self.load_clip_vision_state_dict(sd)
+
+    def _clip_batch(self, images, boxes):
+        """Checked uint8 images on the device + the launch's descriptors and tables (resample.clip_plan)."""
+        torch = self._torch
+        from . import resample as RS
+        if isinstance(images, np.ndarray) or hasattr(images, "convert"):
+            raise TypeError("images must be a list of uint8 HWC arrays / PIL images")
+        imgs = [RS.check_clip_image(a) for a in images]
+        if boxes is None:
+            boxes = [None] * len(imgs)
+        desc, tables, owner = RS.clip_plan(imgs, boxes)
+        if len(desc) == 0:
+            raise ValueError("no patches")
+        src = torch.from_numpy(np.concatenate([a.reshape(-1) for a in imgs])).to(self.device)
+        desc_d = torch.from_numpy(desc.view(np.uint8)).to(self.device)
+        tab_d = torch.from_numpy(tables).to(self.device)
+        return src, desc_d, tab_d, len(desc)
+
+    def clip_preprocess(self, images, boxes=None):
+        """`CLIPImageProcessor(images=[image.crop((y0, x0, y1, x1))])["pixel_values"]` (cluster.py:227) for every box of every image,
+        bit-equal to it, on the device.  images: list of uint8 HWC RGB arrays or PIL images (`Cluster.load_image`'s output); boxes:
+        per image a list of boxes (x_start, y_start, x_end, y_end; x = rows) or None for the whole image (None: every image whole).
+        Returns pixel_values [P, 3, 224, 224] fp32 on the GPU in box order."""
+        torch = self._torch
+        src, desc_d, tab_d, P = self._clip_batch(images, boxes)
+        out = torch.empty(P, 3, 224, 224, dtype=torch.float32, device=self.device)
+        self._check(self.lib.dm_f32_clip_preprocess(self._h, C.c_void_p(src.data_ptr()), C.c_void_p(desc_d.data_ptr()),
+                                                    C.c_void_p(tab_d.data_ptr()), P, C.c_void_p(out.data_ptr()), self._stream()),
+                    "dm_f32_clip_preprocess")
+        return out
+
+    def _pixel_values(self, pixel_values):
+        torch = self._torch
+        pv = torch.as_tensor(pixel_values).to(self.device, torch.float32).contiguous()
+        if pv.dim() != 4 or tuple(pv.shape[1:]) != (3, 224, 224) or pv.shape[0] < 1:
+            raise ValueError(f"pixel_values must be [n, 3, 224, 224], got {tuple(pv.shape)}")
+        return pv
+
+    def clip_image_features(self, pixel_values, normalize: bool = True):
+        """`CLIPModel.get_image_features(pixel_values)` in fp32 -> [n, 512] on the GPU; normalize=True divides by the L2 norm as
+        `Cluster.embed` does (cluster.py:229-230)."""
+        torch = self._torch
+        pv = self._pixel_values(pixel_values)
+        out = torch.empty(pv.shape[0], 512, dtype=torch.float32, device=self.device)
+        self._check(self.lib.dm_f32_clip_image_features(self._h, C.c_void_p(pv.data_ptr()), pv.shape[0], int(bool(normalize)),
+                                                        C.c_void_p(out.data_ptr()), self._stream()), "dm_f32_clip_image_features")
+        return out
+
+    def clip_vision_hidden(self, pixel_values):
+        """The vision transformer's last_hidden_state [n, 50, 768] fp32 (before post_layernorm), for parity checks."""
+        torch = self._torch
+        pv = self._pixel_values(pixel_values)
+        out = torch.empty(pv.shape[0], 50, 768, dtype=torch.float32, device=self.device)
+        self._check(self.lib.dm_f32_clip_vision_hidden(self._h, C.c_void_p(pv.data_ptr()), pv.shape[0], C.c_void_p(out.data_ptr()),
+                                                       self._stream()), "dm_f32_clip_vision_hidden")
+        return out
+
+    def clip_patch_features(self, images, boxes, normalize: bool = True):
+        """`embed(image.convert('RGB').crop(box))` (cluster.py:224-231, 308) for every box of every image in one call: preprocessing and
+        tower fused (bit-equal to clip_image_features(clip_preprocess(images, boxes))) -> [P, 512] fp32 on the GPU in box order."""
+        torch = self._torch
+        src, desc_d, tab_d, P = self._clip_batch(images, boxes)
+        out = torch.empty(P, 512, dtype=torch.float32, device=self.device)
+        self._check(self.lib.dm_f32_clip_patch_features(self._h, C.c_void_p(src.data_ptr()), C.c_void_p(desc_d.data_ptr()),
+                                                        C.c_void_p(tab_d.data_ptr()), P, int(bool(normalize)), C.c_void_p(out.data_ptr()),
+                                                        self._stream()), "dm_f32_clip_patch_features")
         return out
 
     def vae_encode(self, image, noise=None, scaling_factor: float = 0.18215, return_moments=False, draws_per_image: int = 1):

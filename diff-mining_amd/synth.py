@@ -274,6 +274,35 @@ def synth_clip_state_dict(cfg=None, seed: int = 0, dtype=np.float32) -> dict:
     return out
 
 
+def synth_clip_vision_state_dict(seed: int = 0, cfg=None, dtype=np.float32) -> dict:
+    """Synthetic CLIP ViT-B/32 image-tower tensors (`CLIPVisionModelWithProjection` names, see clip_spec.py).  Class and position
+    embeddings ~ N(0, 0.02) like synth_clip_state_dict's embeddings; the patch embedding, linear layers and projection fan-in
+    scaled; norms near identity."""
+    from .clip_spec import CLIP_B32_VISION, clip_vision_tensor_spec
+    out = {}
+    for name, shape in clip_vision_tensor_spec(cfg or CLIP_B32_VISION):
+        if name in ("embeddings.class_embedding", "embeddings.position_embedding.weight"):
+            z = hash_normal("clipv." + name, int(np.prod(shape)), seed)
+            t = (0.02 * z).astype(np.float32).astype(np.float16).astype(np.float32).reshape(shape)
+        else:
+            t = synth_tensor("clipv." + name, shape, seed)
+        key = name if name == "visual_projection.weight" else "vision_model." + name
+        out[key] = t if dtype == np.float32 else t.astype(dtype)
+    return out
+
+
+def synth_clip_pixel_values(n: int, seed: int = 0) -> np.ndarray:
+    """Deterministic processor-like input [n, 3, 224, 224] fp32: a smooth per-image pattern plus noise, in the range the processor
+    produces ((x - mean) / std of x in [0, 1], about [-1.8, 2.2])."""
+    u = hash_uniform("input.clip_pixels", n * 3 * 224 * 224, seed).reshape(n, 3, 224, 224)
+    yy, xx = np.meshgrid(np.linspace(0.0, 1.0, 224), np.linspace(0.0, 1.0, 224), indexing="ij")
+    base = 0.5 + 0.4 * np.sin(3.0 * xx + 5.0 * yy + np.arange(n * 3).reshape(n, 3, 1, 1))
+    x = np.clip(0.7 * base + 0.3 * u, 0.0, 1.0).astype(np.float32)
+    mean = np.array([0.48145466, 0.4578275, 0.40821073], dtype=np.float32).reshape(1, 3, 1, 1)
+    std = np.array([0.26862954, 0.26130258, 0.27577711], dtype=np.float32).reshape(1, 3, 1, 1)
+    return np.ascontiguousarray((x - mean) / std)
+
+
 def synth_token_ids(n: int, cfg=None, seed: int = 3) -> np.ndarray:
     """[n, 77] int64 prompts shaped like the tokenizer's output (compute.py:35-37): BOS, a few random
     tokens, EOS, then EOS padding (`padding="max_length"` pads CLIP prompts with the EOS id)."""

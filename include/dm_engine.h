@@ -447,6 +447,44 @@ int dm_f32_vae_encode(dm_f32_net* e, const void* image_dev, const void* noise_de
 int dm_f32_load_clip_weight(dm_f32_net* e, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim);
 int dm_f32_finalize_clip(dm_f32_net* e);
 int dm_f32_clip_encode(dm_f32_net* e, const int32_t* input_ids_dev, int n_prompts, int seq_len, void* out_f32_dev, void* stream);
+/* optional CLIP ViT-B/32 image tower in fp32: `CLIPModel("openai/clip-vit-base-patch32").get_image_features` of the clustering stage
+ * (`Cluster.embed`, cluster.py:224-231; the reference loads it without a dtype and runs it without autocast) — CLIPVisionModelWithProjection:
+ * stride-32 patch embedding (no bias), class token + position embedding, pre_layrnorm, 12 layers (LN1 -> q|k|v -> bidirectional attention
+ * over 50 tokens x 12 heads of 64 -> out_proj + residual -> LN2 -> fc1 -> quick_gelu -> fc2 + residual), post_layernorm of the CLS token,
+ * visual_projection 768 -> 512 (no bias); fp32 GEMMs on the fp32 matrix cores, calls split into runs of at most 512 images.
+ * Weights: `CLIPVisionModelWithProjection` or full `CLIPModel` state-dict names (`vision_model.*`, `visual_projection.weight`;
+ * `text_model.*`, `text_projection.weight`, `logit_scale` and `position_ids` are ignored); finalize checks all 200 tensors and shapes. */
+int dm_f32_load_clip_vision_weight(dm_f32_net* e, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim);
+int dm_f32_finalize_clip_vision(dm_f32_net* e);
+/* `CLIPImageProcessor` (PIL backend) of `batch` crops on the device, bit-equal to it: BICUBIC shortest-edge resize to 224 (PIL's 8-bit
+ * two passes, a pass skipped when its axis keeps its size), center crop 224 x 224, `(u8.astype(float64) * (1/255)).astype(float32)`,
+ * `(x - OPENAI_CLIP_MEAN) / OPENAI_CLIP_STD` in fp32.  images_u8_dev: uint8 HWC RGB images (any sizes) at desc.src_offset; desc.crop_*:
+ * the crop in source pixels (col = PIL x); tables_dev: int32 BICUBIC tables (bounds [224][2] = window start relative to the crop, length;
+ * weights [224][k] with 22 fraction bits) of the 224 output columns (xb_off, xk_off, stride kx) and rows (yb_off, yk_off, stride ky) the
+ * crop keeps, built on the host (resample.bicubic_axis); flags: DM_CLIP_NEED_H / DM_CLIP_NEED_V, the passes PIL runs (a skipped pass
+ * reads the crop from column `left` / row `top` on).  out_pixel_values_dev: fp32 [n_patches, 3, 224, 224]. */
+#define DM_CLIP_NEED_H 1
+#define DM_CLIP_NEED_V 2
+typedef struct dm_clip_pre_desc {
+    int64_t src_offset;                 /* bytes from images_u8_dev to the image's first pixel */
+    int32_t src_w, src_h;
+    int32_t crop_col0, crop_row0, crop_w, crop_h;
+    int32_t left, top;                  /* center-crop offsets in the resized crop */
+    int32_t kx, ky;                     /* weight row strides (max taps) */
+    int32_t xb_off, xk_off, yb_off, yk_off;
+    int32_t flags, pad;
+} dm_clip_pre_desc;
+int dm_f32_clip_preprocess(dm_f32_net* e, const void* images_u8_dev, const dm_clip_pre_desc* descs_dev, const int32_t* tables_dev,
+                           int n_patches, void* out_pixel_values_dev, void* stream);
+/* `get_image_features(pixel_values)` (normalize = 0) or that divided by its L2 norm (normalize = 1, `embed`'s
+ * `features / features.norm(dim=-1, keepdim=True)`): pixel_values_dev fp32 [n, 3, 224, 224] -> out_f32_dev fp32 [n, 512] */
+int dm_f32_clip_image_features(dm_f32_net* e, const void* pixel_values_dev, int n, int normalize, void* out_f32_dev, void* stream);
+/* the vision transformer's last_hidden_state (before post_layernorm): pixel_values_dev [n, 3, 224, 224] -> out_f32_dev [n, 50, 768] */
+int dm_f32_clip_vision_hidden(dm_f32_net* e, const void* pixel_values_dev, int n, void* out_f32_dev, void* stream);
+/* dm_f32_clip_preprocess + dm_f32_clip_image_features in one call: the preprocessing writes the patch rows of the embedding GEMM
+ * directly; bit-equal to the two calls */
+int dm_f32_clip_patch_features(dm_f32_net* e, const void* images_u8_dev, const dm_clip_pre_desc* descs_dev, const int32_t* tables_dev,
+                               int n_patches, int normalize, void* out_f32_dev, void* stream);
 int dm_f32_prof_enable(dm_f32_net* e, int on);
 int dm_f32_prof_read(dm_f32_net* e, double* gemm_ms, double* gemm_flops, int64_t* gemm_launches, double* attn_ms,
                      double* attn_flops, int64_t* attn_launches);
