@@ -366,41 +366,63 @@ bool attention_qk64_supports(const AttnParams& p);
 hipError_t launch_attention_pp(const AttnParams& p, int variant, hipStream_t s);   // attention_pp.hip
 bool attention_pp_supports(const AttnParams& p);
 
-hipError_t launch_attention(const AttnParams& p, hipStream_t s) {
-    if (p.Tq <= 0 || p.Tk <= 0 || p.B <= 0) return hipErrorInvalidValue;
-    // long head_dim-40 / 80 self-attention: software-pipelined variants (DM_ATTN_PIPE=0 disables)
-    if (option(OPT_ATTN_CROSS) && attention_cross_supports(p)) return launch_attention_cross(p, s);   // 77-key cross-attention
-    if (option(OPT_ATTN_CROSS) && attention_d160_cross_supports(p)) return launch_attention_d160_cross(p, s);      // ... at head_dim 160 (r06)
-    const int pipe = option(OPT_ATTN_PIPE);
-    if (p.q_mod > 0) {                       // only the generic and the 77-key kernels index Q modulo (cross-attention; handled above / below)
-        switch (p.D) { case 40: return launch_t<40, 2>(p, s); case 80: return launch_t<80, 2>(p, s); case 160: return launch_t<160, 2>(p, s); default: return hipErrorInvalidValue; }
+static AttnRoute generic_route(int D) {
+    switch (D) {
+        case 40: return ATTN_ROUTE_GENERIC40;
+        case 80: return ATTN_ROUTE_GENERIC80;
+        case 160: return ATTN_ROUTE_GENERIC160;
+        default: return ATTN_ROUTE_NONE;
     }
+}
+
+AttnRoute attention_route(const AttnParams& p) {
+    if (p.Tq <= 0 || p.Tk <= 0 || p.B <= 0) return ATTN_ROUTE_NONE;
+    // long head_dim-40 / 80 self-attention: software-pipelined variants (DM_ATTN_PIPE=0 disables)
+    if (option(OPT_ATTN_CROSS) && attention_cross_supports(p)) return ATTN_ROUTE_CROSS;              // 77-key cross-attention
+    if (option(OPT_ATTN_CROSS) && attention_d160_cross_supports(p)) return ATTN_ROUTE_D160_CROSS;    // ... at head_dim 160 (r06)
+    const int pipe = option(OPT_ATTN_PIPE);
+    if (p.q_mod > 0) return generic_route(p.D);   // only the generic and the 77-key kernels index Q modulo (cross-attention; handled above)
     // the anti-phase kernel everywhere it applies (A/B): 10 / 12 = three wave sets without / with static priorities; 9 = the r04 dispatch.
     // set_option() admits no other value (a stray value used to select timing-only ablation instantiations)
-    if ((pipe == 10 || pipe == 12) && attention_pp_supports(p)) return launch_attention_pp(p, pipe, s);
-    if (pipe == 5 && attention_qk32_supports(p)) return launch_attention_qk32(p, s);      // r06: QK^T on 32x32x16 wherever it applies (A/B)
-    if (pipe == 6 && attention_qk64_supports(p)) return launch_attention_qk64(p, s);      // two query sets per wave wherever it applies (A/B)
+    if ((pipe == 10 || pipe == 12) && attention_pp_supports(p)) return pipe == 10 ? ATTN_ROUTE_PP10 : ATTN_ROUTE_PP12;
+    if (pipe == 5 && attention_qk32_supports(p)) return ATTN_ROUTE_QK32;      // r06: QK^T on 32x32x16 wherever it applies (A/B)
+    if (pipe == 6 && attention_qk64_supports(p)) return ATTN_ROUTE_QK64;      // two query sets per wave wherever it applies (A/B)
 #ifdef DM_ATTN_PP_ABLATE
-    if (pipe >= 4 && pipe != 9 && attention_pp_supports(p)) return launch_attention_pp(p, pipe, s);        // debug library only
+    if (pipe >= 4 && pipe != 9 && attention_pp_supports(p)) return ATTN_ROUTE_PP_ABLATE;        // debug library only
 #endif
     // default: the three-set anti-phase kernel where it measured faster (>= 8192 keys: the 128x128 level of a 1024-pixel image, -4...6 %
     // per launch; bit-identical to attn_pipe_kernel) and its 384-query blocks waste < 2 % of their rows; attn_pipe = 2 / 3 keep the r04 kernels
     if (pipe == 1 && p.Tk >= 8192 && attention_pp_supports(p) && (long long)((p.Tq + 383) / 384) * 384 * 50 <= 51LL * p.Tq)
-        return launch_attention_pp(p, 12, s);
+        return ATTN_ROUTE_PP12;
     // head_dim 40 on two 32-query sets per wave (attention_qk64.hip: qk32's arithmetic, bit-identical, with the K / V^T fragment reads
     // and LDS-DMA pieces shared by both sets; profiles/qk64_ab_attn.txt); attn_pipe = 5 keeps attention_qk32.hip, 9 / 2 attn_pipe_kernel
-    if (pipe == 1 && attention_qk64_supports(p)) return launch_attention_qk64(p, s);
-    if (pipe && attention_pipe_supports(p)) return launch_attention_pipe(p, s);
-    if ((pipe == 1 || pipe >= 3) && attention_pipe80_supports(p)) return launch_attention_pipe80(p, s);     // attn_pipe = 2: head_dim 40 only (A/B)
+    if (pipe == 1 && attention_qk64_supports(p)) return ATTN_ROUTE_QK64;
+    if (pipe && attention_pipe_supports(p)) return ATTN_ROUTE_PIPE;
+    if ((pipe == 1 || pipe >= 3) && attention_pipe80_supports(p)) return ATTN_ROUTE_PIPE80;     // attn_pipe = 2: head_dim 40 only (A/B)
     // head_dim 160 (r06): eight waves sharing one (sample, head)'s K / V, <= 256 registers; bit-identical to the generic kernel.  attn_pipe = 9 / 2
     // keep the generic kernel (A/B)
-    if ((pipe == 1 || pipe == 5 || pipe == 6) && attention_d160_supports(p)) return launch_attention_d160(p, s);
-    switch (p.D) {
-        case 40: return launch_t<40, 2>(p, s);
-        case 80: return launch_t<80, 2>(p, s);
-        case 160: return launch_t<160, 2>(p, s);
-        default: return hipErrorInvalidValue;
+    if ((pipe == 1 || pipe == 5 || pipe == 6) && attention_d160_supports(p)) return ATTN_ROUTE_D160;
+    return generic_route(p.D);
+}
+
+hipError_t launch_attention(const AttnParams& p, hipStream_t s) {
+    switch (attention_route(p)) {
+        case ATTN_ROUTE_CROSS: return launch_attention_cross(p, s);
+        case ATTN_ROUTE_D160_CROSS: return launch_attention_d160_cross(p, s);
+        case ATTN_ROUTE_PP10: return launch_attention_pp(p, 10, s);
+        case ATTN_ROUTE_PP12: return launch_attention_pp(p, 12, s);
+        case ATTN_ROUTE_PP_ABLATE: return launch_attention_pp(p, option(OPT_ATTN_PIPE), s);
+        case ATTN_ROUTE_QK32: return launch_attention_qk32(p, s);
+        case ATTN_ROUTE_QK64: return launch_attention_qk64(p, s);
+        case ATTN_ROUTE_PIPE: return launch_attention_pipe(p, s);
+        case ATTN_ROUTE_PIPE80: return launch_attention_pipe80(p, s);
+        case ATTN_ROUTE_D160: return launch_attention_d160(p, s);
+        case ATTN_ROUTE_GENERIC40: return launch_t<40, 2>(p, s);
+        case ATTN_ROUTE_GENERIC80: return launch_t<80, 2>(p, s);
+        case ATTN_ROUTE_GENERIC160: return launch_t<160, 2>(p, s);
+        case ATTN_ROUTE_NONE: break;
     }
+    return hipErrorInvalidValue;
 }
 
 }  // namespace dm

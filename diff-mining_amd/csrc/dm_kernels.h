@@ -205,6 +205,15 @@ struct AttnParams {
     float scale;
 };
 hipError_t launch_attention(const AttnParams& p, hipStream_t s);
+// The kernel launch_attention runs a shape on under the current options: the one decision, exported as dm_op_attention_route (the
+// numbers are ABI; tests/test_abi.py pins the route of every product shape).  ATTN_ROUTE_NONE: the launch is refused.
+enum AttnRoute {
+    ATTN_ROUTE_NONE = 0, ATTN_ROUTE_GENERIC40 = 1, ATTN_ROUTE_GENERIC80 = 2, ATTN_ROUTE_GENERIC160 = 3, ATTN_ROUTE_QK32 = 4,
+    ATTN_ROUTE_QK64 = 5, ATTN_ROUTE_PIPE = 6, ATTN_ROUTE_PIPE80 = 7, ATTN_ROUTE_PP10 = 8, ATTN_ROUTE_PP12 = 9, ATTN_ROUTE_D160 = 10,
+    ATTN_ROUTE_D160_CROSS = 11, ATTN_ROUTE_CROSS = 12,
+    ATTN_ROUTE_PP_ABLATE = 13,           // debug library only (DM_ATTN_PP_ABLATE): the anti-phase ablation numbered by attn_pipe
+};
+AttnRoute attention_route(const AttnParams& p);
 
 // ---- K6: GroupNorm statistics + apply(+SiLU); K7: LayerNorm ----------------------------------
 // x = concat(X[...,C1], X2[...,C-C1]) NHWC.  Two kernels: per-(sample, pixel chunk, group) fp64 partial sums (one read of x),

@@ -2247,14 +2247,27 @@ int dm_op_igemm_head_rows(int M, int spatial, int Cin, int Cout, int mode) {
     return igemm_head_rows(p);
 }
 
-int dm_op_attention(void* stream, const void* Q, const void* K, const void* V, void* O, int ldq, int ldk, int ldv,
-                    int ldo, int64_t bsq, int64_t bsk, int64_t bsv, int64_t bso, const int32_t* kv_slot,
-                    int B, int heads, int Tq, int Tk, int D, float scale) {
+int dm_op_attention_slots(void* stream, const void* Q, const void* K, const void* V, void* O, int ldq, int ldk, int ldv,
+                          int ldo, int64_t bsq, int64_t bsk, int64_t bsv, int64_t bso, const int32_t* kv_slot, int slot_div, int n_slots,
+                          int q_mod, int B, int heads, int Tq, int Tk, int D, float scale) {
     AttnParams a;
     a.Q = (const f16*)Q; a.K = (const f16*)K; a.V = (const f16*)V; a.O = (f16*)O;
     a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.bsq = bsq; a.bsk = bsk; a.bsv = bsv; a.bso = bso;
-    a.kv_slot = kv_slot; a.slot_div = 0; a.B = B; a.heads = heads; a.Tq = Tq; a.Tk = Tk; a.D = D; a.scale = scale;
+    a.kv_slot = kv_slot; a.slot_div = slot_div; a.n_slots = n_slots; a.q_mod = q_mod;
+    a.B = B; a.heads = heads; a.Tq = Tq; a.Tk = Tk; a.D = D; a.scale = scale;
     return launch_attention(a, (hipStream_t)stream) == hipSuccess ? 0 : 1;
+}
+
+int dm_op_attention(void* stream, const void* Q, const void* K, const void* V, void* O, int ldq, int ldk, int ldv,
+                    int ldo, int64_t bsq, int64_t bsk, int64_t bsv, int64_t bso, const int32_t* kv_slot,
+                    int B, int heads, int Tq, int Tk, int D, float scale) {
+    return dm_op_attention_slots(stream, Q, K, V, O, ldq, ldk, ldv, ldo, bsq, bsk, bsv, bso, kv_slot, 0, 0, 0, B, heads, Tq, Tk, D, scale);
+}
+
+int dm_op_attention_route(int B, int heads, int Tq, int Tk, int D, int q_mod) {
+    AttnParams a{};
+    a.B = B; a.heads = heads; a.Tq = Tq; a.Tk = Tk; a.D = D; a.q_mod = q_mod;
+    return (int)attention_route(a);
 }
 
 int dm_op_groupnorm(void* stream, const void* X, const void* X2, int N, int HW, int C, int C1, int G, float eps,

@@ -26,7 +26,7 @@ SYMBOLS = [
     "dm_op_conv_temb_gn_blocks", "dm_op_gn_blocks", "dm_op_groupnorm_blocks", "dm_op_conv_out",
     "dm_engine_load_vae_weight", "dm_engine_finalize_vae", "dm_vae_encode", "dm_op_attention512", "dm_patch_embed",
     "dm_engine_load_clip_weight", "dm_engine_finalize_clip", "dm_clip_encode", "dm_op_igemm_splitk",
-    "dm_op_ln_stats", "dm_op_igemm_ln", "dm_reduce_typicality_batched", "dm_op_igemm_tile", "dm_op_igemm_head_rows", "dm_set_option",
+    "dm_op_ln_stats", "dm_op_igemm_ln", "dm_reduce_typicality_batched", "dm_op_igemm_tile", "dm_op_attention_route", "dm_op_attention_slots", "dm_op_igemm_head_rows", "dm_set_option",
     "dm_engine_reserve", "dm_engine_stats", "dm_op_groupnorm_conv1x1", "dm_op_igemm_shortcut", "dm_normalize_map",
     "dm_op_fold_upconv_weights", "dm_op_upconv_folded", "dm_prof_read_folded", "dm_get_option", "dm_measure_mfma_rate",
     "dm_f32_create", "dm_f32_destroy", "dm_f32_last_error", "dm_f32_load_weight", "dm_f32_finalize", "dm_f32_set_prompts",
@@ -99,6 +99,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.dm_engine_memory.argtypes = [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     lib.dm_op_igemm.argtypes = [vp] * 8 + [i32] * 11
     lib.dm_op_attention.argtypes = [vp] * 5 + [i32] * 4 + [i64] * 4 + [vp] + [i32] * 5 + [C.c_float]
+    lib.dm_op_attention_slots.argtypes = [vp] * 5 + [i32] * 4 + [i64] * 4 + [vp] + [i32] * 8 + [C.c_float]
     lib.dm_op_groupnorm.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, C.c_float, vp, vp, i32, vp]
     if hasattr(lib, "dm_op_conv_out"):
         lib.dm_op_conv_out.argtypes = [vp] * 5 + [i32] * 4 + [vp, vp]
@@ -119,6 +120,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.dm_engine_finalize_clip.argtypes = [vp]
     lib.dm_clip_encode.argtypes = [vp, vp, i32, i32, vp, vp, vp]
     lib.dm_op_igemm_tile.argtypes = [i32, i32, i32, i32]
+    lib.dm_op_attention_route.argtypes = [i32] * 6
     lib.dm_set_option.argtypes = [C.c_char_p, i32]
     if hasattr(lib, "dm_get_option"):
         lib.dm_get_option.argtypes = [C.c_char_p, C.POINTER(i32)]

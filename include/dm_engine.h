@@ -343,9 +343,19 @@ int dm_op_igemm_tile(int M, int Cin, int Cout, int mode);
 /* rows [0, r) of such a launch run on the persistent 256x320 tile (whole rounds over the CUs), rows [r, M) on the
  * 128-row tile ("igemm_tail"; r = 0 / M: one kernel for all rows).  `spatial` = OH*OW of one sample (ignored for mode 0). */
 int dm_op_igemm_head_rows(int M, int spatial, int Cin, int Cout, int mode);
+/* flash attention, head_dim 40 / 80 / 160: O[b] = softmax(scale Q[b] K[s]^T) V[s] per head, s = kv_slot[b] if kv_slot, else b */
 int dm_op_attention(void* stream, const void* Q, const void* K, const void* V, void* O, int ldq, int ldk, int ldv,
                     int ldo, int64_t bsq, int64_t bsk, int64_t bsv, int64_t bso, const int32_t* kv_slot,
                     int B, int heads, int Tq, int Tk, int D, float scale);
+/* the same with the engine's index rules: s = kv_slot[b] if kv_slot, else b / slot_div if slot_div > 0, else b; s clamped to
+ * [0, n_slots) if n_slots > 0; sample b reads the queries of sample b % q_mod if q_mod > 0 (the shared-draw layout) */
+int dm_op_attention_slots(void* stream, const void* Q, const void* K, const void* V, void* O, int ldq, int ldk, int ldv,
+                          int ldo, int64_t bsq, int64_t bsk, int64_t bsv, int64_t bso, const int32_t* kv_slot, int slot_div, int n_slots,
+                          int q_mod, int B, int heads, int Tq, int Tk, int D, float scale);
+/* which kernel dm_op_attention runs a shape on under the current options (dm_set_option "attn_pipe" / "attn_cross"):
+ * 0 = refused, 1 / 2 / 3 = generic head_dim 40 / 80 / 160, 4 = qk32, 5 = qk64, 6 = pipe (head_dim 40), 7 = pipe80,
+ * 8 / 9 = anti-phase variants 10 / 12, 10 = d160, 11 = d160_cross, 12 = cross (77-key, head_dim 40 / 80) */
+int dm_op_attention_route(int B, int heads, int Tq, int Tk, int D, int q_mod);
 /* LayerNorm folded into a Linear (the transformer blocks' LN -> to_q/k/v, LN -> to_q, LN -> GEGLU projection):
  * dm_op_ln_stats writes (mean, rstd) per row of X [rows][C]; dm_op_igemm_ln computes
  *   Y[m][c] = rstd_m * (sum_k X[m][k] Wp[c][k] - mean_m * ln_s[c]) + ln_t[c]     (then GEGLU when epi = 1)

@@ -63,16 +63,34 @@ def op_igemm(X, W, bias=None, X2=None, temb=None, res=None, mode=0, epi=0, OH=No
     return Y
 
 
-def op_attention(Q, K, V, heads, slots=None):
-    """Q [B,Tq,C], K/V [Bk,Tk,C] fp16 cuda -> O [B,Tq,C]"""
+def attention_route(B, heads, Tq, Tk, D, q_mod=0):
+    """the kernel dm_op_attention takes for this shape under the current options (name of ATTN_ROUTES)"""
+    return ATTN_ROUTES[E.load_library().dm_op_attention_route(B, heads, Tq, Tk, D, q_mod)]
+
+
+# enum AttnRoute (dm_kernels.h; the numbers of dm_op_attention_route in include/dm_engine.h)
+ATTN_ROUTES = ["none", "generic40", "generic80", "generic160", "qk32", "qk64", "pipe", "pipe80", "pp10", "pp12", "d160",
+               "d160_cross", "cross", "pp_ablate"]
+
+
+def op_attention(Q, K, V, heads, slots=None, B=None, slot_div=0, n_slots=0, q_mod=0):
+    """Q [Bq,Tq,C], K/V [Bk,Tk,C] fp16 cuda -> O [B,Tq,C] (B = Bq unless given: with q_mod > 0, sample b reads Q[b % q_mod]);
+    K/V of sample b: slots[b], else b // slot_div if slot_div > 0, else b; clamped to [0, n_slots) if n_slots > 0"""
     lib = E.load_library()
-    B, Tq, Cc = Q.shape
+    Bq, Tq, Cc = Q.shape
+    B = Bq if B is None else B
     Tk = K.shape[1]
     D = Cc // heads
-    O = torch.empty_like(Q)
-    rc = lib.dm_op_attention(stream(), ptr(Q), ptr(K), ptr(V), ptr(O), Q.stride(1), K.stride(1), V.stride(1), Cc,
-                             Q.stride(0), K.stride(0), V.stride(0), Tq * Cc, ptr(slots), B, heads, Tq, Tk, D,
-                             float(D) ** -0.5)
+    O = torch.empty(B, Tq, Cc, dtype=Q.dtype, device=Q.device)
+    if slot_div or n_slots or q_mod:
+        rc = lib.dm_op_attention_slots(stream(), ptr(Q), ptr(K), ptr(V), ptr(O), Q.stride(1), K.stride(1), V.stride(1), Cc,
+                                       Q.stride(0), K.stride(0), V.stride(0), Tq * Cc, ptr(slots), slot_div, n_slots, q_mod,
+                                       B, heads, Tq, Tk, D, float(D) ** -0.5)
+    else:
+        assert B == Bq
+        rc = lib.dm_op_attention(stream(), ptr(Q), ptr(K), ptr(V), ptr(O), Q.stride(1), K.stride(1), V.stride(1), Cc,
+                                 Q.stride(0), K.stride(0), V.stride(0), Tq * Cc, ptr(slots), B, heads, Tq, Tk, D,
+                                 float(D) ** -0.5)
     assert rc == 0, "dm_op_attention failed"
     torch.cuda.synchronize()
     return O

@@ -113,3 +113,91 @@ def test_tap_reuse_kernels_do_not_spill():
         text = open(out).read()
     found = re.findall(r"\.name:\s+(\S*igemm_pers_kernelILi0ELb0ELi0ELb0ELb0ELb1E\S*).*?\.vgpr_spill_count:\s+(\d+)", text, re.S)
     assert len(found) == 1 and int(found[0][1]) == 0, found
+
+
+# The attention route of every product shape (the table of DESIGN.md 4m): (latent h, w) -> the self-attention layers at head_dim 40 / 80
+# / 160 (the mid block is head_dim 160 one level further down) and the 77-key cross-attention of the same query counts.
+def _levels(h, w):
+    out = [(h, w)]
+    for _ in range(3):
+        h, w = (h + 1) // 2, (w + 1) // 2
+        out.append((h, w))
+    return [a * b for a, b in out]        # tokens at head_dim 40, 80, 160 and the mid block (160)
+
+
+ATTN_ROUTE_TABLE = [
+    # latent, self D40, D80, D160 (down / up and mid)
+    ((64, 64), "qk64", "pipe80", "d160", "d160"),
+    ((64, 85), "generic40", "generic80", "generic160", "generic160"),
+    ((85, 64), "generic40", "generic80", "generic160", "generic160"),
+    ((32, 42), "generic40", "generic80", "generic160", "generic160"),
+    ((42, 32), "generic40", "generic80", "generic160", "generic160"),
+    ((32, 40), "qk64", "generic80", "d160_cross", "generic160"),      # 1280 / 320 / 80 / 20: 80 keys are inside the resident-K/V range
+    ((32, 56), "qk64", "generic80", "generic160", "generic160"),      # 1792 / 448 / 112 / 28
+]
+
+
+def _route(lib, B, heads, Tq, Tk, D, q_mod=0):
+    from tests.gpu_util import ATTN_ROUTES
+    return ATTN_ROUTES[lib.dm_op_attention_route(B, heads, Tq, Tk, D, q_mod)]
+
+
+@pytest.fixture
+def default_attn_options(lib):
+    for name in (b"attn_pipe", b"attn_cross"):
+        v = E.C.c_int(-99)
+        assert lib.dm_get_option(name, E.C.byref(v)) == 0 and v.value == 1, (name, v.value)
+    yield
+    assert lib.dm_set_option(b"attn_pipe", 1) == 0 and lib.dm_set_option(b"attn_cross", 1) == 0
+
+
+@pytest.mark.parametrize("latent,r40,r80,r160,rmid", ATTN_ROUTE_TABLE, ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else None)
+def test_attention_route_of_the_work_list_shapes(lib, default_attn_options, latent, r40, r80, r160, rmid):
+    """dm_op_attention_route is the one decision launch_attention switches on.  At the work list's latents (compute_worklist: 32 x
+    40...56 landscapes and 42 x 32 portraits of the cars rule, 64 x 85 / 85 x 64 of the places rule) Tk % 128 != 0 keeps the fast
+    self-attention kernels off, so the generic kernel runs there: a predicate change that moves any of these shapes shows here."""
+    t40, t80, t160, tmid = _levels(*latent)
+    B = 20
+    assert _route(lib, B, 8, t40, t40, 40) == r40
+    assert _route(lib, B, 8, t80, t80, 80) == r80
+    assert _route(lib, B, 8, t160, t160, 160) == r160
+    assert _route(lib, B, 8, tmid, tmid, 160) == rmid
+    # cross-attention (77 keys): the resident-K/V kernels from 256 queries at head_dim 40 / 80, at every query count at 160
+    assert _route(lib, B, 8, t40, 77, 40) == ("cross" if t40 >= 256 else "generic40")
+    assert _route(lib, B, 8, t80, 77, 80) == ("cross" if t80 >= 256 else "generic80")
+    assert _route(lib, B, 8, t160, 77, 160) == "d160_cross"
+    assert _route(lib, B, 8, tmid, 77, 160) == "d160_cross"
+    # shared-draw mode (q_mod > 0): the Q-modulo layout is read by the cross kernels and the generic kernel only
+    assert _route(lib, B, 8, t40, 77, 40, q_mod=10) == ("cross" if t40 >= 256 else "generic40")
+    assert _route(lib, B, 8, t160, 77, 160, q_mod=10) == "d160_cross"
+    assert _route(lib, B, 8, t40, t40, 40, q_mod=10) == "generic40"
+    assert _route(lib, B, 8, t160, t160, 160, q_mod=10) == ("d160_cross" if r160 == "d160_cross" else "generic160")
+    # attn_cross = 0: every cross-attention on the generic kernel
+    assert lib.dm_set_option(b"attn_cross", 0) == 0
+    for T, D in ((t40, 40), (t80, 80), (t160, 160), (tmid, 160)):
+        assert _route(lib, B, 8, T, 77, D) == f"generic{D}"
+
+
+def test_attention_route_options_move_routes_as_documented(lib, default_attn_options):
+    """The A/B values of attn_pipe at the 64 x 64 shapes and at 16384 keys (the 128 x 128 level): 9 = the r04 dispatch (attn_pipe_kernel
+    / pipe80, the generic kernel at head_dim 160), 5 = qk32, 6 = qk64, 10 / 12 = the anti-phase kernel, 2 = head_dim-40 pipelining only,
+    0 = the generic kernel everywhere; Tk = 65 / 80 are inside the resident-K/V kernels' (64, 80] range, 64 and 81 outside it."""
+    r = lambda Tq, Tk, D, B=2: _route(lib, B, 8, Tq, Tk, D)        # noqa: E731
+    assert (r(16384, 16384, 40), r(4096, 4096, 40), r(1024, 1024, 80), r(256, 256, 160), r(64, 64, 160)) == \
+        ("pp12", "qk64", "pipe80", "d160", "d160")
+    assert (r(5440, 5440, 40), r(1376, 1376, 80), r(352, 352, 160)) == ("generic40", "generic80", "generic160")
+    assert (r(256, 65, 40), r(256, 80, 80), r(24, 65, 160), r(352, 80, 160)) == ("cross", "cross", "d160_cross", "d160_cross")
+    assert (r(255, 77, 40), r(256, 64, 40), r(256, 81, 80), r(88, 64, 160), r(88, 81, 160)) == \
+        ("generic40", "generic40", "generic80", "d160", "generic160")
+    expect = {9: ("pipe", "pipe", "pipe80", "generic160", "generic160"), 5: ("qk32", "qk32", "pipe80", "d160", "d160"),
+              6: ("qk64", "qk64", "pipe80", "d160", "d160"), 10: ("pp10", "pp10", "pipe80", "generic160", "generic160"),
+              12: ("pp12", "pp12", "pipe80", "generic160", "generic160"), 2: ("pipe", "pipe", "generic80", "generic160", "generic160"),
+              3: ("pipe", "pipe", "pipe80", "generic160", "generic160"),
+              0: ("generic40", "generic40", "generic80", "generic160", "generic160")}
+    for pipe, routes in expect.items():
+        assert lib.dm_set_option(b"attn_pipe", pipe) == 0
+        got = (r(16384, 16384, 40), r(4096, 4096, 40), r(1024, 1024, 80), r(256, 256, 160), r(64, 64, 160))
+        assert got == routes, (pipe, got)
+        assert (r(4096, 77, 40), r(352, 77, 160)) == ("cross", "d160_cross")       # attn_pipe does not move cross-attention
+    assert lib.dm_set_option(b"attn_pipe", 1) == 0
+    assert r(0, 77, 40) == "none" and r(64, 64, 64) == "none" and r(64, 64, 40, B=0) == "none"

@@ -45,8 +45,14 @@ def test_igemm_identity_asymmetric():
     assert torch.equal(y.cpu().view(256, K), x.view(256, K))
 
 
-@pytest.mark.parametrize("N,H,W,Cin,Cout", [(2, 9, 7, 64, 160), (1, 16, 16, 320, 320), (3, 8, 8, 128, 640)])
-def test_igemm_conv3x3(N, H, W, Cin, Cout):
+@pytest.mark.parametrize("N,H,W,Cin,Cout,up_to", [pytest.param(*r, None, id="-".join(map(str, r))) for r in ((2, 9, 7, 64, 160), (1, 16, 16, 320, 320), (3, 8, 8, 128, 640))] + [
+                                                  # (the rows above keep the ids they had before up_to became a parameter)
+                                                  # a 64 x 85 latent's samplers at their channel counts: stride 2 64x85 -> 32x43,
+                                                  # 32x43 -> 16x22, 16x22 -> 8x11; nearest-to-skip-size 32x43 -> 64x85, 16x22 -> 32x43
+                                                  (1, 64, 85, 320, 320, None),
+                                                  pytest.param(2, 32, 43, 640, 640, (64, 85), id="2-32-43-640-640-up64x85"),
+                                                  pytest.param(2, 16, 22, 1280, 1280, (32, 43), id="2-16-22-1280-1280-up32x43")])
+def test_igemm_conv3x3(N, H, W, Cin, Cout, up_to):
     x = U.f16_randn(N, Cin, H, W, seed=5)
     w = U.f16_randn(Cout, Cin, 3, 3, seed=6, scale=(9 * Cin) ** -0.5)
     b = U.f16_randn(Cout, seed=7, scale=0.1)
@@ -74,7 +80,7 @@ def test_igemm_conv3x3(N, H, W, Cin, Cout):
     y = U.op_igemm(xg, wg, bg, mode=3, OH=2 * H, OW=2 * W)
     U.assert_close_fp16(U.to_nchw(y), ref_up, "upsample2x+conv3x3")
     # forced output size (odd latent sizes: dift.py:146-147 `upsample_size`)
-    oh, ow = 2 * H - 1, 2 * W - 1
+    oh, ow = up_to or (2 * H - 1, 2 * W - 1)
     up = F.interpolate(x.float(), size=(oh, ow), mode="nearest")
     ref_up = F.conv2d(up, w.float(), b.float(), padding=1)
     y = U.op_igemm(xg, wg, bg, mode=3, OH=oh, OW=ow)
@@ -187,19 +193,26 @@ def test_attention_cross_with_prompt_slots(D):
     U.assert_close_fp16(o, ref, f"cross-attn D={D}", rel=3e-3, abs_frac=4e-3)
 
 
-@pytest.mark.parametrize("D,Tq,B", [(40, 4096, 4), (40, 1000, 5), (80, 1024, 5), (80, 300, 3)])
-def test_attention_cross_resident_kv_kernel(D, Tq, B):
-    """The 77-key cross-attention kernel that keeps K / V of a (prompt, head) resident in LDS over all query blocks of a
-    sample (head_dim 40 / 80, Tq >= 256): ragged query counts, prompt slots, a dominating key; against fp32 SDPA and the
-    generic kernel (`attn_cross` = 0)."""
+@pytest.mark.parametrize("D,Tq,B,Tk", [pytest.param(D, Tq, B, 77, id=f"{D}-{Tq}-{B}") for D, Tq, B in ((40, 4096, 4), (40, 1000, 5), (80, 1024, 5), (80, 300, 3))] + [
+                                      # (the rows above keep the ids they had before the key count became a parameter)
+                                      (160, 352, 5, 77), (160, 88, 5, 77), (160, 24, 5, 77), (160, 1024, 3, 77),
+                                      (40, 300, 3, 65), (40, 256, 2, 80), (80, 1024, 2, 65), (80, 300, 3, 80),
+                                      (160, 88, 3, 65), (160, 352, 3, 80)])
+def test_attention_cross_resident_kv_kernel(D, Tq, B, Tk):
+    """The cross-attention kernels that keep K / V of a (prompt, head) resident in LDS over all query blocks of a sample (head_dim
+    40 / 80 from 256 queries: attention_cross.hip; head_dim 160 at every query count: attn_d160_cross_kernel, the default of every
+    1280-channel attn2): ragged query counts (352 = a whole and a ragged 256-query block at head_dim 160; 24 / 88 = the mid block of
+    the work list's latents), prompt slots, key counts at both ends of the (64, 80] range the kernels take, a dominating key in
+    the last 16-key block (keys 64...79) and one in the first; against fp32 SDPA and the generic kernel (`attn_cross` = 0)."""
     from diff_mining_amd import engine as E
     lib = E.load_library()
-    heads, Tk, P = 8, 77, 3
+    heads, P = 8, 3
     Cc = heads * D
     q = U.f16_randn(B, Tq, Cc, seed=28)
     kv = U.f16_randn(P, Tk, 2 * Cc, seed=29)
-    kv[1, 70, :Cc] = q[1, 9] * 3.0                    # one late key dominates some rows of prompt 1
     slots = torch.tensor([2, 1, 0, 1, 2][:B], dtype=torch.int32)
+    kv[1, min(70, Tk - 1), :Cc] = q[1, 9] * 3.0       # one late key (last 16-key block) dominates some rows of prompt 1
+    kv[2, 3, :Cc] = q[0, Tq - 2] * 3.0                # ... and an early one (first block) the last query block's rows of prompt 2
     k, v = kv[..., :Cc][slots.long()], kv[..., Cc:][slots.long()]
 
     def split(t, T):
@@ -208,13 +221,106 @@ def test_attention_cross_resident_kv_kernel(D, Tq, B):
     d = U.dev()
     qd, kvg, sl = q.to(d), kv.to(d), slots.to(d)
     try:
+        route = U.attention_route(B, heads, Tq, Tk, D)
         o = U.op_attention(qd, kvg[..., :Cc], kvg[..., Cc:], heads, slots=sl)
         assert lib.dm_set_option(b"attn_cross", 0) == 0
+        route_gen = U.attention_route(B, heads, Tq, Tk, D)
         o_gen = U.op_attention(qd, kvg[..., :Cc], kvg[..., Cc:], heads, slots=sl)
     finally:
         lib.dm_set_option(b"attn_cross", 1)
-    U.assert_close_fp16(o, ref, f"cross-attn resident D={D} Tq={Tq}", rel=3e-3, abs_frac=4e-3)
+    assert (route, route_gen) == ("d160_cross" if D == 160 else "cross", f"generic{D}")
+    print(f"cross-attn {route} D={D} Tq={Tq} Tk={Tk}: rel-L2 vs fp32 SDPA {U.rel_l2(o, ref):.2e} ({route_gen} {U.rel_l2(o_gen, ref):.2e})")
+    U.assert_close_fp16(o, ref, f"cross-attn resident D={D} Tq={Tq} Tk={Tk}", rel=3e-3, abs_frac=4e-3)
+    U.assert_close_fp16(o_gen, ref, f"cross-attn generic D={D} Tq={Tq} Tk={Tk}", rel=3e-3, abs_frac=4e-3)
     U.assert_close_fp16(o, o_gen.float().cpu(), f"cross-attn resident vs generic D={D}", rel=3e-3, abs_frac=4e-3)
+
+
+@pytest.mark.parametrize("attn_cross", [1, 0])
+@pytest.mark.parametrize("D,Tq", [(40, 300), (80, 256), (160, 88)])
+def test_attention_cross_shared_draw_layout_and_slot_rules(D, Tq, attn_cross):
+    """The three index rules of the engine's cross-attention that only whole-engine shared-draw runs reached before: q_mod (sample b
+    reads the queries of draw b % q_mod: B = q_mod x prompts, projected once per draw), slot_div (K/V of sample b = prompt b / slot_div,
+    no slot table) and the clamp of a slot table entry outside [0, n_slots).  Per kernel: the resident-K/V kernel (attn_cross = 1) and
+    the generic one (0); the reference applies the same rules in torch."""
+    from diff_mining_amd import engine as E
+    lib = E.load_library()
+    heads, Tk, P, Ud = 8, 77, 3, 4              # P prompts x Ud draws
+    Cc = heads * D
+    B = P * Ud
+    q_draws = U.f16_randn(Ud, Tq, Cc, seed=61)
+    q_all = U.f16_randn(B, Tq, Cc, seed=62)
+    kv = U.f16_randn(P, Tk, 2 * Cc, seed=63)
+    kv[1, 72, :Cc] = q_draws[1, 5] * 3.0
+
+    def ref(qs, kvb):                            # qs [B,Tq,Cc] per sample, kvb [B] K/V rows
+        k, v = kv[..., :Cc][kvb], kv[..., Cc:][kvb]
+
+        def split(t, T):
+            return t.float().view(B, T, heads, D).transpose(1, 2)
+        return F.scaled_dot_product_attention(split(qs, Tq), split(k, Tk), split(v, Tk)).transpose(1, 2).reshape(B, Tq, Cc)
+    d = U.dev()
+    kvg = kv.to(d)
+    K, V = kvg[..., :Cc], kvg[..., Cc:]
+    b = torch.arange(B)
+    bad = torch.tensor([P + 5, -3, 1, P, 0, 2, -1, 1, 2 * P, 0, 1, 2], dtype=torch.int32)[:B]
+    try:
+        assert lib.dm_set_option(b"attn_cross", attn_cross) == 0
+        route = U.attention_route(B, heads, Tq, Tk, D, q_mod=Ud)
+        # (asserted before any launch: a kernel that ignores q_mod would read Q rows past the Ud draws)
+        assert route == ({40: "cross", 80: "cross", 160: "d160_cross"}[D] if attn_cross else f"generic{D}"), route
+        o_qmod = U.op_attention(q_draws.to(d), K, V, heads, B=B, slot_div=Ud, n_slots=P, q_mod=Ud)
+        o_div = U.op_attention(q_all.to(d), K, V, heads, slot_div=Ud)
+        o_clamp = U.op_attention(q_all.to(d), K, V, heads, slots=bad.to(d), n_slots=P)
+    finally:
+        lib.dm_set_option(b"attn_cross", 1)
+    r_qmod = ref(q_draws[b % Ud], b // Ud)
+    r_div = ref(q_all, b // Ud)
+    r_clamp = ref(q_all, bad.long().clamp(0, P - 1))
+    for what, o, r in (("q_mod", o_qmod, r_qmod), ("slot_div", o_div, r_div), ("n_slots clamp", o_clamp, r_clamp)):
+        U.assert_close_fp16(o, r, f"{route} D={D} {what}", rel=3e-3, abs_frac=4e-3)
+    # the rules are not vacuous: the shared-draw output differs from reading every sample's own Q row b
+    assert U.rel_l2(o_qmod, ref(q_draws[b.clamp(max=Ud - 1)], b // Ud)) > 0.1
+
+
+def _sampled_softmax_ref(q, k, v, heads, rows):
+    """exact softmax attention (float64) of the query rows `rows` of every sample: q [B,Tq,Cc], k / v [B,Tk,Cc] -> [B,len(rows),Cc]"""
+    B, _, Cc = q.shape
+    D = Cc // heads
+    qs = q[:, rows].double().view(B, len(rows), heads, D).transpose(1, 2)
+    kk = k.double().view(B, -1, heads, D).transpose(1, 2)
+    vv = v.double().view(B, -1, heads, D).transpose(1, 2)
+    p = torch.softmax(qs @ kk.transpose(2, 3) * D ** -0.5, dim=-1)
+    return (p @ vv).transpose(1, 2).reshape(B, len(rows), Cc)
+
+
+@pytest.mark.parametrize("D,T,route", [(40, 5440, "generic40"), (40, 1344, "generic40"), (80, 1376, "generic80"), (80, 336, "generic80"),
+                                       (160, 352, "generic160"), (160, 88, "generic160"), (160, 24, "generic160"),
+                                       (160, 80, "d160_cross")])
+def test_attention_self_at_work_list_shapes(D, T, route):
+    """Self-attention at the token counts of the work list's latents (64 x 85 / 85 x 64: 5440 / 1376 / 352 / 88; 32 x 42 / 42 x 32:
+    1344 / 336 / 88 / 24; 32 x 40: 80 at head_dim 160), where Tk % 128 != 0 keeps the fast kernels off: the generic kernel, and at 80
+    keys the resident-K/V kernel (its (64, 80] key range holds a self-attention too).  One key dominates in the last (partial) 64-key
+    tile; a spike mid-sequence first raises the same rows' running max past the lazy-rescale threshold (8 log2 units), so both the
+    first and a second rescale happen.  Against an exact softmax on sampled query rows (all rows of the short sequences)."""
+    heads, B = 8, 2
+    Cc = heads * D
+    q = U.f16_randn(B, T, Cc, seed=71)
+    k = U.f16_randn(B, T, Cc, seed=72)
+    v = U.f16_randn(B, T, Cc, seed=73)
+    k[:, T // 2] = q[:, 7] * 2.0                       # query 7 (and the rows that correlate) meet a large logit mid-sequence ...
+    k[:, T - 3] = q[:, 7] * 4.0                        # ... and a larger one in the last tile
+    k[:, T - 1, :D] = q[:, T - 5, :D] * 3.0            # head 0 of a last-block query: its max jumps at the very last key
+    assert U.attention_route(B, heads, T, T, D) == route
+    d = U.dev()
+    o = U.op_attention(q.to(d), k.to(d), v.to(d), heads)
+    if T <= 1024:
+        rows = torch.arange(T)
+    else:
+        rows = torch.cat([torch.arange(0, 64), torch.randperm(T - 128, generator=torch.Generator().manual_seed(4))[:256] + 64,
+                          torch.arange(T - 64, T)])
+    ref = _sampled_softmax_ref(q, k, v, heads, rows)
+    r, m = U.assert_close_fp16(o.cpu()[:, rows], ref, f"self-attn {route} D={D} T={T}", rel=3e-3, abs_frac=4e-3)
+    print(f"self-attention {route} D={D} T={T} ({len(rows)} rows x {B * heads} heads): rel-L2 {r:.2e}, max|err|/max|ref| {m:.2e}")
 
 
 def test_attention_large_logits_online_softmax():
@@ -255,11 +361,14 @@ def test_attention_pipelined_kernels_ragged_queries_and_rescale(D, Tq, Tk, spike
     d = U.dev()
     qd, kd, vd = q.to(d), k.to(d), v.to(d)
     try:
+        routes = [U.attention_route(B, heads, Tq, Tk, D)]
         o = U.op_attention(qd, kd, vd, heads)
         assert lib.dm_set_option(b"attn_pipe", 0) == 0
+        routes.append(U.attention_route(B, heads, Tq, Tk, D))
         o_plain = U.op_attention(qd, kd, vd, heads)
     finally:
         lib.dm_set_option(b"attn_pipe", 1)
+    assert routes == ["qk64" if D == 40 else "pipe80", f"generic{D}"], routes     # (head_dim 40 runs qk64 by default since 728e10f)
     U.assert_close_fp16(o, ref, f"pipelined attn D={D} Tq={Tq} Tk={Tk}", rel=3e-3, abs_frac=4e-3)
     U.assert_close_fp16(o, o_plain.float().cpu(), f"pipelined vs plain D={D}", rel=3e-3, abs_frac=4e-3)
 
@@ -290,13 +399,16 @@ def test_attention_scores_on_32x32_mfma(Tq, Tk, spike):
     qd, kd, vd = q.to(d), k.to(d), v.to(d)
     try:
         assert lib.dm_set_option(b"attn_pipe", 5) == 0
+        routes = [U.attention_route(B, heads, Tq, Tk, D)]
         o = U.op_attention(qd, kd, vd, heads)
         o2 = U.op_attention(qd, kd, vd, heads)
         o1 = U.op_attention(qd[1:2].contiguous(), kd[1:2].contiguous(), vd[1:2].contiguous(), heads)
         assert lib.dm_set_option(b"attn_pipe", 9) == 0
+        routes.append(U.attention_route(B, heads, Tq, Tk, D))
         o_pipe = U.op_attention(qd, kd, vd, heads)
     finally:
         lib.dm_set_option(b"attn_pipe", 1)
+    assert routes == ["qk32", "pipe"], routes
     e32, e16 = U.rel_l2(o, ref), U.rel_l2(o_pipe, ref)
     print(f"qk32 attention Tq={Tq} Tk={Tk} spike={spike}: rel-L2 vs fp32 SDPA {e32:.2e} (attn_pipe_kernel {e16:.2e})")
     U.assert_close_fp16(o, ref, f"qk32 attn Tq={Tq} Tk={Tk}", rel=3e-3, abs_frac=4e-3)
@@ -331,12 +443,15 @@ def test_attention_head_dim_160_eight_wave_kernel(Tq, Tk, spike, B):
     qd, kd, vd = q.to(d), k.to(d), v.to(d)
     try:
         assert lib.dm_set_option(b"attn_pipe", 1) == 0
+        routes = [U.attention_route(B, heads, Tq, Tk, D)]
         o = U.op_attention(qd, kd, vd, heads)
         o1 = U.op_attention(qd[2:3].contiguous(), kd[2:3].contiguous(), vd[2:3].contiguous(), heads)
         assert lib.dm_set_option(b"attn_pipe", 9) == 0
+        routes.append(U.attention_route(B, heads, Tq, Tk, D))
         o_gen = U.op_attention(qd, kd, vd, heads)
     finally:
         lib.dm_set_option(b"attn_pipe", 1)
+    assert routes == ["d160", "generic160"], routes                  # (else the bit-equality below compares a kernel with itself)
     print(f"head_dim 160 Tq={Tq} Tk={Tk} spike={spike}: rel-L2 vs fp32 SDPA {U.rel_l2(o, ref):.2e}")
     U.assert_close_fp16(o, ref, f"d160 attn Tq={Tq} Tk={Tk}", rel=3e-3, abs_frac=4e-3)
     assert torch.equal(o, o_gen), f"not bit-equal to the generic kernel: max |diff| {(o.float() - o_gen.float()).abs().max().item():.3e}"
@@ -1293,6 +1408,11 @@ def _block_sums_torch(y2d):
     (160, 16, 16, 1280, 1280, 1, "head"),   # 2.5 rounds of 256-row tiles: the head from the epilogue, the tail rows from the output
     (96, 32, 32, 640, 640, 1, "none"),      # the 32-pixel-wide tap-reuse kernel does not emit them
     (2, 16, 16, 320, 320, 1, "none"),       # a launch the 128-row tile takes
+    # the 16 x 22 and 8 x 11 levels of a 64 x 85 latent: M is a multiple of 64, H * W (352, 88) is not, so 64-row blocks would
+    # straddle samples: no epilogue may emit them (igemm_gn_layer), and the engine takes the statistics pass (gn_blocks_ok)
+    (8, 16, 22, 1280, 1280, 1, "refused"),
+    (8, 8, 11, 1280, 1280, 1, "refused"),
+    (16, 16, 22, 640, 1280, 0, "refused"),
 ])
 def test_groupnorm_block_sums_from_the_conv1_epilogue(N, H, W, Cin, Cout, tap_reuse, expect):
     """r05: norm2's statistics as per-(64-row block, channel pair) fp32 sums.  The persistent kernels write them from conv1's epilogue
@@ -1321,6 +1441,15 @@ def test_groupnorm_block_sums_from_the_conv1_epilogue(N, H, W, Cin, Cout, tap_re
         lib.dm_set_option(b"tap_reuse", 1)
     assert torch.equal(y, y_ref)
     rows_done = done.value
+    if expect == "refused":
+        assert (H * W) % 64 != 0 and M % 64 == 0 and rows_done == 0
+        assert torch.isnan(blocks).all()                                  # nothing written
+        g = (torch.randn(Cout, generator=torch.Generator().manual_seed(45)) * 0.1 + 1).to(d)
+        be = (torch.randn(Cout, generator=torch.Generator().manual_seed(46)) * 0.1).to(d)
+        out = U.op_groupnorm(y, g, be, 32, 1e-5, True)                   # the statistics pass the engine takes at this size
+        refn = F.silu(F.group_norm(U.to_nchw(y).float(), 32, g, be, 1e-5))
+        U.assert_close_fp16(U.to_nchw(out), refn, f"groupnorm at {H}x{W}")
+        return
     if expect == "all":
         assert rows_done == M
     elif expect == "none":
