@@ -162,3 +162,27 @@ def op_upconv_folded(X, W4, bias):
     assert rc == 0, "dm_op_upconv_folded failed"
     torch.cuda.synchronize()
     return Y
+
+
+def op_attention512(q, k, v):
+    """the VAE mid block's single-head attention (head_dim 512): q / k / v [B,T,512] fp16 -> O [B,T,512] fp16 cuda.
+    Q / K / V go in as one [B,T,1536] row per token, as the engine's fused projection lays them out."""
+    lib = E.load_library()
+    B, T, Cc = q.shape
+    qkv = torch.cat([q, k, v], dim=2).contiguous().to(dev())
+    o = torch.empty(B, T, Cc, dtype=torch.float16, device=dev())
+    rc = lib.dm_op_attention512(stream(), ptr(qkv), C.c_void_p(qkv.data_ptr() + Cc * 2),
+                                C.c_void_p(qkv.data_ptr() + 2 * Cc * 2), ptr(o), B, T, 3 * Cc, Cc, float(Cc) ** -0.5)
+    assert rc == 0
+    torch.cuda.synchronize()
+    return o
+
+
+def line_rel_l2(got, ref):
+    """per latent row and per latent column: rel-L2 over the channels (and images) of `got` vs `ref` [B,C,h,w] ->
+    (rows [h], cols [w]) float64.  A global rel-L2 hides one wrong row or column of a wide grid; these do not."""
+    a, b = got.double().cpu(), ref.double().cpu()
+    d2, r2 = (a - b) ** 2, b ** 2
+    rows = (d2.sum(dim=(0, 1, 3)) / r2.sum(dim=(0, 1, 3)).clamp_min(1e-60)).sqrt()
+    cols = (d2.sum(dim=(0, 1, 2)) / r2.sum(dim=(0, 1, 2)).clamp_min(1e-60)).sqrt()
+    return rows, cols

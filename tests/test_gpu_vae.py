@@ -4,7 +4,6 @@ parity unpinned — see its header) and the committed golden fixture.
 
 Tolerances as for the U-Net: per-op rel-L2 <= 2e-3 vs torch fp32 on the same fp16
 inputs; end-to-end moments rel-L2 <= 3e-3 (2x the measured value) against the fp16-autocast emulation of the oracle."""
-import ctypes as C
 import os
 
 import numpy as np
@@ -84,17 +83,7 @@ def test_igemm64_downsample_pad0(N, H, W, C):
     U.assert_close_fp16(U.to_nchw(y), ref, "conv3x3 s2 pad(0,1,0,1)")
 
 
-def _attn512(q, k, v):
-    from diff_mining_amd import engine as E
-    lib = E.load_library()
-    B, T, Cc = q.shape
-    qkv = torch.cat([q, k, v], dim=2).contiguous().to(U.dev())          # [B,T,1536], as the engine lays it out
-    o = torch.empty(B, T, Cc, dtype=torch.float16, device=U.dev())
-    rc = lib.dm_op_attention512(U.stream(), U.ptr(qkv), C.c_void_p(qkv.data_ptr() + Cc * 2),
-                                C.c_void_p(qkv.data_ptr() + 2 * Cc * 2), U.ptr(o), B, T, 3 * Cc, Cc, float(Cc) ** -0.5)
-    assert rc == 0
-    torch.cuda.synchronize()
-    return o
+_attn512 = U.op_attention512
 
 
 @pytest.mark.parametrize("B,T", [(2, 64), (1, 256), (3, 80), (1, 1344), (1, 33)])
