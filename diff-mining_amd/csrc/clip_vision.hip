@@ -1,6 +1,7 @@
 // clip_vision.hip — the glue kernels of the fp32 CLIP ViT-B/32 image tower (dm_f32_clip_image_features, unet_f32.hip): the
-// processor's preprocessing, patch rows, token assembly, bidirectional attention over 50 tokens, the CLS gather and the L2
-// normalisation.  Every GEMM of the tower (patch embedding, q|k|v, out_proj, fc1, fc2, visual_projection) runs on gemm32.
+// processor's preprocessing, patch rows, token assembly, the CLS gather and the L2 normalisation (the attention over the 50
+// tokens is the text tower's kernel without the mask, f32_ops.hip).  Every GEMM of the tower (patch embedding, q|k|v, out_proj,
+// fc1, fc2, visual_projection) runs on gemm32.
 //
 // Preprocessing = `CLIPImageProcessor` (PIL backend) of `Cluster.embed` (cluster.py:224-231) on uint8 HWC RGB crops:
 //   * BICUBIC shortest-edge resize: PIL's 8-bit two-pass resampler (horizontal first, 8-bit intermediate, int32 accumulators
@@ -23,7 +24,7 @@ namespace {
 constexpr int kPrecisionBits = 32 - 8 - 2;        // PIL Resample.c PRECISION_BITS
 constexpr int kThreads = 256;
 constexpr int S = 224, PS = 32, GRID = S / PS, NPATCH = GRID * GRID, KP = 3 * PS * PS;     // 224 px, 7 x 7 patches of 3 x 32 x 32
-constexpr int VT = NPATCH + 1, VD = 64;           // 50 tokens, heads of 64
+constexpr int VT = NPATCH + 1;                    // 50 tokens
 
 __device__ __forceinline__ int clip8(int v) {
     v >>= kPrecisionBits;
@@ -101,51 +102,6 @@ __global__ void __launch_bounds__(kThreads) clip_tokens_kernel(const float* __re
     for (int c = threadIdx.x; c < C; c += blockDim.x) x[(size_t)row * C + c] = a[c] + b[c];
 }
 
-// bidirectional self-attention over the 50 tokens, heads of 64: one block per (image, head), one thread per query (50 of 64 lanes
-// work); qkv [n*50][3*heads*64]; q scaled by head_dim^-0.5 = 1/8 after its projection (a power of two: exact); softmax in fp32
-__global__ __launch_bounds__(64) void clipvis32_attn_kernel(const float* __restrict__ qkv, int heads, float* __restrict__ out) {
-    __shared__ float Ks[VT][VD + 1], Vs[VT][VD + 1];
-    const int h = blockIdx.x, n = blockIdx.y;
-    const int C = heads * VD;
-    const float* base = qkv + (size_t)n * VT * 3 * C + h * VD;
-    for (int i = threadIdx.x; i < VT * VD; i += blockDim.x) {
-        const int t = i / VD, d = i - t * VD;
-        Ks[t][d] = base[(size_t)t * 3 * C + C + d];
-        Vs[t][d] = base[(size_t)t * 3 * C + 2 * C + d];
-    }
-    __syncthreads();
-    const int t = threadIdx.x;
-    if (t >= VT) return;
-    float q[VD];
-#pragma unroll
-    for (int d = 0; d < VD; ++d) q[d] = base[(size_t)t * 3 * C + d] * 0.125f;
-    float sc[VT];
-    float m = -INFINITY;
-#pragma unroll
-    for (int k = 0; k < VT; ++k) {
-        float a = 0.f;
-#pragma unroll
-        for (int d = 0; d < VD; ++d) a = fmaf(q[d], Ks[k][d], a);
-        sc[k] = a;
-        m = fmaxf(m, a);
-    }
-    float l = 0.f;
-#pragma unroll
-    for (int k = 0; k < VT; ++k) { sc[k] = expf(sc[k] - m); l += sc[k]; }
-    float o[VD];
-#pragma unroll
-    for (int d = 0; d < VD; ++d) o[d] = 0.f;
-#pragma unroll
-    for (int k = 0; k < VT; ++k) {
-        const float pk = sc[k] / l;
-#pragma unroll
-        for (int d = 0; d < VD; ++d) o[d] = fmaf(pk, Vs[k][d], o[d]);
-    }
-    float* dst = out + ((size_t)n * VT + t) * C + h * VD;
-#pragma unroll
-    for (int d = 0; d < VD; ++d) dst[d] = o[d];
-}
-
 // last_hidden_state[:, 0, :] -> [n][C] (post_layernorm runs on these rows)
 __global__ void __launch_bounds__(kThreads) clip_cls_kernel(const float* __restrict__ x, int C, float* __restrict__ y) {
     const int p = blockIdx.x;
@@ -180,12 +136,6 @@ hipError_t launch_clip_patchify(const float* pix, int n, float* rows, hipStream_
 
 hipError_t launch_clip_tokens(const float* pe, const float* cls, const float* pos, int n, int C, float* x, hipStream_t s) {
     hipLaunchKernelGGL(clip_tokens_kernel, dim3(n * VT), dim3(kThreads), 0, s, pe, cls, pos, n, C, x);
-    return hipGetLastError();
-}
-
-hipError_t launch_clipvis_attention(const float* qkv, int n, int heads, float* out, hipStream_t s) {
-    if (n < 1 || n > 65535) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(clipvis32_attn_kernel, dim3(heads, n), dim3(64), 0, s, qkv, heads, out);
     return hipGetLastError();
 }
 

@@ -10,6 +10,7 @@
 #include "../../include/dm_engine.h"
 #include "dm_kernels.h"
 #include "arena.h"
+#include "weights.h"
 
 #include <cmath>
 #include <cstdio>
@@ -44,12 +45,7 @@ constexpr float GN_EPS = 1e-5f, ATTN_GN_EPS = 1e-6f, LN_EPS = 1e-5f;
 const bool DOWN_ATTN[NB] = {true, true, true, false};
 const bool UP_ATTN[NB] = {false, true, true, true};
 
-struct HostTensor {
-    std::vector<f16> data;
-    std::vector<int64_t> shape;
-    bool used = false;
-    size_t numel() const { size_t n = 1; for (auto s : shape) n *= (size_t)s; return n; }
-};
+using HostTensor = dm::HostTensorT<f16>;
 
 // packed device-side parameter handles (offsets into one weight slab, resolved to pointers)
 struct ConvW { const f16* w = nullptr; const f16* b = nullptr; int cin = 0, cout = 0, k = 0; int csc = 0; };   // csc: channels of a folded shortcut
@@ -108,11 +104,10 @@ struct ProfEv { std::vector<hipEvent_t> pairs; double flops; int kind; int M = 0
 struct dm_engine {
     int device = 0;
     std::string err;
-    std::map<std::string, HostTensor> host;
-    bool finalized = false;
+    dm::WeightSet<f16> w_unet;
+    bool finalized = false;          // the U-Net's slab, the tables and the tile counters are on the device
 
     // weights
-    char* wslab = nullptr; size_t wslab_bytes = 0;
     ConvW conv_in, conv_out, time1, time2, tproj_all;
     NormW norm_out;
     DownBlockW down[NB];
@@ -128,14 +123,12 @@ struct dm_engine {
     float* sb32_tab = nullptr;       // [1000] fp32 sqrt(1-acp)
 
     // optional CLIP text tower (dm_engine_load_clip_weight / dm_engine_finalize_clip)
-    std::map<std::string, HostTensor> host_clip;
-    ClipW clip; bool clip_ready = false;
-    char* cslab = nullptr; size_t cslab_bytes = 0;
+    dm::WeightSet<f16> w_clip;
+    ClipW clip;
 
     // optional VAE encoder (dm_engine_load_vae_weight / dm_engine_finalize_vae)
-    std::map<std::string, HostTensor> host_vae;
-    VaeW vae; bool vae_ready = false;
-    char* vslab = nullptr; size_t vslab_bytes = 0;
+    dm::WeightSet<f16> w_vae;
+    VaeW vae;
 
     // prompt K/V cache
     int n_prompts = 0;
@@ -216,10 +209,10 @@ void host_sinusoid(int t, int dim, float* out) {
 // ------------------------------------------------------------------------------------------------
 // weight packing
 // ------------------------------------------------------------------------------------------------
-struct Packer {
+struct Packer {             // one finalize: reads the staged tensors of `set`, owns the host image of its slab
     dm_engine* e;
+    dm::WeightSet<f16>& set;
     std::vector<char> blob;
-    std::map<std::string, HostTensor>* src = nullptr;      // default: the U-Net state dict
     std::vector<char> scratch;                             // operands needed only while finalize runs (freed afterwards)
     size_t put_scratch(const void* src, size_t bytes) {
         size_t off = (scratch.size() + 255) & ~(size_t)255;
@@ -233,22 +226,11 @@ struct Packer {
         memcpy(blob.data() + off, src, bytes);
         return off;
     }
-    HostTensor* get(const std::string& name, std::initializer_list<int64_t> shape) {
-        std::map<std::string, HostTensor>& m = src ? *src : e->host;
-        auto it = m.find(name);
-        if (it == m.end()) { e->err = "missing tensor: " + name; return nullptr; }
-        HostTensor& t = it->second;
-        std::vector<int64_t> want(shape);
-        if (t.shape != want) {
-            std::string s = "shape mismatch for " + name + ": got [";
-            for (auto v : t.shape) s += std::to_string(v) + ",";
-            s += "] want [";
-            for (auto v : want) s += std::to_string(v) + ",";
-            e->err = s + "]";
-            return nullptr;
-        }
-        t.used = true;
-        return &t;
+    HostTensor* get(const std::string& name, std::initializer_list<int64_t> shape) { return set.get(name, shape, e->err); }
+    int finish(const char* what, size_t expected) {
+        DM_TRY(set.finish(blob.data(), blob.size(), what, expected, e->err));
+        ++e->n_device_allocs;
+        return 0;
     }
 };
 
@@ -321,6 +303,16 @@ int pack_stack(Packer& P, const std::vector<std::string>& names, int rows_each, 
     return 0;
 }
 
+// the biases [c] of the stacked layers, concatenated (the caller puts them: CLIP scales the q part first)
+int stack_bias(Packer& P, const std::vector<std::string>& names, int c, std::vector<f16>* out) {
+    for (const std::string& n : names) {
+        HostTensor* b = P.get(n + ".bias", {c});
+        if (!b) return 1;
+        out->insert(out->end(), b->data.begin(), b->data.end());
+    }
+    return 0;
+}
+
 // GEGLU projection [8C, C]: rows permuted so that every MFMA lane holds (h0,h1,g0,g1) quads:
 // packed row rho = 16F + 4q + r  <-  r<2 ? hidden 8F+2q+r : gate 4C + 8F+2q+(r-2)
 int pack_geglu(Packer& P, const std::string& name, int c, ConvW* o) {
@@ -378,20 +370,26 @@ int pack_ln_fold(Packer& P, const std::string& ln, const std::vector<std::string
     return 0;
 }
 
-int pack_resnet(Packer& P, const std::string& name, int cin, int cout, ResW* r, std::vector<f16>& tw, std::vector<f16>& tb) {
+int pack_vae_resnet(Packer& P, const std::string& name, int cin, int cout, ResW* r) {
     r->cin = cin; r->cout = cout;
     DM_TRY(pack_norm(P, name + ".norm1", cin, &r->n1));
     DM_TRY(pack_conv3(P, name + ".conv1", cout, cin, &r->c1));
+    DM_TRY(pack_norm(P, name + ".norm2", cout, &r->n2));
+    DM_TRY(pack_conv3(P, name + ".conv2", cout, cout, &r->c2));
+    r->has_sc = (cin != cout);
+    if (r->has_sc) DM_TRY(pack_dense(P, name + ".conv_shortcut", cout, cin, true, true, &r->sc));
+    return 0;
+}
+
+// the U-Net's ResnetBlock2D = the VAE's + a time-embedding projection (rows to tw / tb, not to the blob) + conv2 with the shortcut folded in
+int pack_resnet(Packer& P, const std::string& name, int cin, int cout, ResW* r, std::vector<f16>& tw, std::vector<f16>& tb) {
     HostTensor* w = P.get(name + ".time_emb_proj.weight", {cout, TEMB});
     HostTensor* b = P.get(name + ".time_emb_proj.bias", {cout});
     if (!w || !b) return 1;
     r->temb_off = (int)tb.size();
     tw.insert(tw.end(), w->data.begin(), w->data.end());
     tb.insert(tb.end(), b->data.begin(), b->data.end());
-    DM_TRY(pack_norm(P, name + ".norm2", cout, &r->n2));
-    DM_TRY(pack_conv3(P, name + ".conv2", cout, cout, &r->c2));
-    r->has_sc = (cin != cout);
-    if (r->has_sc) DM_TRY(pack_dense(P, name + ".conv_shortcut", cout, cin, true, true, &r->sc));
+    DM_TRY(pack_vae_resnet(P, name, cin, cout, r));
     if (r->has_sc && cin % 64 == 0) {
         // conv2 with the shortcut folded in (igemm_pers_tile.h, SC): weight rows [9 * cout (tap, c) | cin], bias = b2 + b_sc
         HostTensor* w2 = P.get(name + ".conv2.weight", {cout, cout, 3, 3});
@@ -412,17 +410,6 @@ int pack_resnet(Packer& P, const std::string& name, int cin, int cout, ResW* r, 
         r->c2sc.b = as_ptr(P.put(pb.data(), pb.size() * 2));
         r->c2sc.cin = cout; r->c2sc.cout = cout; r->c2sc.k = 3; r->c2sc.csc = cin;
     }
-    return 0;
-}
-
-int pack_vae_resnet(Packer& P, const std::string& name, int cin, int cout, ResW* r) {
-    r->cin = cin; r->cout = cout; r->temb_off = 0;
-    DM_TRY(pack_norm(P, name + ".norm1", cin, &r->n1));
-    DM_TRY(pack_conv3(P, name + ".conv1", cout, cin, &r->c1));
-    DM_TRY(pack_norm(P, name + ".norm2", cout, &r->n2));
-    DM_TRY(pack_conv3(P, name + ".conv2", cout, cout, &r->c2));
-    r->has_sc = (cin != cout);
-    if (r->has_sc) DM_TRY(pack_dense(P, name + ".conv_shortcut", cout, cin, true, true, &r->sc));
     return 0;
 }
 
@@ -1466,9 +1453,7 @@ void dm_engine_destroy(dm_engine* e) {
     if (!e) return;
     (void)hipSetDevice(e->device);
     (void)hipDeviceSynchronize();
-    if (e->wslab) (void)hipFree(e->wslab);
-    if (e->vslab) (void)hipFree(e->vslab);
-    if (e->cslab) (void)hipFree(e->cslab);
+    for (f16* slab : {e->w_unet.slab, e->w_vae.slab, e->w_clip.slab}) if (slab) (void)hipFree(slab);
     if (e->arena_base) (void)hipFree(e->arena_base);
     if (e->tile_ctr) (void)hipFree(e->tile_ctr);
     if (e->slot_scratch) (void)hipFree(e->slot_scratch);
@@ -1487,22 +1472,14 @@ void dm_engine_destroy(dm_engine* e) {
 int dm_engine_load_weight(dm_engine* e, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim) {
     if (!e || !name || !host_ptr || !shape) return 1;
     if (e->finalized) DM_FAIL(e, "load_weight after finalize");
-    HostTensor t;
-    t.shape.assign(shape, shape + ndim);
-    const size_t n = t.numel();
-    t.data.resize(n);
-    if (dtype == DM_F16) memcpy(t.data.data(), host_ptr, n * 2);
-    else if (dtype == DM_F32) { const float* f = (const float*)host_ptr; for (size_t i = 0; i < n; ++i) t.data[i] = (f16)f[i]; }
-    else DM_FAIL(e, "unsupported dtype %d for %s", dtype, name);
-    e->host[name] = std::move(t);
-    return 0;
+    return dm::stage_tensor(e->w_unet.host, name, host_ptr, dtype, shape, ndim, e->err);
 }
 
 int dm_engine_finalize(dm_engine* e) {
     if (!e) return 1;
     if (e->finalized) return 0;
     DM_HIP(e, hipSetDevice(e->device));
-    Packer P{e, {}};
+    Packer P{e, e->w_unet};
     std::vector<f16> tw, tb;
     e->n_tf = 0; e->tfs.clear();
     // conv_in as a dense GEMM over the im2col rows: [C0][64], k = c*9 + ky*3 + kx (PyTorch order), zero padded
@@ -1579,16 +1556,8 @@ int dm_engine_finalize(dm_engine* e) {
     e->tproj_all.b = as_ptr(P.put(tb.data(), tb.size() * 2));
     e->tproj_all.cin = TEMB; e->tproj_all.cout = e->tproj_total; e->tproj_all.k = 1;
 
-    size_t unused = 0; std::string first_unused;
-    for (auto& kv : e->host) if (!kv.second.used) { if (!unused) first_unused = kv.first; ++unused; }
-    if (unused) DM_FAIL(e, "%zu unexpected tensors in the state dict (first: %s)", unused, first_unused.c_str());
-    if (e->host.size() != 686) DM_FAIL(e, "expected 686 tensors, got %zu", e->host.size());
-
-    // upload
-    e->wslab_bytes = P.blob.size();
-    DM_MALLOC(e, &e->wslab, e->wslab_bytes);
-    DM_HIP(e, hipMemcpy(e->wslab, P.blob.data(), e->wslab_bytes, hipMemcpyHostToDevice));
-    char* base = e->wslab;
+    DM_TRY(P.finish("U-Net", 686));
+    char* base = (char*)e->w_unet.slab;
     rebase_conv(e->conv_in, base); rebase_conv(e->conv_out, base); rebase_conv(e->time1, base); rebase_conv(e->time2, base);
     rebase_conv(e->tproj_all, base); rebase_norm(e->norm_out, base);
     for (int i = 0; i < NB; ++i) {
@@ -1612,7 +1581,6 @@ int dm_engine_finalize(dm_engine* e) {
     }
     DM_HIP(e, hipDeviceSynchronize());
     DM_HIP(e, hipFree(scratch));
-    e->host.clear();
 
     // scheduler + sinusoid tables
     {
@@ -1656,31 +1624,23 @@ int dm_engine_finalize(dm_engine* e) {
 
 int dm_engine_load_vae_weight(dm_engine* e, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim) {
     if (!e || !name || !host_ptr || !shape) return 1;
-    if (e->vae_ready) DM_FAIL(e, "load_vae_weight after finalize_vae");
+    if (e->w_vae.ready) DM_FAIL(e, "load_vae_weight after finalize_vae");
     std::string nm(name);
     if (nm.rfind("vae.", 0) == 0) nm = nm.substr(4);
     if (nm.rfind("decoder.", 0) == 0 || nm.rfind("post_quant_conv.", 0) == 0) return 0;     // not on the path
     // pre-0.15 diffusers names of the mid-block attention
     static const char* legacy[4][2] = {{".query.", ".to_q."}, {".key.", ".to_k."}, {".value.", ".to_v."}, {".proj_attn.", ".to_out.0."}};
     for (auto& l : legacy) { const size_t at = nm.find(l[0]); if (at != std::string::npos) nm.replace(at, strlen(l[0]), l[1]); }
-    HostTensor t;
-    t.shape.assign(shape, shape + ndim);
-    // legacy checkpoints store the attention projections as 1x1 convs [C, C, 1, 1]
-    if (nm.find(".attentions.0.to_") != std::string::npos && ndim == 4 && shape[2] == 1 && shape[3] == 1) t.shape.resize(2);
-    const size_t n = t.numel();
-    t.data.resize(n);
-    if (dtype == DM_F16) memcpy(t.data.data(), host_ptr, n * 2);
-    else if (dtype == DM_F32) { const float* f = (const float*)host_ptr; for (size_t i = 0; i < n; ++i) t.data[i] = (f16)f[i]; }
-    else DM_FAIL(e, "unsupported dtype %d for %s", dtype, name);
-    e->host_vae[nm] = std::move(t);
-    return 0;
+    // legacy checkpoints store the attention projections as 1x1 convs [C, C, 1, 1]: staged as [C, C]
+    if (nm.find(".attentions.0.to_") != std::string::npos && ndim == 4 && shape[2] == 1 && shape[3] == 1) ndim = 2;
+    return dm::stage_tensor(e->w_vae.host, nm, host_ptr, dtype, shape, ndim, e->err);
 }
 
 int dm_engine_finalize_vae(dm_engine* e) {
     if (!e) return 1;
-    if (e->vae_ready) return 0;
+    if (e->w_vae.ready) return 0;
     DM_HIP(e, hipSetDevice(e->device));
-    Packer P{e, {}, &e->host_vae};
+    Packer P{e, e->w_vae};
     VaeW& v = e->vae;
     {
         HostTensor* w = P.get("encoder.conv_in.weight", {VBOC[0], 3, 3, 3});
@@ -1708,11 +1668,7 @@ int dm_engine_finalize_vae(dm_engine* e) {
         DM_TRY(pack_norm(P, a + ".group_norm", C, &v.attn_gn));
         DM_TRY(pack_stack(P, {a + ".to_q", a + ".to_k", a + ".to_v"}, C, C, &v.qkv));
         std::vector<f16> qb;
-        for (const char* leaf : {".to_q", ".to_k", ".to_v"}) {
-            HostTensor* b = P.get(a + leaf + ".bias", {C});
-            if (!b) return 1;
-            qb.insert(qb.end(), b->data.begin(), b->data.end());
-        }
+        DM_TRY(stack_bias(P, {a + ".to_q", a + ".to_k", a + ".to_v"}, C, &qb));
         v.qkv.b = as_ptr(P.put(qb.data(), qb.size() * 2));
         DM_TRY(pack_dense(P, a + ".to_out.0", C, C, false, true, &v.o));
     }
@@ -1739,15 +1695,8 @@ int dm_engine_finalize_vae(dm_engine* e) {
         v.qw = as_ptr(P.put(qw->data.data(), 64 * 2));
         v.qb = as_ptr(P.put(qb->data.data(), 8 * 2));
     }
-    size_t unused = 0; std::string first_unused;
-    for (auto& kv : e->host_vae) if (!kv.second.used) { if (!unused) first_unused = kv.first; ++unused; }
-    if (unused) DM_FAIL(e, "%zu unexpected tensors in the VAE state dict (first: %s)", unused, first_unused.c_str());
-    if (e->host_vae.size() != 108) DM_FAIL(e, "expected 108 VAE encoder tensors, got %zu", e->host_vae.size());
-
-    e->vslab_bytes = P.blob.size();
-    DM_MALLOC(e, &e->vslab, e->vslab_bytes);
-    DM_HIP(e, hipMemcpy(e->vslab, P.blob.data(), e->vslab_bytes, hipMemcpyHostToDevice));
-    char* base = e->vslab;
+    DM_TRY(P.finish("VAE", 108));
+    char* base = (char*)e->w_vae.slab;
     rebase_conv(v.conv_in, base); rebase_conv(v.qkv, base); rebase_conv(v.o, base); rebase_conv(v.conv_out, base);
     rebase_norm(v.attn_gn, base); rebase_norm(v.norm_out, base);
     rebase(v.qw, base); rebase(v.qb, base);
@@ -1756,15 +1705,13 @@ int dm_engine_finalize_vae(dm_engine* e) {
         if (i != VNB - 1) rebase_conv(v.ds[i], base);
     }
     rebase_res(v.mid[0], base); rebase_res(v.mid[1], base);
-    e->host_vae.clear();
-    e->vae_ready = true;
     return 0;
 }
 
 int dm_vae_encode(dm_engine* e, const void* image_dev, const void* noise_dev, int batch, int draws_per_image, int H, int W,
                   float scaling_factor, void* latent_f16_dev, void* latent_f32_dev, void* moments_f32_dev, void* stream) {
     if (!e) return 1;
-    if (!e->vae_ready) DM_FAIL(e, "dm_vae_encode: VAE weights not loaded (dm_engine_finalize_vae)");
+    if (!e->w_vae.ready) DM_FAIL(e, "dm_vae_encode: VAE weights not loaded (dm_engine_finalize_vae)");
     if (!image_dev || (!latent_f16_dev && !latent_f32_dev && !moments_f32_dev)) DM_FAIL(e, "dm_vae_encode: null argument");
     // any size >= 8: like diffusers' three Downsample2D(padding=0) stages (pad right/bottom by one, 3x3 stride 2), each stage
     // floors odd sizes, so the latent is floor(H / 8) x floor(W / 8) (cars rescaled to 256 x 341 px -> 32 x 42)
@@ -1793,27 +1740,18 @@ int dm_vae_encode(dm_engine* e, const void* image_dev, const void* noise_dev, in
 
 int dm_engine_load_clip_weight(dm_engine* e, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim) {
     if (!e || !name || !host_ptr || !shape) return 1;
-    if (e->clip_ready) DM_FAIL(e, "load_clip_weight after finalize_clip");
+    if (e->w_clip.ready) DM_FAIL(e, "load_clip_weight after finalize_clip");
     std::string nm(name);
     for (const char* pre : {"text_encoder.", "text_model."}) if (nm.rfind(pre, 0) == 0) nm = nm.substr(strlen(pre));
-    if (nm.rfind("text_model.", 0) == 0) nm = nm.substr(11);
     if (nm.size() >= 12 && nm.compare(nm.size() - 12, 12, "position_ids") == 0) return 0;          // index buffer
-    HostTensor t;
-    t.shape.assign(shape, shape + ndim);
-    const size_t n = t.numel();
-    t.data.resize(n);
-    if (dtype == DM_F16) memcpy(t.data.data(), host_ptr, n * 2);
-    else if (dtype == DM_F32) { const float* f = (const float*)host_ptr; for (size_t i = 0; i < n; ++i) t.data[i] = (f16)f[i]; }
-    else DM_FAIL(e, "unsupported dtype %d for %s", dtype, name);
-    e->host_clip[nm] = std::move(t);
-    return 0;
+    return dm::stage_tensor(e->w_clip.host, nm, host_ptr, dtype, shape, ndim, e->err);
 }
 
 int dm_engine_finalize_clip(dm_engine* e) {
     if (!e) return 1;
-    if (e->clip_ready) return 0;
+    if (e->w_clip.ready) return 0;
     DM_HIP(e, hipSetDevice(e->device));
-    Packer P{e, {}, &e->host_clip};
+    Packer P{e, e->w_clip};
     ClipW& c = e->clip;
     {
         HostTensor* tok = P.get("embeddings.token_embedding.weight", {CL_VOCAB, CL_H});
@@ -1827,14 +1765,11 @@ int dm_engine_finalize_clip(dm_engine* e) {
         const std::string b = "encoder.layers." + std::to_string(l);
         DM_TRY(pack_norm(P, b + ".layer_norm1", CL_H, &L.ln1));
         // q/k/v stacked; the attention scale d^-0.5 = 1/8 (exact in fp16) is folded into q_proj
-        DM_TRY(pack_stack(P, {b + ".self_attn.q_proj", b + ".self_attn.k_proj", b + ".self_attn.v_proj"}, CL_H, CL_H, &L.qkv));
+        const std::vector<std::string> qkv = {b + ".self_attn.q_proj", b + ".self_attn.k_proj", b + ".self_attn.v_proj"};
+        DM_TRY(pack_stack(P, qkv, CL_H, CL_H, &L.qkv));
         {
             std::vector<f16> qb;
-            for (const char* leaf : {".self_attn.q_proj", ".self_attn.k_proj", ".self_attn.v_proj"}) {
-                HostTensor* bt = P.get(b + leaf + ".bias", {CL_H});
-                if (!bt) return 1;
-                qb.insert(qb.end(), bt->data.begin(), bt->data.end());
-            }
+            DM_TRY(stack_bias(P, qkv, CL_H, &qb));
             for (int i = 0; i < CL_H; ++i) qb[i] = (f16)((float)qb[i] * 0.125f);
             f16* w = reinterpret_cast<f16*>(P.blob.data() + (reinterpret_cast<size_t>(L.qkv.w) - 1));
             for (size_t i = 0; i < (size_t)CL_H * CL_H; ++i) w[i] = (f16)((float)w[i] * 0.125f);
@@ -1846,29 +1781,21 @@ int dm_engine_finalize_clip(dm_engine* e) {
         DM_TRY(pack_dense(P, b + ".mlp.fc2", CL_H, CL_F, false, true, &L.fc2));
     }
     DM_TRY(pack_norm(P, "final_layer_norm", CL_H, &c.final_ln));
-    size_t unused = 0; std::string first_unused;
-    for (auto& kv : e->host_clip) if (!kv.second.used) { if (!unused) first_unused = kv.first; ++unused; }
-    if (unused) DM_FAIL(e, "%zu unexpected tensors in the CLIP text state dict (first: %s)", unused, first_unused.c_str());
-    if (e->host_clip.size() != 196) DM_FAIL(e, "expected 196 CLIP text tensors, got %zu", e->host_clip.size());
-    e->cslab_bytes = P.blob.size();
-    DM_MALLOC(e, &e->cslab, e->cslab_bytes);
-    DM_HIP(e, hipMemcpy(e->cslab, P.blob.data(), e->cslab_bytes, hipMemcpyHostToDevice));
-    char* base = e->cslab;
+    DM_TRY(P.finish("CLIP text", 196));
+    char* base = (char*)e->w_clip.slab;
     rebase(c.tok, base); rebase(c.pos, base); rebase_norm(c.final_ln, base);
     for (int l = 0; l < CL_LAYERS; ++l) {
         ClipLayerW& L = c.layer[l];
         rebase_norm(L.ln1, base); rebase_norm(L.ln2, base);
         rebase_conv(L.qkv, base); rebase_conv(L.o, base); rebase_conv(L.fc1, base); rebase_conv(L.fc2, base);
     }
-    e->host_clip.clear();
-    e->clip_ready = true;
     return 0;
 }
 
 int dm_clip_encode(dm_engine* e, const int32_t* input_ids_dev, int n_prompts, int seq_len, void* out_f16_dev, void* out_f32_dev,
                    void* stream) {
     if (!e) return 1;
-    if (!e->clip_ready) DM_FAIL(e, "dm_clip_encode: CLIP text weights not loaded (dm_engine_finalize_clip)");
+    if (!e->w_clip.ready) DM_FAIL(e, "dm_clip_encode: CLIP text weights not loaded (dm_engine_finalize_clip)");
     if (!input_ids_dev || (!out_f16_dev && !out_f32_dev) || n_prompts <= 0) DM_FAIL(e, "dm_clip_encode: bad argument");
     if (seq_len != CL_T) DM_FAIL(e, "dm_clip_encode: seq_len must be %d (padding=\"max_length\")", CL_T);
     DM_HIP(e, hipSetDevice(e->device));
@@ -2210,7 +2137,7 @@ int dm_engine_reserve(dm_engine* e, int max_batch, int max_h, int max_w, int n_c
 
 int dm_engine_memory(dm_engine* e, size_t* weights_bytes, size_t* arena_bytes) {
     if (!e) return 1;
-    if (weights_bytes) *weights_bytes = e->wslab_bytes + e->vslab_bytes + e->cslab_bytes;     // U-Net + optional VAE / CLIP slabs
+    if (weights_bytes) *weights_bytes = e->w_unet.bytes + e->w_vae.bytes + e->w_clip.bytes;     // U-Net + optional VAE / CLIP slabs
     if (arena_bytes) *arena_bytes = e->arena_cap;
     return 0;
 }

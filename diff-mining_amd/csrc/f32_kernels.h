@@ -46,20 +46,19 @@ hipError_t launch_gn_stats(const float* X, const float* X2, int N, int HW, int C
 hipError_t launch_gn_apply(const float* X, const float* X2, int N, int HW, int C, int C1, int G, const float* gamma, const float* beta,
                            const float* stats, int silu, float* Y, hipStream_t s);
 hipError_t launch_layernorm(const float* X, int rows, int C, const float* gamma, const float* beta, float eps, float* Y, hipStream_t s);
-// CLIP text tower glue (fp32): token + position embedding; causal attention of <= 80 tokens x heads of 64 on the stacked q|k|v rows
-// [n*T][3*heads*64] (q scaled by 1/8 inside); y * sigmoid(1.702 y) in place
+// CLIP tower glue (fp32): token + position embedding; attention of both towers, heads of 64 on the stacked q|k|v rows [n*T][3*heads*64]
+// (q scaled by 1/8 inside): (T, causal) = (77, true) for the text tower, (50, false) for the image tower, nothing else; y * sigmoid(1.702 y)
+// in place
 hipError_t launch_clip_embed(const int32_t* ids, const float* tok, const float* pos, int rows, int T, int C, int vocab, float* out, hipStream_t s);
-hipError_t launch_clip_attention(const float* qkv, int n, int T, int heads, float* out, hipStream_t s);
+hipError_t launch_clip_attention(const float* qkv, int n, int T, int heads, bool causal, float* out, hipStream_t s);
 hipError_t launch_quick_gelu(float* x, long long n, hipStream_t s);
 // CLIP ViT-B/32 image tower glue (clip_vision.hip): the processor's BICUBIC resize + center crop + rescale + normalise of uint8 HWC crops
 // (layout 0: [n][3][224][224], 1: patch rows [n*49][3072] with k = (c, ky, kx)); pixel_values -> patch rows; class token + patch embeddings +
-// position embedding [n*50][C]; bidirectional attention over 50 tokens x heads of 64 on q|k|v rows [n*50][3*heads*64] (q scaled by 1/8
-// inside); the CLS rows [n][C]; row-wise x / ||x||
+// position embedding [n*50][C]; the CLS rows [n][C]; row-wise x / ||x||
 hipError_t launch_clip_preprocess(const uint8_t* images, const dm_clip_pre_desc* desc, const int32_t* tables, int n, int layout, float* out,
                                   hipStream_t s);
 hipError_t launch_clip_patchify(const float* pix, int n, float* rows, hipStream_t s);
 hipError_t launch_clip_tokens(const float* pe, const float* cls, const float* pos, int n, int C, float* x, hipStream_t s);
-hipError_t launch_clipvis_attention(const float* qkv, int n, int heads, float* out, hipStream_t s);
 hipError_t launch_clip_cls(const float* x, int n, int C, float* y, hipStream_t s);
 hipError_t launch_clip_l2norm(const float* x, int n, int C, float* y, hipStream_t s);
 hipError_t launch_silu(const float* in, float* out, long long n, hipStream_t s);

@@ -273,11 +273,14 @@ __global__ void clip32_embed_kernel(const int32_t* ids, const float* tok, const 
     for (int c = threadIdx.x; c < C; c += blockDim.x) out[(size_t)row * C + c] = a[c] + b[c];
 }
 
-// causal self-attention over <= 80 tokens, heads of 64: one block per (prompt, head), one thread per query; qkv [n*T][3*heads*64];
-// q is scaled by head_dim^-0.5 = 1/8 AFTER its projection (bias included), as CLIPAttention does (a power of two: exact)
-constexpr int CLD = 64, CLT = 80;
-__global__ __launch_bounds__(128) void clip32_attn_kernel(const float* qkv, int T, int heads, float* out) {
-    __shared__ float Ks[CLT][CLD + 1], Vs[CLT][CLD + 1];
+// self-attention over the T tokens of a sequence, heads of 64: one block per (sequence, head), one thread per query; qkv
+// [n*T][3*heads*64]; CAUSAL: query t reads keys 0..t (the text tower), otherwise all T (the image tower).  q is scaled by
+// head_dim^-0.5 = 1/8 AFTER its projection (bias included), as CLIPAttention does (a power of two: exact); softmax in fp32
+constexpr int CLD = 64;
+constexpr int clip_attn_threads(int T) { return (T + 63) / 64 * 64; }
+template <int T, bool CAUSAL>
+__global__ __launch_bounds__(clip_attn_threads(T)) void clip32_attn_kernel(const float* __restrict__ qkv, int heads, float* __restrict__ out) {
+    __shared__ float Ks[T][CLD + 1], Vs[T][CLD + 1];
     const int h = blockIdx.x, n = blockIdx.y;
     const int C = heads * CLD;
     const float* base = qkv + (size_t)n * T * 3 * C + h * CLD;
@@ -289,12 +292,15 @@ __global__ __launch_bounds__(128) void clip32_attn_kernel(const float* qkv, int 
     __syncthreads();
     const int t = threadIdx.x;
     if (t >= T) return;
+    const int nk = CAUSAL ? t + 1 : T;             // keys 0..nk-1, in increasing order
+    constexpr int KU = CAUSAL ? 1 : T;             // a compile-time key range is unrolled: sc[] stays in registers
     float q[CLD];
 #pragma unroll
     for (int d = 0; d < CLD; ++d) q[d] = base[(size_t)t * 3 * C + d] * 0.125f;
-    float sc[CLT];
+    float sc[T];
     float m = -INFINITY;
-    for (int k = 0; k <= t; ++k) {                 // causal: keys 0..t
+#pragma unroll KU
+    for (int k = 0; k < nk; ++k) {
         float a = 0.f;
 #pragma unroll
         for (int d = 0; d < CLD; ++d) a = fmaf(q[d], Ks[k][d], a);
@@ -302,11 +308,13 @@ __global__ __launch_bounds__(128) void clip32_attn_kernel(const float* qkv, int 
         m = fmaxf(m, a);
     }
     float l = 0.f;
-    for (int k = 0; k <= t; ++k) { sc[k] = expf(sc[k] - m); l += sc[k]; }
+#pragma unroll KU
+    for (int k = 0; k < nk; ++k) { sc[k] = expf(sc[k] - m); l += sc[k]; }
     float o[CLD];
 #pragma unroll
     for (int d = 0; d < CLD; ++d) o[d] = 0.f;
-    for (int k = 0; k <= t; ++k) {
+#pragma unroll KU
+    for (int k = 0; k < nk; ++k) {
         const float pk = sc[k] / l;                // softmax output (fp32), then P V
 #pragma unroll
         for (int d = 0; d < CLD; ++d) o[d] = fmaf(pk, Vs[k][d], o[d]);
@@ -499,9 +507,11 @@ hipError_t launch_clip_embed(const int32_t* ids, const float* tok, const float* 
     hipLaunchKernelGGL(clip32_embed_kernel, dim3(rows), dim3(256), 0, s, ids, tok, pos, rows, T, C, vocab, out);
     return hipGetLastError();
 }
-hipError_t launch_clip_attention(const float* qkv, int n, int T, int heads, float* out, hipStream_t s) {
-    if (T <= 0 || T > CLT || n <= 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(clip32_attn_kernel, dim3(heads, n), dim3(128), 0, s, qkv, T, heads, out);
+hipError_t launch_clip_attention(const float* qkv, int n, int T, int heads, bool causal, float* out, hipStream_t s) {
+    if (n < 1 || n > 65535) return hipErrorInvalidValue;
+    if (T == 77 && causal) hipLaunchKernelGGL((clip32_attn_kernel<77, true>), dim3(heads, n), dim3(clip_attn_threads(77)), 0, s, qkv, heads, out);
+    else if (T == 50 && !causal) hipLaunchKernelGGL((clip32_attn_kernel<50, false>), dim3(heads, n), dim3(clip_attn_threads(50)), 0, s, qkv, heads, out);
+    else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 hipError_t launch_quick_gelu(float* x, long long n, hipStream_t s) {

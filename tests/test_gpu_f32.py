@@ -579,6 +579,26 @@ def test_f32_net_error_behaviour(sd15_weights_f16):
     e.close()
 
 
+def test_all_loaders_refuse_a_nonsensical_ndim():
+    """The seven state-dict loaders stage a tensor through one helper: an ndim outside 0..8 is refused by name by every one of them
+    (before, only the image tower's loader checked it), and a 0-dimensional tensor is staged."""
+    import ctypes as C
+    a = np.zeros(4, np.float32)
+    shape = (C.c_int64 * 1)(4)
+    loaders = {E.UNetEngine: ("dm_engine_load_weight", "dm_engine_load_vae_weight", "dm_engine_load_clip_weight"),
+               E.UNetEngineF32: ("dm_f32_load_weight", "dm_f32_load_vae_weight", "dm_f32_load_clip_weight", "dm_f32_load_clip_vision_weight")}
+    for cls, names in loaders.items():
+        e = cls(0)
+        try:
+            for fn in names:
+                for ndim in (-1, 9):
+                    with pytest.raises(E.EngineError, match="ndim.*some.weight"):
+                        e._check(getattr(e.lib, fn)(e._h, b"some.weight", a.ctypes.data_as(C.c_void_p), 1, shape, ndim), fn)
+                e._check(getattr(e.lib, fn)(e._h, b"some.scalar", a.ctypes.data_as(C.c_void_p), 1, shape, 0), fn)
+        finally:
+            e.close()
+
+
 def test_fp32_net_against_real_diffusers_fixture():
     """The pin the image cannot provide: when tests/make_golden_with_diffusers.py has been run where diffusers==0.24.0 exists,
     the fp32 net is compared with diffusers' OWN fp32 U-Net on the CPU — `unet(noisy, t, ctx).sample` at every size of the
