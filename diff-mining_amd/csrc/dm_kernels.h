@@ -14,6 +14,8 @@
 #define DM_MFMA_SNAKE 1
 #endif
 
+struct dm_mine_desc;          // include/dm_engine.h
+
 namespace dm {
 
 typedef _Float16 f16;
@@ -308,6 +310,14 @@ hipError_t launch_typicality(const void* loss, int is_f16, int n_images, int n_d
 // AvgPool2d((kx, ky), stride 1); tmp [H][W-ky+1], out [H-kx+1][W-ky+1] fp32
 hipError_t launch_typicality_image(const float* map, int h, int w, int H, int W, int kx, int ky, float* tmp,
                                    float* out, hipStream_t s);
+// the same for n_images images of any sizes in three launches (blockIdx.y = image, sizes and offsets from the dm_mine_desc table on
+// the device); max_hw / max_rowsum / max_out = the largest h*w, H*(W-ky+1) and (H-kx+1)*(W-ky+1) of the call.  Bit-equal per image.
+hipError_t launch_typicality_image_batched(const void* loss, int is_f16, const dm_mine_desc* desc, int n_images, int kx, int ky,
+                                           int max_hw, int max_rowsum, int max_out, float* work, float* maps, hipStream_t s);
+// greedy non-overlapping selection (utils.py:94-102 on the frame of cluster.py:194-201) on the pooled maps, one workgroup per image
+// (mine.hip): boxes [n][k][4] int32, d_out [n][k] fp32, count [n] int32; unused slots -1 / NaN
+hipError_t launch_mine_select(const float* maps, const float* priority, const dm_mine_desc* desc, int n_images, int kx, int ky,
+                              int k_per_image, int ascending, int32_t* boxes, float* d_out, int32_t* count, hipStream_t s);
 // consumers' normalisations of an fp32 map (cluster.py:32-47, utils.py:14-20,130): mode 1 signed -> [0,1], 2 / max|.|,
 // 3 positive only, 4 split (out2 = the negative part); mm = 2 floats of scratch (min, max)
 hipError_t launch_map_normalize(const float* map, long long n, int mode, float* mm, float* out, float* out2, hipStream_t s);

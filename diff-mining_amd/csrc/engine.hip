@@ -2046,6 +2046,59 @@ int dm_typicality_image(dm_engine* e, const void* loss_dev, int loss_is_f16, int
     return 0;
 }
 
+// the descriptor table of a mining call, read back once: the entry points check it and size their launches from it
+static int read_mine_desc(dm_engine* e, const char* who, const dm_mine_desc* desc_dev, int n_images, int kx, int ky, int need_grid,
+                          std::vector<dm_mine_desc>& host, hipStream_t s) {
+    host.resize((size_t)n_images);
+    DM_HIP(e, hipMemcpyAsync(host.data(), desc_dev, (size_t)n_images * sizeof(dm_mine_desc), hipMemcpyDeviceToHost, s));
+    DM_HIP(e, hipStreamSynchronize(s));
+    for (int b = 0; b < n_images; ++b) {
+        const dm_mine_desc& d = host[(size_t)b];
+        if (d.H < 1 || d.W < 1 || d.map_offset < 0) DM_FAIL(e, "%s: bad descriptor %d", who, b);
+        if (kx > d.H || ky > d.W) DM_FAIL(e, "%s: bad window %dx%d for %dx%d (image %d)", who, kx, ky, d.H, d.W, b);
+        if ((long long)d.H * d.W > 0x7fffffffLL) DM_FAIL(e, "%s: image %d too large", who, b);
+        if (need_grid && (d.n_draws < 1 || d.n_cond < 1 || d.h < 1 || d.w < 1 || d.grid_offset < 0 || d.work_offset < 0))
+            DM_FAIL(e, "%s: bad descriptor %d", who, b);
+    }
+    return 0;
+}
+
+int dm_typicality_image_batched(dm_engine* e, const void* loss_dev, int loss_is_f16, const dm_mine_desc* desc_dev, int n_images,
+                                int kx, int ky, void* work_dev, void* maps_out_dev, void* stream) {
+    if (!e) return 1;
+    if (!loss_dev || !desc_dev || !work_dev || !maps_out_dev) DM_FAIL(e, "dm_typicality_image_batched: null argument");
+    if (n_images < 1) DM_FAIL(e, "dm_typicality_image_batched: n_images %d", n_images);
+    if (kx < 1 || ky < 1) DM_FAIL(e, "dm_typicality_image_batched: bad window %dx%d", kx, ky);
+    DM_HIP(e, hipSetDevice(e->device));
+    std::vector<dm_mine_desc> host;
+    DM_TRY(read_mine_desc(e, "dm_typicality_image_batched", desc_dev, n_images, kx, ky, 1, host, (hipStream_t)stream));
+    int max_hw = 0, max_rowsum = 0, max_out = 0;
+    for (const dm_mine_desc& d : host) {
+        max_hw = std::max(max_hw, d.h * d.w);
+        max_rowsum = std::max(max_rowsum, d.H * (d.W - ky + 1));
+        max_out = std::max(max_out, (d.H - kx + 1) * (d.W - ky + 1));
+    }
+    DM_HIP(e, launch_typicality_image_batched(loss_dev, loss_is_f16, desc_dev, n_images, kx, ky, max_hw, max_rowsum, max_out,
+                                              (float*)work_dev, (float*)maps_out_dev, (hipStream_t)stream));
+    return 0;
+}
+
+int dm_mine_patches(dm_engine* e, const void* maps_dev, const void* priority_dev, const dm_mine_desc* desc_dev, int n_images, int kx,
+                    int ky, int k_per_image, int ascending, int32_t* boxes_out_dev, float* d_out_dev, int32_t* count_out_dev,
+                    void* stream) {
+    if (!e) return 1;
+    if (!maps_dev || !desc_dev || !boxes_out_dev || !d_out_dev || !count_out_dev) DM_FAIL(e, "dm_mine_patches: null argument");
+    if (n_images < 1) DM_FAIL(e, "dm_mine_patches: n_images %d", n_images);
+    if (kx < 1 || ky < 1) DM_FAIL(e, "dm_mine_patches: bad window %dx%d", kx, ky);
+    if (k_per_image < 1 || k_per_image > DM_MINE_MAX_K) DM_FAIL(e, "dm_mine_patches: k_per_image %d outside [1, %d]", k_per_image, DM_MINE_MAX_K);
+    DM_HIP(e, hipSetDevice(e->device));
+    std::vector<dm_mine_desc> host;
+    DM_TRY(read_mine_desc(e, "dm_mine_patches", desc_dev, n_images, kx, ky, 0, host, (hipStream_t)stream));
+    DM_HIP(e, launch_mine_select((const float*)maps_dev, (const float*)priority_dev, desc_dev, n_images, kx, ky, k_per_image, ascending,
+                                 boxes_out_dev, d_out_dev, count_out_dev, (hipStream_t)stream));
+    return 0;
+}
+
 int dm_normalize_map(dm_engine* e, const void* map_dev, int64_t n, int mode, void* work_dev, void* out_dev, void* out_neg_dev,
                      void* stream) {
     if (!e) return 1;

@@ -6,6 +6,7 @@
 //   K11 DIFT ensemble mean (dift.py:231) + NHWC->NCHW feature export,
 //   and the consumers' typicality reductions (cluster.py:125-137, xray/compute.py:210-218).
 #include "dm_kernels.h"
+#include "../../include/dm_engine.h"
 
 namespace dm {
 
@@ -264,6 +265,58 @@ __global__ void colsum_kernel(const float* __restrict__ tmp, int H, int OWd, int
     out[i] = acc * inv;
 }
 
+// Batched forms of the three map kernels for dm_typicality_image_batched: blockIdx.y = image, every size from the image's
+// dm_mine_desc row (images of one call may differ in every size).  Each thread does what its single-image twin does, in the
+// same order, so image b's map is bit-equal to dm_typicality_image on that image.  Image b's scratch at work + work_offset is
+// its latent map [h][w] followed by the row sums [H][W-ky+1].
+template <typename T>
+__global__ void typicality_map_desc_kernel(const T* __restrict__ L, const dm_mine_desc* __restrict__ desc, float* __restrict__ work) {
+    const dm_mine_desc d = desc[blockIdx.y];
+    const int HW = d.h * d.w, n_draws = d.n_draws, n_cond = d.n_cond;
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= HW) return;
+    L += d.grid_offset;
+    float acc = 0.f;
+    for (int n = 0; n < n_draws; ++n) {
+        const T* l0 = L + ((size_t)n * n_cond) * 4 * HW;
+        const T* l1 = L + ((size_t)n * n_cond + (size_t)(n_cond - 1)) * 4 * HW;
+        float m0 = 0.f, m1 = 0.f;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) { m0 += (float)l0[(size_t)c * HW + p]; m1 += (float)l1[(size_t)c * HW + p]; }
+        acc += (m1 - m0) * 0.25f;
+    }
+    work[d.work_offset + p] = acc / (float)n_draws;
+}
+
+__global__ void upsample_rowsum_desc_kernel(const dm_mine_desc* __restrict__ desc, int ky, float* __restrict__ work) {
+    const dm_mine_desc d = desc[blockIdx.y];
+    const int h = d.h, w = d.w, H = d.H, W = d.W;
+    const float* __restrict__ D = work + d.work_offset;
+    float* __restrict__ tmp = work + d.work_offset + (size_t)h * w;
+    const int OWd = W - ky + 1;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= H * OWd) return;
+    const int y = i / OWd, x = i - y * OWd;
+    const float sy = (float)h / (float)H, sx = (float)w / (float)W;
+    float acc = 0.f;
+    for (int dx = 0; dx < ky; ++dx) acc += bilinear_at(D, h, w, sy, sx, y, x + dx);
+    tmp[i] = acc;
+}
+
+__global__ void colsum_desc_kernel(const dm_mine_desc* __restrict__ desc, const float* __restrict__ work, int kx, int ky, float inv,
+                                   float* __restrict__ maps) {
+    const dm_mine_desc d = desc[blockIdx.y];
+    const float* __restrict__ tmp = work + d.work_offset + (size_t)d.h * d.w;
+    float* __restrict__ out = maps + d.map_offset;
+    const int OWd = d.W - ky + 1, OHd = d.H - kx + 1;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= OHd * OWd) return;
+    const int y = i / OWd, x = i - y * OWd;
+    float acc = 0.f;
+    for (int dy = 0; dy < kx; ++dy) acc += tmp[(y + dy) * OWd + x];
+    out[i] = acc * inv;
+}
+
 // Consumers' normalisations of an image-space typicality map (fp32, numpy semantics restated in fp32 IEEE arithmetic):
 //   mode 1  `normalize(dm)` of cluster.py:32-47 as `load_typicality_norm` (cluster.py:112-123) calls it: negatives / |min|,
 //           positives / max, then (dm + 1) / 2
@@ -436,6 +489,19 @@ hipError_t launch_typicality_image(const float* map, int h, int w, int H, int W,
     hipLaunchKernelGGL(upsample_rowsum_kernel, dim3((H * OWd + 255) / 256), dim3(256), 0, s, map, h, w, H, W, ky, tmp);
     hipLaunchKernelGGL(colsum_kernel, dim3((OHd * OWd + 255) / 256), dim3(256), 0, s, tmp, H, OWd, kx,
                        1.0f / ((float)kx * (float)ky), out);
+    return hipGetLastError();
+}
+
+hipError_t launch_typicality_image_batched(const void* loss, int is_f16, const dm_mine_desc* desc, int n_images, int kx, int ky,
+                                           int max_hw, int max_rowsum, int max_out, float* work, float* maps, hipStream_t s) {
+    if (n_images < 1 || max_hw < 1 || max_rowsum < 1 || max_out < 1) return hipErrorInvalidValue;
+    if (is_f16)
+        hipLaunchKernelGGL(typicality_map_desc_kernel<f16>, dim3((max_hw + 255) / 256, n_images), dim3(256), 0, s, (const f16*)loss, desc, work);
+    else
+        hipLaunchKernelGGL(typicality_map_desc_kernel<float>, dim3((max_hw + 255) / 256, n_images), dim3(256), 0, s, (const float*)loss, desc, work);
+    hipLaunchKernelGGL(upsample_rowsum_desc_kernel, dim3((max_rowsum + 255) / 256, n_images), dim3(256), 0, s, desc, ky, work);
+    hipLaunchKernelGGL(colsum_desc_kernel, dim3((max_out + 255) / 256, n_images), dim3(256), 0, s, desc, (const float*)work, kx, ky,
+                       1.0f / ((float)kx * (float)ky), maps);
     return hipGetLastError();
 }
 

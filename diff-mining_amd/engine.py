@@ -35,7 +35,13 @@ SYMBOLS = [
     "dm_f32_vae_encode", "dm_f32_score", "dm_f32_load_clip_weight", "dm_f32_finalize_clip", "dm_f32_clip_encode",
     "dm_resize_lanczos", "dm_f32_load_clip_vision_weight", "dm_f32_finalize_clip_vision", "dm_f32_clip_preprocess",
     "dm_f32_clip_image_features", "dm_f32_clip_vision_hidden", "dm_f32_clip_patch_features",
+    "dm_typicality_image_batched", "dm_mine_patches",
 ]
+
+# dm_mine_desc of include/dm_engine.h (48 bytes) and the compile-time cap of k_per_image
+MINE_DESC_DTYPE = np.dtype([("grid_offset", "<i8"), ("work_offset", "<i8"), ("map_offset", "<i8"), ("n_draws", "<i4"), ("n_cond", "<i4"),
+                            ("h", "<i4"), ("w", "<i4"), ("H", "<i4"), ("W", "<i4")])
+MINE_MAX_K = 64
 
 
 def get_options(names=("ln_fold", "gn_fold", "ff_fold", "sc_fold", "up_fold", "tap_reuse", "ln_inkernel", "igemm_splitk", "q_once", "gn_epi", "conv_out_rows", "gn_skip", "attn_pipe", "graph")) -> dict:
@@ -90,6 +96,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.dm_dift_shape.argtypes = [i32, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     lib.dm_reduce_typicality.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
     lib.dm_typicality_image.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]
+    if hasattr(lib, "dm_mine_patches"):          # (absent only from older A/B libraries loaded through DM_ENGINE_LIB)
+        lib.dm_typicality_image_batched.argtypes = [vp, vp, i32, vp, i32, i32, i32, vp, vp, vp]
+        lib.dm_mine_patches.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]
     lib.dm_prof_enable.argtypes = [vp, i32]
     lib.dm_measure_mfma_rate.argtypes = [vp, i32, i32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     if hasattr(lib, "dm_prof_read_folded"):
@@ -562,6 +571,85 @@ class UNetEngine:
                                                  C.c_void_p(work.data_ptr()), C.c_void_p(out.data_ptr()), self._stream()),
                     "dm_typicality_image")
         return out
+
+    def typicality_image_batched(self, grids, image_sizes, kx: int = 1, ky: int = 1):
+        """`typicality_image` for a list of images in ONE call (dm_typicality_image_batched): grids[b] [N_b, n_cond_b, 4, h_b, w_b]
+        (fp16 or fp32; every size may differ per image), image_sizes[b] = (H_b, W_b) -> list of maps [H_b-kx+1, W_b-ky+1] fp32 on the
+        GPU, views of one packed buffer, each bit-equal to `typicality_image(grids[b], image_sizes[b], kx, ky)`.  The grids are packed
+        into one buffer of one type: fp16 when all are fp16, else fp32 (the widening is exact and is what the kernel does anyway).
+        The descriptor table is built with numpy and uploaded once."""
+        torch = self._torch
+        if len(grids) != len(image_sizes) or len(grids) < 1:
+            raise ValueError(f"{len(grids)} grids but {len(image_sizes)} image sizes")
+        grids = [torch.as_tensor(g) for g in grids]
+        for g in grids:
+            if g.dim() != 5 or g.shape[2] != 4 or g.dtype not in (torch.float16, torch.float32):
+                raise ValueError(f"grid must be [N, n_cond, 4, h, w] fp16 / fp32, got {tuple(g.shape)} {g.dtype}")
+        dt = torch.float16 if all(g.dtype == torch.float16 for g in grids) else torch.float32
+        desc = np.zeros(len(grids), dtype=MINE_DESC_DTYPE)
+        g_at = w_at = m_at = 0
+        for b, (g, (H, W)) in enumerate(zip(grids, image_sizes)):
+            N, nc, _, h, w = g.shape
+            H, W = int(H), int(W)
+            if kx < 1 or ky < 1 or kx > H or ky > W:
+                raise EngineError(f"typicality_image_batched: bad window {kx}x{ky} for {H}x{W} (image {b})")
+            desc[b] = (g_at, w_at, m_at, N, nc, h, w, H, W)
+            g_at += g.numel()
+            w_at += h * w + H * (W - ky + 1)
+            m_at += (H - kx + 1) * (W - ky + 1)
+        loss = torch.cat([g.to(self.device, dt).reshape(-1) for g in grids])
+        desc_d = torch.from_numpy(desc.view(np.uint8)).to(self.device)
+        work = torch.empty(w_at, dtype=torch.float32, device=self.device)
+        maps = torch.empty(m_at, dtype=torch.float32, device=self.device)
+        self._check(self.lib.dm_typicality_image_batched(self._h, C.c_void_p(loss.data_ptr()), 1 if dt == torch.float16 else 0,
+                                                         C.c_void_p(desc_d.data_ptr()), len(grids), int(kx), int(ky),
+                                                         C.c_void_p(work.data_ptr()), C.c_void_p(maps.data_ptr()), self._stream()),
+                    "dm_typicality_image_batched")
+        return [maps[int(d["map_offset"]):int(d["map_offset"]) + (int(d["H"]) - kx + 1) * (int(d["W"]) - ky + 1)]
+                .view(int(d["H"]) - kx + 1, int(d["W"]) - ky + 1) for d in desc]
+
+    def mine_patches(self, maps, kx: int, ky: int, k_per_image: int = 5, ascending: bool = False, priority=None):
+        """`sort` + `get_non_overlapping` (utils.py:82-102) on the candidate frame of `Cluster.df_D` (cluster.py:194-201), for a list
+        of pooled maps [OH_b, OW_b] fp32 (`typicality_image_batched`'s output, window kx x ky) in ONE launch, one workgroup per image:
+        k_per_image rounds of "take the best remaining candidate (i, j), drop every candidate with |i-i*| <= kx and |j-j*| <= ky".
+        Returns (boxes [n, k, 4] int32 = (x_start, y_start, x_end, y_end) = (i, j, i+kx, j+ky) with x = rows, D [n, k] fp32,
+        count [n] int32) on the GPU; slots past count[b] hold -1 / NaN (the map ran out).  ascending=True is `compute_least`'s
+        order.  Ties go to the lowest row-major index; NaN keys are never chosen.  priority: optional list of maps of the same
+        shapes that supply the sort key instead (D is still read from `maps`) — the ranks of a permutation give the reference's
+        shuffled arm."""
+        torch = self._torch
+        if len(maps) < 1:
+            raise ValueError("no maps")
+        if priority is not None and len(priority) != len(maps):
+            raise ValueError(f"{len(maps)} maps but {len(priority)} priority maps")
+        k_per_image = int(k_per_image)
+        if k_per_image < 1 or k_per_image > MINE_MAX_K:
+            raise EngineError(f"mine_patches: k_per_image {k_per_image} outside [1, {MINE_MAX_K}]")
+        maps = [torch.as_tensor(m) for m in maps]
+        desc = np.zeros(len(maps), dtype=MINE_DESC_DTYPE)
+        at = 0
+        for b, m in enumerate(maps):
+            if m.dim() != 2 or m.numel() < 1:
+                raise ValueError(f"map {b} must be [OH, OW], got {tuple(m.shape)}")
+            if priority is not None and tuple(priority[b].shape) != tuple(m.shape):
+                raise ValueError(f"priority map {b} is {tuple(priority[b].shape)}, the map {tuple(m.shape)}")
+            desc[b]["map_offset"], desc[b]["H"], desc[b]["W"] = at, m.shape[0] + kx - 1, m.shape[1] + ky - 1
+            at += m.numel()
+
+        def pack(ts):
+            return torch.cat([torch.as_tensor(t).to(self.device, torch.float32).reshape(-1) for t in ts])
+        packed = pack(maps)
+        prio = pack(priority) if priority is not None else None
+        desc_d = torch.from_numpy(desc.view(np.uint8)).to(self.device)
+        n = len(maps)
+        boxes = torch.empty(n, k_per_image, 4, dtype=torch.int32, device=self.device)
+        dvals = torch.empty(n, k_per_image, dtype=torch.float32, device=self.device)
+        count = torch.empty(n, dtype=torch.int32, device=self.device)
+        self._check(self.lib.dm_mine_patches(self._h, C.c_void_p(packed.data_ptr()), C.c_void_p(prio.data_ptr()) if prio is not None else None,
+                                             C.c_void_p(desc_d.data_ptr()), n, int(kx), int(ky), k_per_image, 1 if ascending else 0,
+                                             C.c_void_p(boxes.data_ptr()), C.c_void_p(dvals.data_ptr()), C.c_void_p(count.data_ptr()),
+                                             self._stream()), "dm_mine_patches")
+        return boxes, dvals, count
 
     NORM_MODES = {"signed": 1, "maxabs": 2, "positive": 3, "split": 4}
 

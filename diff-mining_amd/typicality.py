@@ -562,6 +562,86 @@ class TypicalityScorer:
         return self.engine.typicality_image(grid, image_size, 1, 1)
 
 
+    # -- patch mining: `Cluster.df_D` (cluster.py:184-215) + `get_top_k` (utils.py:237-252) -----------------------------
+    MINE_COLUMNS = ("seed", "x_start", "y_start", "x_end", "y_end", "D", "origin")
+
+    def mine_patches(self, grids_or_paths, image_sizes, k_per_image: int = 5, kx: int = 64, ky: int = 64, ascending: bool = False,
+                     randomized: bool = False, seed: int = 42, images_per_call: int = 64):
+        """`Cluster.df_D` (cluster.py:184-215) on the GPU: per image the pooled map (`load_typicality`), one candidate box per
+        window position, `sort` by D and `get_non_overlapping` (utils.py:82-102) — maps and selection run on the device, only the
+        k_per_image winners per image come back.  grids_or_paths: per image a grid [N, n_cond, 4, h, w] or an image path whose
+        stored grid is loaded as `__call__` does; image_sizes: per image (H, W).  The images go through the engine in calls of
+        `images_per_call`.  ascending=True is `compute_least`'s order (cluster.py:393).
+
+        Returns the reference's columns as a plain dict of numpy arrays, image order then round order (fewer than k_per_image rows
+        for an image whose map ran out): seed (the path, or the image's index when a grid was given), x_start, y_start, x_end,
+        y_end (int32; x = rows, the convention `clip_patch_features` and `dift.patch_features` take), D (fp32), origin ('real'),
+        plus `image` (int64 index into the input list; `boxes_by_image` groups by it).
+
+        randomized=True is the reference's second frame (`df_random`): the same selection on a shuffled candidate order, D only
+        reported.  Here the order is a permutation per image drawn from np.random.default_rng((seed, image index)).  The
+        reference's `random.shuffle` (cluster.py:197) is NOT seeded — its `seed` argument is unused — so the random arm matches
+        the reference in distribution, not in draws."""
+        n = len(grids_or_paths)
+        if n != len(image_sizes):
+            raise ValueError(f"{n} grids but {len(image_sizes)} image sizes")
+        if (kx == 1) != (ky == 1):          # `pool` (utils.py:74-80) skips the window then, and the frame's boxes leave the image
+            raise ValueError(f"window {kx}x{ky}: one side 1 and the other not is not a frame the reference can mine")
+        cols = {c: [] for c in ("image", "x_start", "y_start", "x_end", "y_end", "D")}
+        for c0 in range(0, n, images_per_call):
+            idx = range(c0, min(n, c0 + images_per_call))
+            grids = [self(g) if isinstance(g, (str, os.PathLike)) else g for g in (grids_or_paths[i] for i in idx)]
+            grids = [torch.from_numpy(g) if isinstance(g, np.ndarray) else g for g in grids]
+            maps = self.engine.typicality_image_batched(grids, [image_sizes[i] for i in idx], kx, ky)
+            prio = None
+            if randomized:
+                prio = []
+                for i, m in zip(idx, maps):
+                    perm = np.random.default_rng((seed, i)).permutation(m.numel())          # perm[r] = the r-th row of the shuffled frame
+                    prio.append(torch.from_numpy(self.permutation_priority(perm).reshape(tuple(m.shape))))
+            boxes, dv, cnt = self.engine.mine_patches(maps, kx, ky, k_per_image, ascending and not randomized, prio)
+            boxes, dv, cnt = boxes.cpu().numpy(), dv.cpu().numpy(), cnt.cpu().numpy()
+            for j, i in enumerate(idx):
+                c = int(cnt[j])
+                cols["image"].append(np.full(c, i, dtype=np.int64))
+                for q, name in enumerate(("x_start", "y_start", "x_end", "y_end")):
+                    cols[name].append(boxes[j, :c, q])
+                cols["D"].append(dv[j, :c])
+        rows = {c: np.concatenate(v) for c, v in cols.items()}
+        rows["seed"] = np.array([grids_or_paths[i] if isinstance(grids_or_paths[i], (str, os.PathLike)) else i for i in rows["image"]], dtype=object)
+        rows["origin"] = np.array(["real"] * len(rows["D"]), dtype=object)
+        return rows
+
+    @staticmethod
+    def permutation_priority(perm) -> np.ndarray:
+        """fp32 sort keys that make a descending selection visit the candidates in the order `perm` (perm[r] = flat index of the
+        r-th row of the shuffled frame): key[perm[r]] = n - 1 - r, exact in fp32 below 2^24 candidates."""
+        perm = np.asarray(perm, dtype=np.int64)
+        if perm.size >= 1 << 24:
+            raise ValueError("more than 2^24 candidates: the ranks are not exact in fp32")
+        key = np.empty(perm.size, dtype=np.float32)
+        key[perm] = np.arange(perm.size - 1, -1, -1, dtype=np.float32)
+        return key
+
+    @staticmethod
+    def boxes_by_image(rows, n_images: Optional[int] = None):
+        """The mined rows as `clip_patch_features` / `dift.patch_features` take them: per image an int array [k_i, 4] of
+        (x_start, y_start, x_end, y_end)."""
+        b = np.stack([rows["x_start"], rows["y_start"], rows["x_end"], rows["y_end"]], axis=1) if len(rows["D"]) else np.zeros((0, 4), np.int32)
+        n = int(rows["image"].max()) + 1 if n_images is None and len(rows["D"]) else int(n_images or 0)
+        return [b[rows["image"] == i] for i in range(n)]
+
+    @staticmethod
+    def top_k(rows, k: int = 1000):
+        """`get_top_k(df, key='D', k=k)` (utils.py:237-252), its non-random, unfiltered branch: the k rows of a category's
+        concatenated frame with the largest D, in that order.  The sort is stable (equal D keep their order; pandas' default
+        sort leaves that undefined).  rows: a dict of equally long arrays with a 'D' column, e.g. `mine_patches`' result."""
+        D = np.asarray(rows["D"])
+        k = min(len(D), int(k))
+        order = np.argsort(-D.astype(np.float64), kind="stable")[:k]
+        return {c: np.asarray(v)[order] for c, v in rows.items()}
+
+
 def shard_indices(n_items: int, rank: int, world: int) -> Sequence[int]:
     """Image-major sharding `subs[i::sub_split]` of compute.py:339."""
     return list(range(rank, n_items, world))

@@ -180,6 +180,37 @@ typedef struct dm_resize_desc {
 int dm_resize_lanczos(const void* src_dev, const dm_resize_desc* desc_dev, const int32_t* tables_dev, int batch, int out_w,
                       int out_h, int tmp_rows_max, void* tmp_dev, float* out_dev, void* stream);
 
+/* ---- Patch mining: grids -> pooled maps -> top non-overlapping boxes (Cluster.df_D, cluster.py:184-215) -----------------
+ * dm_typicality_image_batched: dm_typicality_image for n_images images of any sizes in three launches.  Image b reads its grid
+ *   [n_draws][n_cond][4][h][w] at loss_dev + desc[b].grid_offset elements (fp16 when loss_is_f16, else fp32 — one type per call),
+ *   uses work_dev + desc[b].work_offset as scratch (h*w + H*(W-ky+1) floats) and writes its map [H-kx+1][W-ky+1] fp32 at
+ *   maps_out_dev + desc[b].map_offset; every map is bit-equal to dm_typicality_image on that image.
+ * dm_mine_patches: per image, the reference's candidate frame (one row per window position (i, j) of the pooled map: box
+ *   (x_start, y_start, x_end, y_end) = (i, j, i+kx, j+ky), x = rows, D = map[i][j]), `sort` by D (utils.py:82-83; ascending != 0
+ *   is compute_least's order, cluster.py:393) and `get_non_overlapping` (utils.py:94-102): take the best candidate, drop every
+ *   candidate whose box touches it (inclusive comparisons: |i-i*| <= kx and |j-j*| <= ky), up to k_per_image times
+ *   (1 <= k_per_image <= DM_MINE_MAX_K).  Reads maps_dev + desc[b].map_offset and desc[b].H / W only.  Among equal keys the
+ *   lowest row-major index wins (pandas leaves ties undefined); NaN keys are never selected.  priority_dev (optional, laid out
+ *   like maps_dev) supplies the sort key instead of the map — a permutation's ranks give the reference's shuffled arm — while D
+ *   is still read from the map.  boxes_out_dev int32 [n_images][k_per_image][4], d_out_dev fp32 [n_images][k_per_image],
+ *   count_out_dev int32 [n_images] = boxes found (fewer when the map runs out); unused slots hold -1 / NaN.
+ * Both calls read the descriptor table back once to check it (windows larger than an image are refused) and to size the
+ * launches, so they synchronise `stream` before they launch. */
+#define DM_MINE_MAX_K 64
+typedef struct dm_mine_desc {
+    int64_t grid_offset;                /* elements from loss_dev to the image's grid */
+    int64_t work_offset;                /* floats from work_dev to the image's scratch */
+    int64_t map_offset;                 /* floats from maps(_out)_dev / priority_dev to the image's map */
+    int32_t n_draws, n_cond;
+    int32_t h, w;                       /* latent size */
+    int32_t H, W;                       /* image size */
+} dm_mine_desc;
+int dm_typicality_image_batched(dm_engine* e, const void* loss_dev, int loss_is_f16, const dm_mine_desc* desc_dev, int n_images,
+                                int kx, int ky, void* work_dev, void* maps_out_dev, void* stream);
+int dm_mine_patches(dm_engine* e, const void* maps_dev, const void* priority_dev, const dm_mine_desc* desc_dev, int n_images, int kx,
+                    int ky, int k_per_image, int ascending, int32_t* boxes_out_dev, float* d_out_dev, int32_t* count_out_dev,
+                    void* stream);
+
 /* Profiling support for bench.py: when enabled, every launch of the dominant (implicit-GEMM)
  * kernel is bracketed by hipEvents on the launch stream.  dm_prof_read synchronises and returns
  * the accumulated kernel milliseconds, launch count and algorithmic FLOPs since the last reset. */
