@@ -318,6 +318,14 @@ hipError_t launch_typicality_image_batched(const void* loss, int is_f16, const d
 // (mine.hip): boxes [n][k][4] int32, d_out [n][k] fp32, count [n] int32; unused slots -1 / NaN
 hipError_t launch_mine_select(const float* maps, const float* priority, const dm_mine_desc* desc, int n_images, int kx, int ky,
                               int k_per_image, int ascending, int32_t* boxes, float* d_out, int32_t* count, hipStream_t s);
+// parallel-dataset mining (parallel-dataset/cluster.py:231,233; mine_parallel.hip).  median: per candidate the np.median of the
+// n_sets maps of its group (set c of group g at maps + desc[g*n_sets+c].map_offset) -> median + group_desc[g].map_offset;
+// max_n = the largest candidate count of a group.  gather: set_d [n_groups][k][n_sets] = every set's own value at the winners
+// that launch_mine_select left in boxes / count; unused slots NaN.
+hipError_t launch_median_maps(const float* maps, const dm_mine_desc* desc, const dm_mine_desc* group_desc, int n_groups, int n_sets,
+                              int kx, int ky, int max_n, float* median, hipStream_t s);
+hipError_t launch_gather_sets(const float* maps, const dm_mine_desc* desc, int n_groups, int n_sets, int ky, int k_per_image,
+                              const int32_t* boxes, const int32_t* count, float* set_d, hipStream_t s);
 // consumers' normalisations of an fp32 map (cluster.py:32-47, utils.py:14-20,130): mode 1 signed -> [0,1], 2 / max|.|,
 // 3 positive only, 4 split (out2 = the negative part); mm = 2 floats of scratch (min, max)
 hipError_t launch_map_normalize(const float* map, long long n, int mode, float* mm, float* out, float* out2, hipStream_t s);

@@ -2099,6 +2099,41 @@ int dm_mine_patches(dm_engine* e, const void* maps_dev, const void* priority_dev
     return 0;
 }
 
+int dm_mine_parallel(dm_engine* e, const void* maps_dev, const dm_mine_desc* desc_dev, int n_groups, int n_sets,
+                     const dm_mine_desc* group_desc_dev, int kx, int ky, int k_per_image, int ascending, const void* priority_dev,
+                     void* median_out_dev, int32_t* boxes_out_dev, float* d_out_dev, float* set_d_out_dev, int32_t* count_out_dev,
+                     void* stream) {
+    if (!e) return 1;
+    if (!maps_dev || !desc_dev || !group_desc_dev || !median_out_dev || !boxes_out_dev || !d_out_dev || !set_d_out_dev || !count_out_dev)
+        DM_FAIL(e, "dm_mine_parallel: null argument");
+    if (n_groups < 1) DM_FAIL(e, "dm_mine_parallel: n_groups %d", n_groups);
+    if (n_sets < 1 || n_sets > DM_MINE_MAX_SETS) DM_FAIL(e, "dm_mine_parallel: n_sets %d outside [1, %d]", n_sets, DM_MINE_MAX_SETS);
+    if ((long long)n_groups * n_sets > 0x7fffffffLL) DM_FAIL(e, "dm_mine_parallel: n_groups %d", n_groups);
+    if (kx < 1 || ky < 1) DM_FAIL(e, "dm_mine_parallel: bad window %dx%d", kx, ky);
+    if (k_per_image < 1 || k_per_image > DM_MINE_MAX_K) DM_FAIL(e, "dm_mine_parallel: k_per_image %d outside [1, %d]", k_per_image, DM_MINE_MAX_K);
+    DM_HIP(e, hipSetDevice(e->device));
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<dm_mine_desc> sets, groups;
+    DM_TRY(read_mine_desc(e, "dm_mine_parallel", group_desc_dev, n_groups, kx, ky, 0, groups, s));
+    DM_TRY(read_mine_desc(e, "dm_mine_parallel", desc_dev, n_groups * n_sets, kx, ky, 0, sets, s));
+    int max_n = 0;
+    for (int g = 0; g < n_groups; ++g) {
+        const dm_mine_desc& gd = groups[(size_t)g];
+        for (int c = 0; c < n_sets; ++c) {
+            const dm_mine_desc& d = sets[(size_t)g * n_sets + c];
+            if (d.H != gd.H || d.W != gd.W)
+                DM_FAIL(e, "dm_mine_parallel: set %d of group %d is %dx%d, the group %dx%d", c, g, d.H, d.W, gd.H, gd.W);
+        }
+        max_n = std::max(max_n, (gd.H - kx + 1) * (gd.W - ky + 1));
+    }
+    DM_HIP(e, launch_median_maps((const float*)maps_dev, desc_dev, group_desc_dev, n_groups, n_sets, kx, ky, max_n, (float*)median_out_dev, s));
+    DM_HIP(e, launch_mine_select((const float*)median_out_dev, (const float*)priority_dev, group_desc_dev, n_groups, kx, ky, k_per_image,
+                                 ascending, boxes_out_dev, d_out_dev, count_out_dev, s));
+    DM_HIP(e, launch_gather_sets((const float*)maps_dev, desc_dev, n_groups, n_sets, ky, k_per_image, boxes_out_dev, count_out_dev,
+                                 set_d_out_dev, s));
+    return 0;
+}
+
 int dm_normalize_map(dm_engine* e, const void* map_dev, int64_t n, int mode, void* work_dev, void* out_dev, void* out_neg_dev,
                      void* stream) {
     if (!e) return 1;

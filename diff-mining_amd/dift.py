@@ -245,3 +245,45 @@ def patch_features(feature_which: str, image, boxes, prompt=None, featurizer: Op
             feat = featurizer.forward(x[None], prompt, t=t, up_ft_index=1, ensemble_size=ensemble_size, generator=generator)
         out.append(featurizer.patch_embeddings(feat, boxes, img.shape[:2]).to(torch.float32))
     return out[0] if len(out) == 1 else torch.cat(out, dim=1)
+
+
+@torch.no_grad()
+def parallel_patch_features(feature_which: str, images, boxes, prompts=None, featurizer: Optional[SDFeaturizer] = None,
+                            clip_net: Optional[UNetEngineF32] = None, feats=None, ensemble_size: int = 8, generator=None) -> torch.Tensor:
+    """`Cluster.embed_batch` (parallel-dataset/cluster.py:152-190) for the P boxes of ONE parallel group, fp32 on the GPU.  images:
+    the group's n_sets images in set order (one size); boxes: the group's P boxes (x_start, y_start, x_end, y_end), x = rows,
+    each cut from every image.  Row p is what `embed_batch` returns for box p:
+      * 'clip'        [P, n_sets*512]:  the sets' L2-normalised CLIP features one after another (`features.flatten()`, :160);
+      * 'dift-T'      [P, n_sets*1280]: the sets' L2-normalised DIFT window means one after another (:180), set c's map computed
+                                        with prompts[c] (`dift_prompt`, :172);
+      * 'clip+dift-T' [P, n_sets*1792]: ALL CLIP blocks first, then ALL DIFT blocks (:185-186) — not the per-set interleave.
+    Block c equals `patch_features(..., images[c], boxes, ...)`'s part.  The n_sets x P crops go through ONE
+    `clip_patch_features` call.  feats: optional per-set DIFT maps [1, C, h, w] the caller already holds."""
+    clip, dift, t = parse_feature_which(feature_which)
+    from . import resample as RS
+    imgs = [RS.check_clip_image(im) for im in images]
+    n_sets = len(imgs)
+    if n_sets < 1 or any(im.shape[:2] != imgs[0].shape[:2] for im in imgs):
+        raise ValueError(f"a parallel group's images share one size, got {[im.shape[:2] for im in imgs]}")
+    boxes = [tuple(int(v) for v in b) for b in boxes]
+    for b in boxes:
+        RS.clip_crop_box(imgs[0].shape[:2], b)
+    P = len(boxes)
+    out = []
+    if clip:
+        if clip_net is None:
+            raise ValueError(f"{feature_which!r} needs clip_net: a UNetEngineF32 holding the CLIP vision weights")
+        f = clip_net.clip_patch_features(imgs, [boxes] * n_sets)                     # [n_sets * P, 512], set-major
+        out.append(f.view(n_sets, P, -1).permute(1, 0, 2).reshape(P, -1))
+    if dift:
+        if featurizer is None:
+            raise ValueError(f"{feature_which!r} needs an SDFeaturizer")
+        if feats is None and (prompts is None or len(prompts) != n_sets):
+            raise ValueError(f"{feature_which!r} needs one prompt per set ({n_sets}) or the sets' DIFT maps in `feats`")
+        if feats is not None and len(feats) != n_sets:
+            raise ValueError(f"{len(feats)} DIFT maps for {n_sets} images")
+        for c, img in enumerate(imgs):
+            feat = feats[c] if feats is not None else None
+            out.append(patch_features(f"dift-{t}", img, boxes, prompts[c] if prompts is not None else None, featurizer, None, feat,
+                                      ensemble_size, generator))
+    return out[0] if len(out) == 1 else torch.cat(out, dim=1)

@@ -35,13 +35,14 @@ SYMBOLS = [
     "dm_f32_vae_encode", "dm_f32_score", "dm_f32_load_clip_weight", "dm_f32_finalize_clip", "dm_f32_clip_encode",
     "dm_resize_lanczos", "dm_f32_load_clip_vision_weight", "dm_f32_finalize_clip_vision", "dm_f32_clip_preprocess",
     "dm_f32_clip_image_features", "dm_f32_clip_vision_hidden", "dm_f32_clip_patch_features",
-    "dm_typicality_image_batched", "dm_mine_patches",
+    "dm_typicality_image_batched", "dm_mine_patches", "dm_mine_parallel",
 ]
 
 # dm_mine_desc of include/dm_engine.h (48 bytes) and the compile-time cap of k_per_image
 MINE_DESC_DTYPE = np.dtype([("grid_offset", "<i8"), ("work_offset", "<i8"), ("map_offset", "<i8"), ("n_draws", "<i4"), ("n_cond", "<i4"),
                             ("h", "<i4"), ("w", "<i4"), ("H", "<i4"), ("W", "<i4")])
 MINE_MAX_K = 64
+MINE_MAX_SETS = 16          # DM_MINE_MAX_SETS: the set counts median_maps_kernel is instantiated for
 
 
 def get_options(names=("ln_fold", "gn_fold", "ff_fold", "sc_fold", "up_fold", "tap_reuse", "ln_inkernel", "igemm_splitk", "q_once", "gn_epi", "conv_out_rows", "gn_skip", "attn_pipe", "graph")) -> dict:
@@ -99,6 +100,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     if hasattr(lib, "dm_mine_patches"):          # (absent only from older A/B libraries loaded through DM_ENGINE_LIB)
         lib.dm_typicality_image_batched.argtypes = [vp, vp, i32, vp, i32, i32, i32, vp, vp, vp]
         lib.dm_mine_patches.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]
+    if hasattr(lib, "dm_mine_parallel"):
+        lib.dm_mine_parallel.argtypes = [vp, vp, vp, i32, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     lib.dm_prof_enable.argtypes = [vp, i32]
     lib.dm_measure_mfma_rate.argtypes = [vp, i32, i32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     if hasattr(lib, "dm_prof_read_folded"):
@@ -650,6 +653,79 @@ class UNetEngine:
                                              C.c_void_p(boxes.data_ptr()), C.c_void_p(dvals.data_ptr()), C.c_void_p(count.data_ptr()),
                                              self._stream()), "dm_mine_patches")
         return boxes, dvals, count
+
+    @staticmethod
+    def _place_maps(torch, maps, device):
+        """fp32 maps for a call that addresses them as base pointer + element offsets: contiguous views of ONE buffer on
+        `device` (`typicality_image_batched`'s output) stay where they lie, anything else is packed into a new buffer.
+        Returns (base tensor, offsets from its first element, copied)."""
+        stores = {m.untyped_storage().data_ptr() for m in maps}
+        if len(stores) == 1 and all(m.dtype == torch.float32 and m.device == torch.device(device) and m.is_contiguous() for m in maps):
+            lo = min(m.storage_offset() for m in maps)
+            hi = max(m.storage_offset() + m.numel() for m in maps)
+            base = maps[0].as_strided((hi - lo,), (1,), lo)
+            return base, [m.storage_offset() - lo for m in maps], False
+        base = torch.cat([m.to(device, torch.float32).reshape(-1) for m in maps])
+        return base, [int(v) for v in np.cumsum([0] + [m.numel() for m in maps[:-1]])], True
+
+    def mine_parallel(self, maps_by_group, kx: int, ky: int, k_per_image: int = 5, ascending: bool = False, priority=None):
+        """`Cluster.df_PD.compute` (parallel-dataset/cluster.py:229-241) for a list of parallel groups in ONE call
+        (dm_mine_parallel).  maps_by_group[g]: the n_sets pooled maps [OH_g, OW_g] fp32 of group g, one per set (country), all of
+        one size; n_sets is the same for every group, 1..MINE_MAX_SETS.  Views of `typicality_image_batched`'s packed buffer are
+        read in place.  Per group: the per-candidate median across the sets (`np.median(np.stack(...), axis=0)`; NaN where any
+        set is NaN), `mine_patches`' selection on that median map, and every set's own value at the winners.
+        Returns (boxes [G, k, 4] int32, D [G, k] fp32 = the median at the winner, set_D [G, k, n_sets] fp32, count [G] int32,
+        medians: list of G maps [OH_g, OW_g] fp32), all on the GPU; slots past count[g] hold -1 / NaN.  priority: optional list
+        of G maps shaped like the medians that supply the sort key (the shuffled arm), as in `mine_patches`."""
+        torch = self._torch
+        G = len(maps_by_group)
+        if G < 1:
+            raise ValueError("no groups")
+        n_sets = len(maps_by_group[0])
+        if n_sets < 1 or n_sets > MINE_MAX_SETS:
+            raise EngineError(f"mine_parallel: n_sets {n_sets} outside [1, {MINE_MAX_SETS}]")
+        if any(len(g) != n_sets for g in maps_by_group):
+            raise ValueError(f"every group must hold {n_sets} maps, got {[len(g) for g in maps_by_group]}")
+        if priority is not None and len(priority) != G:
+            raise ValueError(f"{G} groups but {len(priority)} priority maps")
+        k_per_image = int(k_per_image)
+        if k_per_image < 1 or k_per_image > MINE_MAX_K:
+            raise EngineError(f"mine_parallel: k_per_image {k_per_image} outside [1, {MINE_MAX_K}]")
+        flat = [torch.as_tensor(m) for g in maps_by_group for m in g]
+        for b, m in enumerate(flat):
+            if m.dim() != 2 or m.numel() < 1:
+                raise ValueError(f"map {b % n_sets} of group {b // n_sets} must be [OH, OW], got {tuple(m.shape)}")
+        desc = np.zeros(G * n_sets, dtype=MINE_DESC_DTYPE)
+        gdesc = np.zeros(G, dtype=MINE_DESC_DTYPE)
+        at = 0
+        for g in range(G):
+            m0 = flat[g * n_sets]
+            for c in range(n_sets):
+                m = flat[g * n_sets + c]
+                if tuple(m.shape) != tuple(m0.shape):
+                    raise EngineError(f"mine_parallel: set {c} of group {g} is {tuple(m.shape)}, the group {tuple(m0.shape)}")
+                desc[g * n_sets + c]["H"], desc[g * n_sets + c]["W"] = m.shape[0] + kx - 1, m.shape[1] + ky - 1
+            if priority is not None and tuple(priority[g].shape) != tuple(m0.shape):
+                raise ValueError(f"priority map {g} is {tuple(priority[g].shape)}, the group's maps {tuple(m0.shape)}")
+            gdesc[g]["map_offset"], gdesc[g]["H"], gdesc[g]["W"] = at, m0.shape[0] + kx - 1, m0.shape[1] + ky - 1
+            at += m0.numel()
+        packed, offsets, _ = self._place_maps(torch, flat, self.device)
+        desc["map_offset"] = offsets
+        prio = torch.cat([torch.as_tensor(t).to(self.device, torch.float32).reshape(-1) for t in priority]) if priority is not None else None
+        up = torch.from_numpy(np.concatenate([desc, gdesc]).view(np.uint8)).to(self.device)          # both tables in one upload
+        desc_d, gdesc_d = up[:desc.nbytes], up[desc.nbytes:]
+        med = torch.empty(at, dtype=torch.float32, device=self.device)
+        boxes = torch.empty(G, k_per_image, 4, dtype=torch.int32, device=self.device)
+        dvals = torch.empty(G, k_per_image, dtype=torch.float32, device=self.device)
+        set_d = torch.empty(G, k_per_image, n_sets, dtype=torch.float32, device=self.device)
+        count = torch.empty(G, dtype=torch.int32, device=self.device)
+        p = lambda t: C.c_void_p(t.data_ptr())          # noqa: E731
+        self._check(self.lib.dm_mine_parallel(self._h, p(packed), p(desc_d), G, n_sets, p(gdesc_d), int(kx), int(ky), k_per_image,
+                                              1 if ascending else 0, p(prio) if prio is not None else None, p(med), p(boxes), p(dvals),
+                                              p(set_d), p(count), self._stream()), "dm_mine_parallel")
+        medians = [med[int(d["map_offset"]):int(d["map_offset"]) + (int(d["H"]) - kx + 1) * (int(d["W"]) - ky + 1)]
+                   .view(int(d["H"]) - kx + 1, int(d["W"]) - ky + 1) for d in gdesc]
+        return boxes, dvals, set_d, count, medians
 
     NORM_MODES = {"signed": 1, "maxabs": 2, "positive": 3, "split": 4}
 

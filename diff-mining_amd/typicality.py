@@ -641,6 +641,106 @@ class TypicalityScorer:
         order = np.argsort(-D.astype(np.float64), kind="stable")[:k]
         return {c: np.asarray(v)[order] for c, v in rows.items()}
 
+    # -- parallel-dataset mining: `Cluster.df_PD` (parallel-dataset/cluster.py:224-251) ---------------------------------
+    @staticmethod
+    def parallel_columns(set_names):
+        """`df_PD`'s columns (parallel-dataset/cluster.py:226), then `group` and `image` (both the group's index; `image` is the
+        key `boxes_by_image` groups by — a group's boxes are shared by its images)."""
+        return (["x_start", "y_start", "x_end", "y_end", "origin", "D"] + list(set_names) + ["path_" + c for c in set_names]
+                + ["group", "image"])
+
+    def mine_parallel_patches(self, groups, image_sizes, set_names, origins, k_per_image: int = 5, kx: int = 64, ky: int = 64,
+                              ascending: bool = False, randomized: bool = False, seed: int = 42, groups_per_call: int = 8):
+        """`Cluster.df_PD` (parallel-dataset/cluster.py:224-251) on the GPU.  A parallel group is a real image plus its
+        translations into the other sets (countries), all of one size.  groups[g]: per set, in `set_names` order, a grid
+        [N, n_cond, 4, h, w] or an image path whose stored grid is loaded from `<typicality_path>/<set name>/` (the reference
+        keeps one `D` per country, compute.py:184); image_sizes[g] = (H, W) of the group; origins[g]: the set the real image
+        belongs to (`country_origin`).  Per group: every set's pooled map (`load_typicallity`), the per-candidate median across
+        the sets, `sort` by it and `get_non_overlapping` — one `typicality_image_batched` call per groups_per_call x n_sets
+        images, then one `mine_parallel`; only the winners come back.
+
+        Returns `parallel_columns(set_names)` as a plain dict of numpy arrays, group order then round order: x_start, y_start,
+        x_end, y_end (int32, x = rows), origin, D (fp32, the median), one fp32 column per set name (that set's own value at
+        the box), path_<name> (the path, or g * n_sets + c when a grid was given), group and image (int64, the group's index).
+        `top_k` and `boxes_by_image` take it as it is.
+
+        randomized=True is `df_random` with `mine_patches`' rule and caveat: a permutation per group from
+        np.random.default_rng((seed, group index)); the reference's `random.shuffle` (cluster.py:235) is NOT seeded, so this arm
+        matches it in distribution, not in draws."""
+        G, n_sets = len(groups), len(set_names)
+        if G != len(image_sizes) or G != len(origins):
+            raise ValueError(f"{G} groups but {len(image_sizes)} image sizes and {len(origins)} origins")
+        if len(set(set_names)) != n_sets or any(len(g) != n_sets for g in groups):
+            raise ValueError(f"every group needs one entry per distinct set name ({n_sets}), got {[len(g) for g in groups]}")
+        if (kx == 1) != (ky == 1):
+            raise ValueError(f"window {kx}x{ky}: one side 1 and the other not is not a frame the reference can mine")
+        names = self.parallel_columns(set_names)
+        cols = {c: [] for c in ("group", "x_start", "y_start", "x_end", "y_end", "D")}
+        sets = []
+
+        def grid_of(g, c):
+            x = groups[g][c]
+            if isinstance(x, (str, os.PathLike)):
+                x = np.load(self.get_path(os.path.join(self.typicality_path, set_names[c]), x))
+            return torch.from_numpy(x) if isinstance(x, np.ndarray) else x
+        for g0 in range(0, G, groups_per_call):
+            idx = range(g0, min(G, g0 + groups_per_call))
+            maps = self.engine.typicality_image_batched([grid_of(g, c) for g in idx for c in range(n_sets)],
+                                                        [image_sizes[g] for g in idx for _ in range(n_sets)], kx, ky)
+            by_group = [maps[j * n_sets:(j + 1) * n_sets] for j in range(len(idx))]
+            prio = None
+            if randomized:
+                prio = []
+                for g, ms in zip(idx, by_group):
+                    perm = np.random.default_rng((seed, g)).permutation(ms[0].numel())
+                    prio.append(torch.from_numpy(self.permutation_priority(perm).reshape(tuple(ms[0].shape))))
+            boxes, dv, sd, cnt, _ = self.engine.mine_parallel(by_group, kx, ky, k_per_image, ascending and not randomized, prio)
+            boxes, dv, sd, cnt = boxes.cpu().numpy(), dv.cpu().numpy(), sd.cpu().numpy(), cnt.cpu().numpy()
+            for j, g in enumerate(idx):
+                c = int(cnt[j])
+                cols["group"].append(np.full(c, g, dtype=np.int64))
+                for q, name in enumerate(("x_start", "y_start", "x_end", "y_end")):
+                    cols[name].append(boxes[j, :c, q])
+                cols["D"].append(dv[j, :c])
+                sets.append(sd[j, :c])
+        cols = {c: np.concatenate(v) if v else np.zeros(0, np.int64 if c == "group" else np.float32 if c == "D" else np.int32)
+                for c, v in cols.items()}
+        sets = np.concatenate(sets, axis=0) if sets else np.zeros((0, n_sets), np.float32)
+        cols["origin"] = np.array([origins[g] for g in cols["group"]], dtype=object)
+        for c, name in enumerate(set_names):
+            cols[name] = np.ascontiguousarray(sets[:, c])
+            cols["path_" + name] = np.array([groups[g][c] if isinstance(groups[g][c], (str, os.PathLike)) else g * n_sets + c
+                                             for g in cols["group"]], dtype=object)
+        cols["image"] = cols["group"]
+        return {c: cols[c] for c in names}
+
+
+def parallel_groups(file_names_by_dir, dataset_path: str = ""):
+    """The grouping of `Typicality.load_paths` (parallel-dataset/compute.py:186-208) from file names alone.
+    file_names_by_dir: {country directory: its file names}.  In a directory `gt--<country>__<sid>` is a real image (the base
+    of a group), `<country>__<sid>` with no '--' in `<country>` one of its translations (a neighbour), anything else is
+    ignored; sid = the name without every '.jpg', after the first '__'.  Returns {directory: [group, ...]} with
+    group = [(base path, directory)] + [(neighbour path, neighbour's set)], paths joined onto dataset_path.
+
+    The reference's two splits are kept as they are: a file's own country is what precedes the first '__', but a neighbour's
+    set in the group is what precedes the first single '_' of its name (compute.py:207), so 'United_Kingdom__7.jpg' is filed
+    under 'United_Kingdom' and paired as 'United'.  Groups are sorted by base path and neighbours by path; the reference's
+    order is `os.listdir`'s, which no two machines share.  Of two bases with one sid the later one in sorted order stays."""
+    out = {}
+    for country_parent, names in file_names_by_dir.items():
+        seed_base, seeds = {}, {}
+        for seed in sorted(names):
+            sid = "__".join(seed.replace(".jpg", "").split("__")[1:])
+            country = seed.split("__")[0]
+            path = os.path.join(dataset_path, country_parent, seed)
+            if country.startswith("gt--"):
+                seed_base[sid] = path
+            elif "--" not in country:
+                seeds.setdefault(sid, []).append(path)
+        out[country_parent] = [[(v, country_parent)] + [(n, os.path.split(n)[1].split("_")[0]) for n in seeds.get(k, [])]
+                               for k, v in sorted(seed_base.items(), key=lambda kv: kv[1])]
+    return out
+
 
 def shard_indices(n_items: int, rank: int, world: int) -> Sequence[int]:
     """Image-major sharding `subs[i::sub_split]` of compute.py:339."""

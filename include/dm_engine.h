@@ -211,6 +211,28 @@ int dm_mine_patches(dm_engine* e, const void* maps_dev, const void* priority_dev
                     int ky, int k_per_image, int ascending, int32_t* boxes_out_dev, float* d_out_dev, int32_t* count_out_dev,
                     void* stream);
 
+/* ---- Parallel-dataset mining: the median map across sets (Cluster.df_PD, parallel-dataset/cluster.py:224-251) -------------
+ * A parallel group is n_sets pooled maps of one size (an image and its translations; one map per set, `load_typicallity`
+ * under the set's own category = dm_typicality_image_batched's output).  dm_mine_parallel, per group g:
+ *   1. median_out[g] = np.median(np.stack(maps of g), axis=0) per candidate: the middle of the n_sets sorted values, for an
+ *      even n_sets (s[n/2-1] + s[n/2]) * 0.5f; NaN when any of the n_sets values is NaN (numpy's rule).  Equal to np.median
+ *      under ==; bit-equal except the sign of a zero when +0 and -0 tie for the middle.
+ *   2. dm_mine_patches' selection on the median map (same kernel, same rules: inclusive zone, lowest row-major index among
+ *      equal keys, NaN never selected; priority_dev, laid out like median_out_dev, supplies the key of the shuffled arm).
+ *   3. set_d_out[g][r][c] = set c's own map at winner r (df_PD's per-country columns).
+ * maps_dev + desc[g*n_sets + c].map_offset is set c's map of group g (desc: n_groups*n_sets rows, group-major, the table
+ * dm_typicality_image_batched was called with; only map_offset, H, W are read); group_desc[g] places group g's median map
+ * [H-kx+1][W-ky+1] at median_out_dev + group_desc[g].map_offset (map_offset, H, W read).  Outputs: boxes_out_dev int32
+ * [n_groups][k_per_image][4], d_out_dev fp32 [n_groups][k_per_image] (the median at the winner), set_d_out_dev fp32
+ * [n_groups][k_per_image][n_sets], count_out_dev int32 [n_groups]; unused slots hold -1 / NaN.
+ * Refused (non-zero, dm_last_error): n_sets outside [1, DM_MINE_MAX_SETS], a set whose H / W differ from its group's, a
+ * window larger than an image, k_per_image outside [1, DM_MINE_MAX_K].  Reads both tables back once, like its siblings. */
+#define DM_MINE_MAX_SETS 16
+int dm_mine_parallel(dm_engine* e, const void* maps_dev, const dm_mine_desc* desc_dev, int n_groups, int n_sets,
+                     const dm_mine_desc* group_desc_dev, int kx, int ky, int k_per_image, int ascending, const void* priority_dev,
+                     void* median_out_dev, int32_t* boxes_out_dev, float* d_out_dev, float* set_d_out_dev, int32_t* count_out_dev,
+                     void* stream);
+
 /* Profiling support for bench.py: when enabled, every launch of the dominant (implicit-GEMM)
  * kernel is bracketed by hipEvents on the launch stream.  dm_prof_read synchronises and returns
  * the accumulated kernel milliseconds, launch count and algorithmic FLOPs since the last reset. */
