@@ -36,6 +36,7 @@ SYMBOLS = [
     "dm_resize_lanczos", "dm_f32_load_clip_vision_weight", "dm_f32_finalize_clip_vision", "dm_f32_clip_preprocess",
     "dm_f32_clip_image_features", "dm_f32_clip_vision_hidden", "dm_f32_clip_patch_features",
     "dm_typicality_image_batched", "dm_mine_patches", "dm_mine_parallel",
+    "dm_kmeans_workspace_bytes", "dm_kmeans_fit", "dm_cluster_rank",
 ]
 
 # dm_mine_desc of include/dm_engine.h (48 bytes) and the compile-time cap of k_per_image
@@ -238,6 +239,19 @@ class UNetEngine:
 
     def _stream(self):
         return C.c_void_p(self._torch.cuda.current_stream(self.device).cuda_stream)
+
+    def kmeans_fit(self, X, k: int = 32, seed: int = 10, max_iter: int = 300, tol: float = 1e-4, init_index=None, work=None):
+        """scikit-learn's `KMeans(n_clusters=k, random_state=seed).fit(X)` on this engine's device and current stream
+        (dm_kmeans_fit; see `clustering.kmeans_fit`)."""
+        from . import clustering
+        with self._torch.cuda.device(self.device):
+            return clustering.kmeans_fit(X, k, seed, max_iter, tol, init_index, work)
+
+    def cluster_rank(self, X, labels, centers, D, aggregate: str = "median", order_by: str = "centroid", rank_features=None, work=None):
+        """The tail of the reference's `cluster()` on the device (dm_cluster_rank; see `clustering.rank_clusters`)."""
+        from . import clustering
+        with self._torch.cuda.device(self.device):
+            return clustering.rank_clusters(X, labels, centers, D, aggregate, order_by, rank_features, work)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -830,6 +844,19 @@ class UNetEngineF32:
 
     def _stream(self):
         return C.c_void_p(self._torch.cuda.current_stream(self.device).cuda_stream)
+
+    def kmeans_fit(self, X, k: int = 32, seed: int = 10, max_iter: int = 300, tol: float = 1e-4, init_index=None, work=None):
+        """scikit-learn's `KMeans(n_clusters=k, random_state=seed).fit(X)` on this engine's device and current stream
+        (dm_kmeans_fit; see `clustering.kmeans_fit`)."""
+        from . import clustering
+        with self._torch.cuda.device(self.device):
+            return clustering.kmeans_fit(X, k, seed, max_iter, tol, init_index, work)
+
+    def cluster_rank(self, X, labels, centers, D, aggregate: str = "median", order_by: str = "centroid", rank_features=None, work=None):
+        """The tail of the reference's `cluster()` on the device (dm_cluster_rank; see `clustering.rank_clusters`)."""
+        from . import clustering
+        with self._torch.cuda.device(self.device):
+            return clustering.rank_clusters(X, labels, centers, D, aggregate, order_by, rank_features, work)
 
     def close(self):
         if getattr(self, "_h", None):

@@ -233,6 +233,56 @@ int dm_mine_parallel(dm_engine* e, const void* maps_dev, const dm_mine_desc* des
                      void* median_out_dev, int32_t* boxes_out_dev, float* d_out_dev, float* set_d_out_dev, int32_t* count_out_dev,
                      void* stream);
 
+/* ---- Clustering: scikit-learn's KMeans fit and the reference's ranked clusters (csrc/kmeans.hip) ------------------
+ * Stream-plus-workspace functions (no engine handle): every launch goes to `stream`; `work` is device memory of at least
+ * dm_kmeans_workspace_bytes(n, d, k) bytes whose contents do not matter.  They return 0 or one of the DM_KMEANS_E_* codes.
+ *
+ * dm_kmeans_fit = KMeans(n_clusters=k, random_state=seed).fit(X) as scikit-learn 1.4 ... 1.7 runs it (one k-means++ seeding in
+ * fp64, Lloyd in fp32 on mean-centred rows).  X: fp32 [n][d] row-major on the device.  uniforms_f64: the device array of the
+ * 1 + (k - 1) t draws k-means++ consumes, t = 2 + int(ln k) (clustering.kmeans_uniforms); NULL with n_uniforms = 0 means
+ * seed_index_i32 is an INPUT: the k rows to start from (KMeans(init=X[seed_index], n_init=1)).  tol_rel: scikit-learn's tol
+ * (1e-4); the loop stops strictly when the labels repeat, else when sum_j |c_new - c_old|^2 <= tol_rel * mean_j var_j(X), else at
+ * max_iter; after a non-strict stop the labels are assigned once more.  Ties: the lowest centre index; the first candidate of
+ * lowest potential; empty clusters, ascending, take the rows farthest from their own centre, descending, the lowest row among
+ * equals.  The stop is decided on the device; the host reads the flag once per group of iterations, so the call returns with the
+ * stream synchronised.  Outputs (device): labels_i32 [n], centers_f32 [k][d] (mean added back), seed_index_i32 [k], inertia_f32
+ * [1], n_iter_i32 [1].  No floating-point atomics: the same input gives the same bits on every run.
+ *
+ * dm_cluster_rank = the tail of the reference's cluster().  key_i = |x_rank_i - ref_label_i| (fp64 accumulation).
+ *   DM_RANK_CENTROID: ref_c = centers[c], x_rank = X, X_rank_or_null must be NULL (typicality/cluster.py:325, ranking.py:147);
+ *   DM_RANK_FARTHEST: ref_c = x_rank[argmax_i |X_i - centers[c]|] over ALL rows, the first among equals; x_rank = X_rank_or_null
+ *   [n][d_rank], or X when NULL (parallel-dataset/cluster.py:277-286).
+ * Members of a cluster are ordered by ascending key, stably by row.  The aggregate of D_f32 [n] over a cluster: DM_AGG_MEDIAN =
+ * np.median (mean of the two middle values for an even count, NaN if any member is NaN); DM_AGG_MEAN = the fp32 left-to-right
+ * sum in member order / count.  Clusters are ordered by descending aggregate, a NaN aggregate after every number, stably in the
+ * order of the label's first appearance by row.  Empty clusters do not appear.  labels must lie in [0, k) (a row whose label
+ * does not is left out).  Outputs (device): order [n] row ids, cluster-major; cluster_of_rank [k]; offsets [k + 1] into order;
+ * aggregate_out [k]; n_nonempty [1]; slots past n_nonempty hold -1 / n / NaN.  The place of a row costs O(members of its
+ * cluster): meant for the stage's thousands of rows.
+ * Refused: n < k, k outside [1, DM_KMEANS_MAX_K], d < 1, n >= 2^24, max_iter < 1, a wrong n_uniforms, a small workspace. */
+#define DM_KMEANS_MAX_K 256
+#define DM_KMEANS_E_NULL 1
+#define DM_KMEANS_E_N_LT_K 2
+#define DM_KMEANS_E_K 3
+#define DM_KMEANS_E_D 4
+#define DM_KMEANS_E_N_LARGE 5
+#define DM_KMEANS_E_MAX_ITER 6
+#define DM_KMEANS_E_UNIFORMS 7
+#define DM_KMEANS_E_WORK 8
+#define DM_KMEANS_E_MODE 9
+#define DM_KMEANS_E_HIP 10
+#define DM_RANK_CENTROID 0
+#define DM_RANK_FARTHEST 1
+#define DM_AGG_MEDIAN 0
+#define DM_AGG_MEAN 1
+int dm_kmeans_workspace_bytes(int n, int d, int k, size_t* bytes_out);
+int dm_kmeans_fit(void* stream, const void* X, int n, int d, int k, const double* uniforms_f64, int n_uniforms, int max_iter,
+                  float tol_rel, void* work, size_t work_bytes, int32_t* labels_i32, float* centers_f32, int32_t* seed_index_i32,
+                  float* inertia_f32, int32_t* n_iter_i32);
+int dm_cluster_rank(void* stream, const void* X, const void* X_rank_or_null, int n, int d, int d_rank, const int32_t* labels,
+                    const float* centers, int k, const float* D_f32, int mode, int aggregate, void* work, size_t work_bytes,
+                    int32_t* order, int32_t* cluster_of_rank, int32_t* offsets, float* aggregate_out, int32_t* n_nonempty);
+
 /* Profiling support for bench.py: when enabled, every launch of the dominant (implicit-GEMM)
  * kernel is bracketed by hipEvents on the launch stream.  dm_prof_read synchronises and returns
  * the accumulated kernel milliseconds, launch count and algorithmic FLOPs since the last reset. */
