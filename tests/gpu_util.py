@@ -136,6 +136,33 @@ def assert_close_fp16(got, ref, what, rel=2e-3, abs_frac=2e-3):
     return r, m
 
 
+# Tolerances that more than one test module asserts (the parity tests and tests/test_gpu_guards.py): one definition, so they cannot drift.
+TOL_FP16_CHAIN = dict(rel=3e-3, abs_frac=4e-3)      # fp16 output behind more than one rounding point: attention (P rounded to fp16 before P V), folded norm -> linear
+TOL_GEGLU = dict(rel=3e-3, abs_frac=3e-3)           # GEGLU epilogue: projection, gate and product each rounded to fp16
+TOL_ATTN512 = dict(rel=2e-3, abs_frac=3e-3)         # the VAE's single 512-wide head
+TOL_UPFOLD_OWN = dict(rel=4e-4, abs_frac=1.2e-3)    # folded up-sampler against its own arithmetic in fp32 (fp32 accumulation distance)
+TOL_TYPICALITY_SCALAR = 1e-6                        # T(x|c) of the batched reduction, relative to max(1, |T|)
+TOL_PATCH_EMBED = 2e-6                              # DIFT patch descriptor (unit vector) against float64
+
+
+def assert_splitk_matches_unsplit(y, ref):
+    """split-K against the fused single-pass kernel: identical except where the fp32 summation order flips an fp16 rounding (1 ulp, rare)"""
+    diff = (y.float() - ref.float()).abs()
+    assert (diff > 0).float().mean().item() < 0.02 and diff.max().item() <= 2e-3 * ref.float().abs().max().item()
+
+
+def assert_block_sums(blocks, ref, scale):
+    """GroupNorm block sums (fp32) against the fp64 sums `ref` of the fp16 tensor; `scale` = the same sums of |x|"""
+    assert ((blocks.double() - ref).abs() <= 4e-6 * scale + 1e-6).all()
+
+
+def assert_conv_out_pred(pred, ref, what=""):
+    """conv_out's fp16 prediction against F.conv2d in fp64 `ref`: the fp16 rounding of an fp32 sum of 2880 exact products"""
+    err = (pred.double().cpu() - ref).abs()
+    ulp = torch.maximum(ref.abs(), torch.tensor(2.0 ** -14, dtype=torch.float64)) * 2.0 ** -10
+    assert (err <= 0.5 * ulp + 1e-5).all(), (what, (err / ulp).max().item())
+
+
 def fold_upconv_torch(w):
     """Upsample2D (nearest 2x) + conv3x3 folded onto the source grid, built with torch: w [Cout,Cin,3,3] ->
     [4 = py*2+px][Cout][(a*2+b)*Cin + ci] fp16; the 3x3 taps that read the same source pixel are summed in fp32, rounded once."""
@@ -176,6 +203,95 @@ def op_attention512(q, k, v):
     assert rc == 0
     torch.cuda.synchronize()
     return o
+
+
+class GuardViolation(AssertionError):
+    """Raised by Guarded.check(): `name` of the tensor, `side` ("front" / "back" guard, or "payload" for a written input), `first` / `last`
+    changed byte offset relative to the payload edge (front and payload: relative to the payload's first byte, so a front offset is
+    negative; back: relative to the first byte after the payload) and the `count` of changed bytes."""
+
+    def __init__(self, name, side, first, last, count):
+        self.name, self.side, self.first, self.last, self.count = name, side, first, last, count
+        super().__init__(f"{name}: {count} byte(s) changed in its {side}{'' if side == 'payload' else ' guard'}, "
+                         f"offsets {first} ... {last} relative to the payload's {'end' if side == 'back' else 'start'}")
+
+
+def _round256(n):
+    return (int(n) + 255) // 256 * 256
+
+
+class Guarded:
+    """All device operands of one operator call inside ONE uint8 allocation, [guard | payload | guard | guard | payload | guard ...]: an
+    access outside a tensor that is shorter than the guard stays inside memory the test owns, and shows — a store as a changed guard byte
+    (check()), a load that reaches the result as a result that depends on the fill byte.
+
+    inputs   {name: host tensor}: copied in; check() also verifies they come back unchanged (an operator must not write its inputs)
+    outputs  {name: (shape, dtype)}: outputs and workspaces, pre-filled with the fill byte (0xFF: NaN in fp16 / fp32, -1 in int32)
+    fill     the byte every guard and every output payload holds before the call
+    Every payload starts at an odd multiple of 256 bytes (256 = the engine arena's granularity, the only alignment its kernels get).  The
+    guard on either side of a tensor is `tile_rows` (256) rows of its row pitch (last dimension; vectors and scalars have no rows), at
+    least `min_guard` (64 KiB), rounded up to 256; a payload's own padding to 256 belongs to its back guard."""
+
+    def __init__(self, inputs, outputs=None, fill=0xFF, device="cpu", tile_rows=256, min_guard=64 * 1024):
+        self.fill = int(fill)
+        specs = [(n, tuple(t.shape), t.dtype, t.contiguous()) for n, t in inputs.items()]
+        specs += [(n, tuple(int(v) for v in s), dt, None) for n, (s, dt) in (outputs or {}).items()]
+        assert len({s[0] for s in specs}) == len(specs), "operand names must be unique"
+        self.layout = {}            # name -> (front guard start, payload start, payload end, back guard end, shape, dtype, is_input)
+        off = 0                     # offsets from an even multiple of 256 (`origin` below)
+        for name, shape, dt, host in specs:
+            es = torch.empty(0, dtype=dt).element_size()
+            nbytes = es * int(np.prod(shape, dtype=np.int64))
+            guard = _round256(max(tile_rows * shape[-1] * es if len(shape) >= 2 else 0, min_guard))
+            start = off + guard
+            if (start // 256) % 2 == 0:
+                start += 256
+            back = _round256(start + nbytes) + guard
+            self.layout[name] = (off, start, start + nbytes, back, shape, dt, host is not None)
+            off = back
+        raw = torch.full((off + 512,), self.fill, dtype=torch.uint8, device=device)
+        origin = -raw.data_ptr() % 512
+        self.buf = raw[origin:origin + off]
+        for name, _, _, host in specs:
+            _, start, end, _, _, _, _ = self.layout[name]
+            assert (self.buf.data_ptr() + start) % 512 == 256
+            if host is not None and end > start:
+                self.buf[start:end] = host.reshape(-1).view(torch.uint8).to(device)
+        self.guard_bytes = {n: (L[1] - L[0], L[3] - L[2]) for n, L in self.layout.items()}
+        self._inputs = {n: self.view(n).clone() for n, _, _, h in specs if h is not None}      # (output payloads are not kept)
+
+    def view(self, name):
+        _, start, end, _, shape, dt, _ = self.layout[name]
+        return self.buf[start:end].view(dt).view(shape)
+
+    def views(self):
+        return {n: self.view(n) for n in self.layout}
+
+    def offset(self, name):
+        """byte address of the payload: an odd multiple of 256"""
+        return self.buf.data_ptr() + self.layout[name][1]
+
+    def _regions(self):
+        for name, (front, start, end, back, _, _, is_input) in self.layout.items():
+            yield name, "front", front, start, start
+            if is_input:
+                yield name, "payload", start, end, start
+            yield name, "back", end, back, end
+
+    def _changed(self, name, side, a, b):
+        if side == "payload":
+            return self.buf[a:b] != self._inputs[name].reshape(-1).view(torch.uint8)
+        return self.buf[a:b] != self.fill
+
+    def check(self):
+        """every guard still holds the fill and every input its bytes, else GuardViolation for the first damaged region in layout order"""
+        flags = torch.stack([self._changed(n, side, a, b).any() for n, side, a, b, _ in self._regions() if b > a])
+        if not bool(flags.any()):
+            return
+        for name, side, a, b, origin in self._regions():
+            idx = self._changed(name, side, a, b).nonzero().flatten() if b > a else torch.empty(0)
+            if idx.numel():
+                raise GuardViolation(name, side, int(idx[0]) + a - origin, int(idx[-1]) + a - origin, int(idx.numel()))
 
 
 def line_rel_l2(got, ref):

@@ -552,7 +552,7 @@ def test_compute_losses_batch_is_bit_equal_to_the_per_image_calls(engine, h, w, 
     assert torch.equal(g1[0], grids[0]) and torch.equal(g1[2], sc.compute_losses(x[2:3].to(d), emb[0].to(d), to_host=False))
     _, sc_b = engine.reduce_typicality_batched(grids, n, N, 2)
     for j in range(n):
-        assert abs(sc_b[j].item() - sc.typicality_scalar(grids[j]).item()) <= 1e-6 * max(1.0, abs(sc_b[j].item()))
+        assert abs(sc_b[j].item() - sc.typicality_scalar(grids[j]).item()) <= U.TOL_TYPICALITY_SCALAR * max(1.0, abs(sc_b[j].item()))
     if h <= 16:
         # a single condition per image (n_cond = 1: dm_score with the slot of each image's prompt) and per-image draws
         g_one = sc.compute_losses_batch(x.to(d), emb[:, :1].to(d), to_host=False)
@@ -601,7 +601,7 @@ def test_dift_patch_embeddings(engine):
     assert out.shape == (5, 1280)
     for i, b in enumerate(boxes):
         ref = R.dift_patch_embedding(feat[0].numpy().astype(np.float64), b, image_hw)
-        assert np.abs(out[i] - ref).max() < 2e-6, (i, np.abs(out[i] - ref).max())
+        assert np.abs(out[i] - ref).max() < U.TOL_PATCH_EMBED, (i, np.abs(out[i] - ref).max())
         assert abs(np.linalg.norm(out[i]) - 1) < 1e-5
     assert feature_boxes([(100, 50, 300, 250)], image_hw, (32, 24)).tolist() == [[6, 18, 3, 15]]
     calls = []

@@ -69,7 +69,8 @@ def test_fit_is_bit_reproducible_on_any_stream_and_workspace(gold, inputs, fits,
     init = gold["empty_seed_index"] if tag == "empty" else None
     Xd = torch.from_numpy(X).cuda()
     assert _same(CL.kmeans_fit(Xd, k, init_index=init), fits[tag])
-    work = torch.full((CL.workspace_bytes(*X.shape, k) + 64,), 0xFF, dtype=torch.uint8, device="cuda")      # nothing relies on zeroed scratch
+    need = CL.workspace_bytes(*X.shape, k)
+    work = torch.full((need + 64,), 0xFF, dtype=torch.uint8, device="cuda")      # nothing relies on zeroed scratch
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
@@ -78,6 +79,7 @@ def test_fit_is_bit_reproducible_on_any_stream_and_workspace(gold, inputs, fits,
         D = torch.from_numpy(KC.typicality(len(X), 5)).cuda()
         r1 = CL.rank_clusters(Xd, labels, again[1], D, work=work.fill_(0xFF))
     side.synchronize()
+    assert (work[need:] == 0xFF).all(), "the 64 bytes behind the workspace were written"
     assert _same(again, fits[tag])
     assert _same(r1, CL.rank_clusters(Xd, labels, fits[tag][1], D))
 

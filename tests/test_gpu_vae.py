@@ -94,7 +94,7 @@ def test_attention512(B, T):
     v = U.f16_randn(B, T, 512, seed=23)
     ref = torch.softmax(torch.matmul(q.float(), k.float().transpose(1, 2)) * 512 ** -0.5, dim=-1) @ v.float()
     o = _attn512(q, k, v)
-    U.assert_close_fp16(o, ref, f"attention512 T={T}", rel=2e-3, abs_frac=3e-3)
+    U.assert_close_fp16(o, ref, f"attention512 T={T}", **U.TOL_ATTN512)
 
 
 def test_attention512_peaked_rows():
@@ -105,7 +105,7 @@ def test_attention512_peaked_rows():
     v = U.f16_randn(B, T, 512, seed=33)
     ref = torch.softmax(torch.matmul(q.float(), k.float().transpose(1, 2)) * 512 ** -0.5, dim=-1) @ v.float()
     o = _attn512(q, k, v)
-    U.assert_close_fp16(o, ref, "attention512 peaked", rel=2e-3, abs_frac=3e-3)
+    U.assert_close_fp16(o, ref, "attention512 peaked", **U.TOL_ATTN512)
 
 
 def _oracle(vae_sd, img, noise, autocast=True):
