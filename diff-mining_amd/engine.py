@@ -37,6 +37,7 @@ SYMBOLS = [
     "dm_f32_clip_image_features", "dm_f32_clip_vision_hidden", "dm_f32_clip_patch_features",
     "dm_typicality_image_batched", "dm_mine_patches", "dm_mine_parallel",
     "dm_kmeans_workspace_bytes", "dm_kmeans_fit", "dm_cluster_rank",
+    "dm_xray_eval_workspace_bytes", "dm_xray_eval",
 ]
 
 # dm_mine_desc of include/dm_engine.h (48 bytes) and the compile-time cap of k_per_image
@@ -252,6 +253,13 @@ class UNetEngine:
         from . import clustering
         with self._torch.cuda.device(self.device):
             return clustering.rank_clusters(X, labels, centers, D, aggregate, order_by, rank_features, work)
+
+    def xray_eval(self, maps, boxes, thresholds=None, work=None):
+        """The counts of the X-ray application's AUC-PR and the box sums for a batch of heat-maps on this engine's device and
+        current stream (dm_xray_eval; see `xray.xray_eval`)."""
+        from . import xray
+        with self._torch.cuda.device(self.device):
+            return xray.xray_eval(maps, boxes, thresholds, work)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -857,6 +865,13 @@ class UNetEngineF32:
         from . import clustering
         with self._torch.cuda.device(self.device):
             return clustering.rank_clusters(X, labels, centers, D, aggregate, order_by, rank_features, work)
+
+    def xray_eval(self, maps, boxes, thresholds=None, work=None):
+        """The counts of the X-ray application's AUC-PR and the box sums for a batch of heat-maps on this engine's device and
+        current stream (dm_xray_eval; see `xray.xray_eval`)."""
+        from . import xray
+        with self._torch.cuda.device(self.device):
+            return xray.xray_eval(maps, boxes, thresholds, work)
 
     def close(self):
         if getattr(self, "_h", None):

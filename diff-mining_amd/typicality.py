@@ -561,6 +561,55 @@ class TypicalityScorer:
         """`Typicallity.compute` dm_pixel (xray/compute.py:210-218): per-pixel E_N[L_null - L_c] at image size."""
         return self.engine.typicality_image(grid, image_size, 1, 1)
 
+    # -- X-ray evaluation: `mean_typicallity` / `aucpr` / `main` (xray/compute.py:263-332) -------------------------------
+    def xray_evaluate(self, grids_or_paths, image_sizes, boxes, images_per_call: int = 8):
+        """`mean_typicallity` and `aucpr` (xray/compute.py:263-284) of the per-pixel maps of a list of images, on the GPU: per
+        call of `images_per_call` images one `typicality_image_batched(..., 1, 1)` and one `xray_eval` on its packed maps, which
+        never leave the device; only the threshold counts come back, and the reference's last lines run on them on the host
+        (`xray.xray_scores_from_counts`).  grids_or_paths: per image a grid [N, n_cond, 4, h, w] or an image path whose stored
+        grid is loaded as `__call__` does; image_sizes: per image (H, W); boxes: per image (x1, y1, x2, y2), x = columns, as
+        `xray.load_boxes` gives them.  Returns {'mean_typicality': fp32 [n], 'auc': fp64 [n]}; both NaN for an empty box.
+
+        image_sizes is (H, W).  The reference passes `pil.size`, which is (W, H), to `interpolate` (xray/compute.py:301): a slip
+        that transposes the map of a non-square image and is harmless for the square images it uses."""
+        from . import xray
+        n = len(grids_or_paths)
+        if n != len(image_sizes) or n != len(boxes):
+            raise ValueError(f"{n} grids but {len(image_sizes)} image sizes and {len(boxes)} boxes")
+        mean, auc = np.empty(n, dtype=np.float32), np.empty(n, dtype=np.float64)
+        thr = xray.xray_thresholds()
+        for c0 in range(0, n, images_per_call):
+            idx = range(c0, min(n, c0 + images_per_call))
+            grids = [self(g) if isinstance(g, (str, os.PathLike)) else g for g in (grids_or_paths[i] for i in idx)]
+            grids = [torch.from_numpy(g) if isinstance(g, np.ndarray) else g for g in grids]
+            maps = self.engine.typicality_image_batched(grids, [image_sizes[i] for i in idx], 1, 1)
+            tp, fp, n_in, box_sum = self.engine.xray_eval(maps, [boxes[i] for i in idx], thr)
+            mean[c0:c0 + len(idx)], auc[c0:c0 + len(idx)] = xray.xray_scores_from_counts(tp, fp, n_in, box_sum)
+        return {"mean_typicality": mean, "auc": auc}
+
+    def xray_report(self, parent, output_path: str, image_sizes=None, images_per_call: int = 8):
+        """`Typicallity.main` (xray/compute.py:286-332): parent = {finding: [(image path, box), ...]} (`xray.load_boxes`) ->
+        `<output_path>/report.json` and `auc.json`, {finding: {file name: float}} in parent's order, a finding without entries
+        dropped.  The grids are the stored ones (`__call__`).  image_sizes: {image path: (H, W)}; an image that is not in it is
+        opened for its size.  Returns (report, auc)."""
+        from . import xray
+
+        def size_of(path):
+            if image_sizes is not None and path in image_sizes:
+                return tuple(image_sizes[path])
+            from PIL import Image
+            with Image.open(path) as im:
+                return im.size[1], im.size[0]
+        names, means, aucs = {}, {}, {}
+        for disease, entries in parent.items():
+            if not len(entries):
+                continue
+            paths = [e[0] for e in entries]
+            got = self.xray_evaluate(paths, [size_of(p) for p in paths], [e[1] for e in entries], images_per_call)
+            names[disease] = [os.path.split(p)[-1] for p in paths]
+            means[disease], aucs[disease] = got["mean_typicality"], got["auc"]
+        return xray.write_reports(output_path, list(parent.keys()), names, means, aucs)
+
 
     # -- patch mining: `Cluster.df_D` (cluster.py:184-215) + `get_top_k` (utils.py:237-252) -----------------------------
     MINE_COLUMNS = ("seed", "x_start", "y_start", "x_end", "y_end", "D", "origin")

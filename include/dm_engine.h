@@ -283,6 +283,36 @@ int dm_cluster_rank(void* stream, const void* X, const void* X_rank_or_null, int
                     const float* centers, int k, const float* D_f32, int mode, int aggregate, void* work, size_t work_bytes,
                     int32_t* order, int32_t* cluster_of_rank, int32_t* offsets, float* aggregate_out, int32_t* n_nonempty);
 
+/* ---- X-ray evaluation: threshold counts of a heat-map against a ground-truth box (csrc/xray_eval.hip) -------------
+ * The device half of `aucpr` and `mean_typicallity` (applications/xray/compute.py:263-284).  A stream-plus-workspace function
+ * (no engine handle).  Row r of the descriptor table names a map [H][W] fp32 at maps_dev + map_offset (floats, any value; two
+ * rows may name one map) and a box (x1, y1, x2, y2) = dm[y1:y2, x1:x2]: x = COLUMNS, clipped to the map as numpy clips a slice,
+ * possibly empty.  thresholds_dev: n_thresholds fp64 values, strictly decreasing.  Per row, for k in [0, T):
+ *   tp[k] = pixels inside the box with (double)v > thresholds[k];  fp[k] = the same outside;  (fp32 value against fp64
+ *   threshold, in fp64, strictly: a NaN pixel exceeds nothing);  n_in = the clipped box's area;  box_sum = the fp64 sum of
+ *   the pixels inside (NaN if one is NaN; 0 for an empty box).
+ * Counts are integers (LDS integer atomics, per-workgroup partials added in a fixed order): exact.  box_sum has no floating-point
+ * atomic and a pixel-to-thread map that depends on the pixel's index alone: the same map and box give the same bits at any
+ * position of any batch.  work_dev: at least dm_xray_eval_workspace_bytes(n_rows, n_thresholds, max_r H_r W_r) bytes (0 = bad
+ * arguments) whose contents do not matter.  Reads the two tables back once, so it synchronises `stream` before it launches.
+ * Refused without a launch (DM_XRAY_E_*): n_thresholds outside [1, DM_XRAY_MAX_THRESHOLDS]; thresholds not strictly decreasing
+ * or NaN; H or W < 1; H W >= 2^24 (the reference's x.sum() is an fp32 sum of ones); a negative box coordinate (numpy would
+ * count it from the end). */
+#define DM_XRAY_MAX_THRESHOLDS 4096
+#define DM_XRAY_E_NULL 1
+#define DM_XRAY_E_ROWS 2
+#define DM_XRAY_E_NTHR 3
+#define DM_XRAY_E_THR_ORDER 4
+#define DM_XRAY_E_SIZE 5
+#define DM_XRAY_E_PIXELS 6
+#define DM_XRAY_E_BOX 7
+#define DM_XRAY_E_HIP 8
+typedef struct dm_xray_desc { int64_t map_offset; int32_t H, W; int32_t x1, y1, x2, y2; } dm_xray_desc;
+size_t dm_xray_eval_workspace_bytes(int n_rows, int n_thresholds, int64_t max_pixels);
+int dm_xray_eval(const void* maps_dev, const dm_xray_desc* desc_dev, int n_rows, const double* thresholds_dev, int n_thresholds,
+                 void* work_dev, int32_t* tp_out_dev /*[n_rows][T]*/, int32_t* fp_out_dev /*[n_rows][T]*/,
+                 int32_t* n_in_out_dev /*[n_rows]*/, double* box_sum_out_dev /*[n_rows]*/, void* stream);
+
 /* Profiling support for bench.py: when enabled, every launch of the dominant (implicit-GEMM)
  * kernel is bracketed by hipEvents on the launch stream.  dm_prof_read synchronises and returns
  * the accumulated kernel milliseconds, launch count and algorithmic FLOPs since the last reset. */
