@@ -26,6 +26,8 @@ import math
 
 import numpy as np
 
+from .engine import EngineError, _p, load_library as _lib
+
 KMEANS_MAX_K = 256           # DM_KMEANS_MAX_K
 KMEANS_MAX_N = 1 << 24       # n >= 2^24 is refused
 RANK_CENTROID, RANK_FARTHEST = 0, 1
@@ -205,18 +207,7 @@ def rank_clusters_host(X, labels, centers, D, aggregate: str = "median", order_b
 # ------------------------------------------------------------------------------------------------------------------------------
 # the device path
 # ------------------------------------------------------------------------------------------------------------------------------
-def _lib():
-    from .engine import load_library
-    lib = load_library()
-    vp, i32 = C.c_void_p, C.c_int
-    lib.dm_kmeans_workspace_bytes.argtypes = [i32, i32, i32, C.POINTER(C.c_size_t)]
-    lib.dm_kmeans_fit.argtypes = [vp, vp, i32, i32, i32, vp, i32, i32, C.c_float, vp, C.c_size_t, vp, vp, vp, vp, vp]
-    lib.dm_cluster_rank.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i32, vp, i32, i32, vp, C.c_size_t, vp, vp, vp, vp, vp]
-    return lib
-
-
 def _fail(what, rc):
-    from .engine import EngineError
     raise EngineError(f"{what}: {ERRORS.get(rc, 'error')} (code {rc})")
 
 
@@ -226,10 +217,6 @@ def workspace_bytes(n: int, d: int, k: int) -> int:
     if rc:
         _fail("dm_kmeans_workspace_bytes", rc)
     return out.value
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
 def _dev_f32(x, device=None):
@@ -248,7 +235,6 @@ def kmeans_fit(X, k: int = 32, seed: int = 10, max_iter: int = 300, tol: float =
     seeding.  work: a uint8 workspace of at least `workspace_bytes(n, d, k)` to reuse (its contents do not matter).
     There is no host path behind this call: without a GPU it raises; `kmeans_fit_host` is the numpy restatement."""
     import torch
-    from .engine import EngineError
     if not (isinstance(X, torch.Tensor) and X.is_cuda):
         raise EngineError("kmeans_fit: X must be a torch tensor on the GPU (kmeans_fit_host is the numpy restatement)")
     if X.dim() != 2:
@@ -286,7 +272,6 @@ def rank_clusters(X, labels, centers, D, aggregate: str = "median", order_by: st
     """The tail of the reference's `cluster()` on the device (dm_cluster_rank); arguments and results as `rank_clusters_host`,
     as device tensors (n_nonempty: int32 [])."""
     import torch
-    from .engine import EngineError
     if order_by not in _MODES or aggregate not in _AGGS:
         raise EngineError(f"rank_clusters: order_by {order_by!r} / aggregate {aggregate!r}")
     if not (isinstance(X, torch.Tensor) and X.is_cuda):

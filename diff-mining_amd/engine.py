@@ -16,29 +16,108 @@ LIB_PATH = os.path.join(_HERE, "lib", "libdm_engine.so")
 _lib = None
 _CHECK_DEVICE_SLOTS = os.environ.get("DM_CHECK_SLOTS", "0") not in ("", "0")     # debug: validate prompt slots that live on the GPU
 
-# every symbol include/dm_engine.h declares (checked by tests/test_abi.py)
-SYMBOLS = [
-    "dm_version", "dm_scheduler_alphas_cumprod", "dm_timestep_sinusoid", "dm_engine_create",
-    "dm_engine_destroy", "dm_last_error", "dm_engine_load_weight", "dm_engine_finalize",
-    "dm_engine_set_prompts", "dm_score", "dm_score_conds", "dm_score_conds_slots", "dm_unet_forward", "dm_dift", "dm_dift_shape",
-    "dm_reduce_typicality", "dm_typicality_image", "dm_prof_enable", "dm_prof_read", "dm_engine_memory",
-    "dm_op_igemm", "dm_op_attention", "dm_op_groupnorm", "dm_op_layernorm",
-    "dm_op_conv_temb_gn_blocks", "dm_op_gn_blocks", "dm_op_groupnorm_blocks", "dm_op_conv_out",
-    "dm_engine_load_vae_weight", "dm_engine_finalize_vae", "dm_vae_encode", "dm_op_attention512", "dm_patch_embed",
-    "dm_engine_load_clip_weight", "dm_engine_finalize_clip", "dm_clip_encode", "dm_op_igemm_splitk",
-    "dm_op_ln_stats", "dm_op_igemm_ln", "dm_reduce_typicality_batched", "dm_op_igemm_tile", "dm_op_attention_route", "dm_op_attention_slots", "dm_op_igemm_head_rows", "dm_set_option",
-    "dm_engine_reserve", "dm_engine_stats", "dm_op_groupnorm_conv1x1", "dm_op_igemm_shortcut", "dm_normalize_map",
-    "dm_op_fold_upconv_weights", "dm_op_upconv_folded", "dm_prof_read_folded", "dm_get_option", "dm_measure_mfma_rate",
-    "dm_f32_create", "dm_f32_destroy", "dm_f32_last_error", "dm_f32_load_weight", "dm_f32_finalize", "dm_f32_set_prompts",
-    "dm_f32_unet_forward", "dm_f32_dift", "dm_f32_prof_enable", "dm_f32_prof_read", "dm_f32_memory", "dm_f32_op_gemm",
-    "dm_f32_op_attention", "dm_f32_op_groupnorm", "dm_f32_op_layernorm", "dm_f32_load_vae_weight", "dm_f32_finalize_vae",
-    "dm_f32_vae_encode", "dm_f32_score", "dm_f32_load_clip_weight", "dm_f32_finalize_clip", "dm_f32_clip_encode",
-    "dm_resize_lanczos", "dm_f32_load_clip_vision_weight", "dm_f32_finalize_clip_vision", "dm_f32_clip_preprocess",
-    "dm_f32_clip_image_features", "dm_f32_clip_vision_hidden", "dm_f32_clip_patch_features",
-    "dm_typicality_image_batched", "dm_mine_patches", "dm_mine_parallel",
-    "dm_kmeans_workspace_bytes", "dm_kmeans_fit", "dm_cluster_rank",
-    "dm_xray_eval_workspace_bytes", "dm_xray_eval",
-]
+_vp, _cp, _i32, _i64, _f32, _sz = C.c_void_p, C.c_char_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
+_pvp, _pi32, _pi64, _pf32, _pf64, _psz = (C.POINTER(t) for t in (_vp, _i32, _i64, _f32, C.c_double, _sz))
+_WEIGHT = [_vp, _cp, _vp, _i32, _pi64, _i32]        # (handle, name, host_ptr, dtype, shape, ndim) of every *_load_*weight
+_PROF = [_vp, _pf64, _pf64, _pi64, _pf64, _pf64, _pi64]
+
+# The C signature of every symbol include/dm_engine.h declares, in the header's order: name -> (restype, argtypes).  This is the one
+# place a signature is written down; load_library() applies it and tests/test_abi.py checks it against the header argument by argument.
+SIGNATURES = {
+    "dm_version": (_cp, []),
+    "dm_scheduler_alphas_cumprod": (_i32, [_i32, _f32, _f32, _pf32]),
+    "dm_timestep_sinusoid": (_i32, [_i32, _i32, _pf32]),
+    "dm_engine_create": (_i32, [_i32, _pvp]),
+    "dm_engine_destroy": (None, [_vp]),
+    "dm_last_error": (_cp, [_vp]),
+    "dm_engine_load_weight": (_i32, _WEIGHT),
+    "dm_engine_finalize": (_i32, [_vp]),
+    "dm_engine_set_prompts": (_i32, [_vp, _vp, _i32, _vp]),
+    "dm_score": (_i32, [_vp] * 6 + [_i32] * 5 + [_vp, _vp]),
+    "dm_score_conds": (_i32, [_vp] * 5 + [_i32] * 6 + [_vp, _vp]),
+    "dm_score_conds_slots": (_i32, [_vp] * 6 + [_i32] * 6 + [_vp, _vp]),
+    "dm_unet_forward": (_i32, [_vp] * 4 + [_i32, _i32, _i32, _vp, _vp]),
+    "dm_dift": (_i32, [_vp] * 4 + [_i32] * 4 + [_vp, _vp, _i32, _vp]),
+    "dm_dift_shape": (_i32, [_i32, _i32, _i32, _pi32, _pi32, _pi32]),
+    "dm_reduce_typicality": (_i32, [_vp, _vp] + [_i32] * 5 + [_vp, _vp, _vp]),
+    "dm_reduce_typicality_batched": (_i32, [_vp, _vp] + [_i32] * 7 + [_vp, _vp, _vp]),
+    "dm_typicality_image": (_i32, [_vp, _vp] + [_i32] * 9 + [_vp, _vp, _vp]),
+    "dm_normalize_map": (_i32, [_vp, _vp, _i64, _i32] + [_vp] * 4),
+    "dm_resize_lanczos": (_i32, [_vp, _vp, _vp] + [_i32] * 4 + [_vp, _vp, _vp]),
+    "dm_typicality_image_batched": (_i32, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "dm_mine_patches": (_i32, [_vp] * 4 + [_i32] * 5 + [_vp] * 4),
+    "dm_mine_parallel": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp] + [_i32] * 4 + [_vp] * 7),
+    "dm_kmeans_workspace_bytes": (_i32, [_i32, _i32, _i32, _psz]),
+    "dm_kmeans_fit": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _f32, _vp, _sz] + [_vp] * 5),
+    "dm_cluster_rank": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _sz] + [_vp] * 5),
+    "dm_xray_eval_workspace_bytes": (_sz, [_i32, _i32, _i64]),
+    "dm_xray_eval": (_i32, [_vp, _vp, _i32, _vp, _i32] + [_vp] * 6),
+    "dm_prof_enable": (_i32, [_vp, _i32]),
+    "dm_measure_mfma_rate": (_i32, [_vp, _i32, _i32, _pf64, _pf64]),
+    "dm_prof_read": (_i32, _PROF),
+    "dm_prof_read_folded": (_i32, [_vp, _pf64]),
+    "dm_engine_load_vae_weight": (_i32, _WEIGHT),
+    "dm_engine_finalize_vae": (_i32, [_vp]),
+    "dm_vae_encode": (_i32, [_vp, _vp, _vp] + [_i32] * 4 + [_f32] + [_vp] * 4),
+    "dm_engine_load_clip_weight": (_i32, _WEIGHT),
+    "dm_engine_finalize_clip": (_i32, [_vp]),
+    "dm_clip_encode": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "dm_patch_embed": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp]),
+    "dm_engine_memory": (_i32, [_vp, _psz, _psz]),
+    "dm_engine_reserve": (_i32, [_vp] + [_i32] * 5 + [_vp]),
+    "dm_engine_stats": (_i32, [_vp, _pi64, _pi64, _pi64]),
+    "dm_op_igemm": (_i32, [_vp] * 8 + [_i32] * 11),
+    "dm_set_option": (_i32, [_cp, _i32]),
+    "dm_get_option": (_i32, [_cp, _pi32]),
+    "dm_op_igemm_tile": (_i32, [_i32] * 4),
+    "dm_op_igemm_head_rows": (_i32, [_i32] * 5),
+    "dm_op_attention": (_i32, [_vp] * 5 + [_i32] * 4 + [_i64] * 4 + [_vp] + [_i32] * 5 + [_f32]),
+    "dm_op_attention_slots": (_i32, [_vp] * 5 + [_i32] * 4 + [_i64] * 4 + [_vp] + [_i32] * 8 + [_f32]),
+    "dm_op_attention_route": (_i32, [_i32] * 6),
+    "dm_op_ln_stats": (_i32, [_vp, _vp, _i32, _i32, _f32, _vp]),
+    "dm_op_igemm_ln": (_i32, [_vp] * 7 + [_i32] * 4),
+    "dm_op_igemm_splitk": (_i32, [_vp] * 8 + [_i32] * 11 + [_vp]),
+    "dm_op_attention512": (_i32, [_vp] * 5 + [_i32] * 4 + [_f32]),
+    "dm_op_groupnorm": (_i32, [_vp, _vp, _vp] + [_i32] * 5 + [_f32, _vp, _vp, _i32, _vp]),
+    "dm_op_layernorm": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _f32, _vp]),
+    "dm_op_conv_out": (_i32, [_vp] * 5 + [_i32] * 4 + [_vp, _vp]),
+    "dm_op_conv_temb_gn_blocks": (_i32, [_vp] * 6 + [_i32] * 6 + [_vp, _pi32]),
+    "dm_op_gn_blocks": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp]),
+    "dm_op_groupnorm_blocks": (_i32, [_vp, _vp, _vp] + [_i32] * 4 + [_f32, _vp, _vp, _i32, _vp]),
+    "dm_op_igemm_shortcut": (_i32, [_vp] * 8 + [_i32] * 8),
+    "dm_op_fold_upconv_weights": (_i32, [_vp, _i32, _i32, _vp]),
+    "dm_op_upconv_folded": (_i32, [_vp] * 5 + [_i32] * 5),
+    "dm_op_groupnorm_conv1x1": (_i32, [_vp, _vp] + [_i32] * 4 + [_f32] + [_vp] * 4 + [_i32, _vp]),
+    "dm_f32_create": (_i32, [_i32, _pvp]),
+    "dm_f32_destroy": (None, [_vp]),
+    "dm_f32_last_error": (_cp, [_vp]),
+    "dm_f32_load_weight": (_i32, _WEIGHT),
+    "dm_f32_finalize": (_i32, [_vp]),
+    "dm_f32_set_prompts": (_i32, [_vp, _vp, _i32, _vp]),
+    "dm_f32_unet_forward": (_i32, [_vp] * 4 + [_i32, _i32, _i32, _vp, _vp]),
+    "dm_f32_dift": (_i32, [_vp] * 4 + [_i32] * 4 + [_vp, _vp, _i32, _vp]),
+    "dm_f32_score": (_i32, [_vp] * 6 + [_i32] * 4 + [_vp, _vp]),
+    "dm_f32_load_vae_weight": (_i32, _WEIGHT),
+    "dm_f32_finalize_vae": (_i32, [_vp]),
+    "dm_f32_vae_encode": (_i32, [_vp, _vp, _vp] + [_i32] * 4 + [_f32, _vp, _vp, _vp]),
+    "dm_f32_load_clip_weight": (_i32, _WEIGHT),
+    "dm_f32_finalize_clip": (_i32, [_vp]),
+    "dm_f32_clip_encode": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp]),
+    "dm_f32_load_clip_vision_weight": (_i32, _WEIGHT),
+    "dm_f32_finalize_clip_vision": (_i32, [_vp]),
+    "dm_f32_clip_preprocess": (_i32, [_vp] * 4 + [_i32, _vp, _vp]),
+    "dm_f32_clip_image_features": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp]),
+    "dm_f32_clip_vision_hidden": (_i32, [_vp, _vp, _i32, _vp, _vp]),
+    "dm_f32_clip_patch_features": (_i32, [_vp] * 4 + [_i32, _i32, _vp, _vp]),
+    "dm_f32_prof_enable": (_i32, [_vp, _i32]),
+    "dm_f32_prof_read": (_i32, _PROF),
+    "dm_f32_memory": (_i32, [_vp, _psz, _psz]),
+    "dm_f32_op_gemm": (_i32, [_vp] * 8 + [_i32] * 10),
+    "dm_f32_op_attention": (_i32, [_vp] * 5 + [_i32] * 4 + [_i64] * 4 + [_vp] + [_i32] * 6 + [_f32]),
+    "dm_f32_op_groupnorm": (_i32, [_vp, _vp, _vp] + [_i32] * 5 + [_f32, _vp, _vp, _i32, _vp, _vp]),
+    "dm_f32_op_layernorm": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _f32, _vp]),
+}
+SYMBOLS = list(SIGNATURES)
 
 # dm_mine_desc of include/dm_engine.h (48 bytes) and the compile-time cap of k_per_image
 MINE_DESC_DTYPE = np.dtype([("grid_offset", "<i8"), ("work_offset", "<i8"), ("map_offset", "<i8"), ("n_draws", "<i4"), ("n_cond", "<i4"),
@@ -78,115 +157,18 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     # same HIP runtime (two runtimes in one process cannot see each other's device context).
     import torch  # noqa: F401
     lib = C.CDLL(p)
-    vp, i32, i64 = C.c_void_p, C.c_int, C.c_int64
-    lib.dm_version.restype = C.c_char_p
-    lib.dm_last_error.restype = C.c_char_p
-    lib.dm_last_error.argtypes = [vp]
-    lib.dm_scheduler_alphas_cumprod.argtypes = [i32, C.c_float, C.c_float, C.POINTER(C.c_float)]
-    lib.dm_timestep_sinusoid.argtypes = [i32, i32, C.POINTER(C.c_float)]
-    lib.dm_engine_create.argtypes = [i32, C.POINTER(vp)]
-    lib.dm_engine_destroy.argtypes = [vp]
-    lib.dm_engine_destroy.restype = None
-    lib.dm_engine_load_weight.argtypes = [vp, C.c_char_p, vp, i32, C.POINTER(i64), i32]
-    lib.dm_engine_finalize.argtypes = [vp]
-    lib.dm_engine_set_prompts.argtypes = [vp, vp, i32, vp]
-    lib.dm_score.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]
-    lib.dm_score_conds.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]
-    lib.dm_score_conds_slots.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]
-    lib.dm_reduce_typicality_batched.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]
-    lib.dm_unet_forward.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp]
-    lib.dm_dift.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, i32, vp]
-    lib.dm_dift_shape.argtypes = [i32, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
-    lib.dm_reduce_typicality.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
-    lib.dm_typicality_image.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]
-    if hasattr(lib, "dm_mine_patches"):          # (absent only from older A/B libraries loaded through DM_ENGINE_LIB)
-        lib.dm_typicality_image_batched.argtypes = [vp, vp, i32, vp, i32, i32, i32, vp, vp, vp]
-        lib.dm_mine_patches.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]
-    if hasattr(lib, "dm_mine_parallel"):
-        lib.dm_mine_parallel.argtypes = [vp, vp, vp, i32, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
-    lib.dm_prof_enable.argtypes = [vp, i32]
-    lib.dm_measure_mfma_rate.argtypes = [vp, i32, i32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
-    if hasattr(lib, "dm_prof_read_folded"):
-        lib.dm_prof_read_folded.argtypes = [vp, C.POINTER(C.c_double)]
-    lib.dm_prof_read.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i64),
-                                 C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i64)]
-    lib.dm_engine_memory.argtypes = [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
-    lib.dm_op_igemm.argtypes = [vp] * 8 + [i32] * 11
-    lib.dm_op_attention.argtypes = [vp] * 5 + [i32] * 4 + [i64] * 4 + [vp] + [i32] * 5 + [C.c_float]
-    lib.dm_op_attention_slots.argtypes = [vp] * 5 + [i32] * 4 + [i64] * 4 + [vp] + [i32] * 8 + [C.c_float]
-    lib.dm_op_groupnorm.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, C.c_float, vp, vp, i32, vp]
-    if hasattr(lib, "dm_op_conv_out"):
-        lib.dm_op_conv_out.argtypes = [vp] * 5 + [i32] * 4 + [vp, vp]
-    if hasattr(lib, "dm_op_gn_blocks"):          # (absent only from older A/B libraries loaded through DM_ENGINE_LIB)
-        lib.dm_op_conv_temb_gn_blocks.argtypes = [vp] * 6 + [i32] * 6 + [vp, C.POINTER(C.c_int)]
-        lib.dm_op_gn_blocks.argtypes = [vp, vp, i32, i32, i32, vp]
-        lib.dm_op_groupnorm_blocks.argtypes = [vp, vp, vp, i32, i32, i32, i32, C.c_float, vp, vp, i32, vp]
-    lib.dm_op_layernorm.argtypes = [vp, vp, i32, i32, vp, vp, C.c_float, vp]
-    lib.dm_engine_load_vae_weight.argtypes = [vp, C.c_char_p, vp, i32, C.POINTER(i64), i32]
-    lib.dm_engine_finalize_vae.argtypes = [vp]
-    lib.dm_vae_encode.argtypes = [vp, vp, vp, i32, i32, i32, i32, C.c_float, vp, vp, vp, vp]
-    lib.dm_resize_lanczos.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]
-    lib.dm_patch_embed.argtypes = [vp, vp, i32, i32, i32, vp, i32, vp, vp]
-    lib.dm_op_ln_stats.argtypes = [vp, vp, i32, i32, C.c_float, vp]
-    lib.dm_op_igemm_ln.argtypes = [vp] * 7 + [i32] * 4
-    lib.dm_op_igemm_splitk.argtypes = [vp] * 8 + [i32] * 11 + [vp]
-    lib.dm_engine_load_clip_weight.argtypes = [vp, C.c_char_p, vp, i32, C.POINTER(i64), i32]
-    lib.dm_engine_finalize_clip.argtypes = [vp]
-    lib.dm_clip_encode.argtypes = [vp, vp, i32, i32, vp, vp, vp]
-    lib.dm_op_igemm_tile.argtypes = [i32, i32, i32, i32]
-    lib.dm_op_attention_route.argtypes = [i32] * 6
-    lib.dm_set_option.argtypes = [C.c_char_p, i32]
-    if hasattr(lib, "dm_get_option"):
-        lib.dm_get_option.argtypes = [C.c_char_p, C.POINTER(i32)]
-    lib.dm_op_attention512.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, C.c_float]
-    if hasattr(lib, "dm_op_igemm_shortcut"):
-        lib.dm_op_igemm_shortcut.argtypes = [vp] * 8 + [i32] * 8
-    if hasattr(lib, "dm_op_upconv_folded"):
-        lib.dm_op_fold_upconv_weights.argtypes = [vp, i32, i32, vp]
-        lib.dm_op_upconv_folded.argtypes = [vp] * 5 + [i32] * 5
-    if hasattr(lib, "dm_op_groupnorm_conv1x1"):
-        lib.dm_op_groupnorm_conv1x1.argtypes = [vp, vp, i32, i32, i32, i32, C.c_float, vp, vp, vp, vp, i32, vp]
-    if hasattr(lib, "dm_engine_reserve"):        # absent only from older A/B libraries loaded through DM_ENGINE_LIB
-        lib.dm_engine_reserve.argtypes = [vp, i32, i32, i32, i32, i32, vp]
-        lib.dm_engine_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
-    if hasattr(lib, "dm_normalize_map"):
-        lib.dm_normalize_map.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp]
-    if hasattr(lib, "dm_f32_create"):            # the fp32 U-Net (DIFT arithmetic), r04
-        lib.dm_f32_create.argtypes = [i32, C.POINTER(vp)]
-        lib.dm_f32_destroy.argtypes = [vp]
-        lib.dm_f32_destroy.restype = None
-        lib.dm_f32_last_error.restype = C.c_char_p
-        lib.dm_f32_last_error.argtypes = [vp]
-        lib.dm_f32_load_weight.argtypes = [vp, C.c_char_p, vp, i32, C.POINTER(i64), i32]
-        lib.dm_f32_finalize.argtypes = [vp]
-        lib.dm_f32_set_prompts.argtypes = [vp, vp, i32, vp]
-        lib.dm_f32_unet_forward.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp]
-        lib.dm_f32_dift.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, i32, vp]
-        lib.dm_f32_prof_enable.argtypes = [vp, i32]
-        lib.dm_f32_prof_read.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i64),
-                                         C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i64)]
-        lib.dm_f32_memory.argtypes = [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
-        lib.dm_f32_op_gemm.argtypes = [vp] * 8 + [i32] * 10
-        lib.dm_f32_op_attention.argtypes = [vp] * 5 + [i32] * 4 + [i64] * 4 + [vp] + [i32] * 6 + [C.c_float]
-        lib.dm_f32_op_groupnorm.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, C.c_float, vp, vp, i32, vp, vp]
-        lib.dm_f32_op_layernorm.argtypes = [vp, vp, i32, i32, vp, vp, C.c_float, vp]
-        lib.dm_f32_load_vae_weight.argtypes = [vp, C.c_char_p, vp, i32, C.POINTER(i64), i32]
-        lib.dm_f32_finalize_vae.argtypes = [vp]
-        lib.dm_f32_vae_encode.argtypes = [vp, vp, vp, i32, i32, i32, i32, C.c_float, vp, vp, vp]
-        lib.dm_f32_load_clip_weight.argtypes = [vp, C.c_char_p, vp, i32, C.POINTER(i64), i32]
-        lib.dm_f32_finalize_clip.argtypes = [vp]
-        lib.dm_f32_clip_encode.argtypes = [vp, vp, i32, i32, vp, vp]
-        lib.dm_f32_score.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
-    if hasattr(lib, "dm_f32_clip_image_features"):
-        lib.dm_f32_load_clip_vision_weight.argtypes = [vp, C.c_char_p, vp, i32, C.POINTER(i64), i32]
-        lib.dm_f32_finalize_clip_vision.argtypes = [vp]
-        lib.dm_f32_clip_preprocess.argtypes = [vp, vp, vp, vp, i32, vp, vp]
-        lib.dm_f32_clip_image_features.argtypes = [vp, vp, i32, i32, vp, vp]
-        lib.dm_f32_clip_vision_hidden.argtypes = [vp, vp, i32, vp, vp]
-        lib.dm_f32_clip_patch_features.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp]
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(lib, name, None)          # a symbol is absent only from older A/B libraries loaded through DM_ENGINE_LIB
+        if fn is not None:
+            fn.restype, fn.argtypes = restype, argtypes
     if path is None:
         _lib = lib
     return lib
+
+
+def _p(t):
+    """A tensor's address as a pointer argument; None stays NULL."""
+    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 def scheduler_alphas_cumprod(n: int = 1000, beta_start: float = 0.00085, beta_end: float = 0.012) -> np.ndarray:
@@ -214,8 +196,50 @@ def dift_shape(h: int, w: int, up_ft_index: int = 1) -> Tuple[int, int, int]:
     return c.value, oh.value, ow.value
 
 
-class UNetEngine:
-    """One engine per GPU (the reference is one process per GPU, compute.py:215)."""
+# -- the dm_mine_desc table of the batched mining calls ---------------------------------------------------------------------------
+def _mine_desc(shapes, kx: int, ky: int):
+    """dm_mine_desc rows (map_offset, H, W) for pooled maps [OH, OW] of window kx x ky packed back to back -> (table, floats in all)."""
+    desc = np.zeros(len(shapes), dtype=MINE_DESC_DTYPE)
+    sizes = [int(s[0]) * int(s[1]) for s in shapes]
+    desc["H"], desc["W"] = [s[0] + kx - 1 for s in shapes], [s[1] + ky - 1 for s in shapes]
+    desc["map_offset"] = np.cumsum([0] + sizes[:-1])
+    return desc, sum(sizes)
+
+
+def _check_mine_args(what: str, k_per_image, priority, n: int, of: str) -> int:
+    if priority is not None and len(priority) != n:
+        raise ValueError(f"{n} {of} but {len(priority)} priority maps")
+    k_per_image = int(k_per_image)
+    if k_per_image < 1 or k_per_image > MINE_MAX_K:
+        raise EngineError(f"{what}: k_per_image {k_per_image} outside [1, {MINE_MAX_K}]")
+    return k_per_image
+
+
+def _pack_priority(torch, device, priority, shapes, whose: str):
+    """The optional sort-key maps, one per entry of `shapes` and shaped like it, as one fp32 buffer on `device` (None stays None)."""
+    if priority is None:
+        return None
+    for b, (t, s) in enumerate(zip(priority, shapes)):
+        if tuple(t.shape) != tuple(s):
+            raise ValueError(f"priority map {b} is {tuple(t.shape)}, the {whose} {tuple(s)}")
+    return torch.cat([torch.as_tensor(t).to(device, torch.float32).reshape(-1) for t in priority])
+
+
+def _views(buffer, desc, kx: int, ky: int):
+    """The maps [H-kx+1, W-ky+1] of a descriptor table as views of the packed buffer they lie in."""
+    out = []
+    for d in desc:
+        at, oh, ow = int(d["map_offset"]), int(d["H"]) - kx + 1, int(d["W"]) - ky + 1
+        out.append(buffer[at:at + oh * ow].view(oh, ow))
+    return out
+
+
+class _EngineBase:
+    """What the fp16 and the fp32 engine share: the handle, the weight loader, the prompt slots, and the calls that differ only in
+    the C prefix and the tensor type.  A subclass names those; one engine per GPU (the reference is one process per GPU,
+    compute.py:215).  No fallback: raises without the library or a GPU."""
+    _OBJ = _RUN = None      # C prefixes: _OBJ of create / destroy / load_*_weight / finalize_* / set_prompts / memory, _RUN of every other call
+    _DTYPE = None           # torch's name of the element type of the tensors at the boundary
 
     def __init__(self, device: int = 0):
         import torch
@@ -223,11 +247,14 @@ class UNetEngine:
         self.lib = load_library()
         if not torch.cuda.is_available():
             raise EngineError("no GPU visible: the MI355X typicality engine has no CPU fallback")
+        self.dtype = getattr(torch, self._DTYPE)
+        # resolved once: `unet` and `dift` run once per U-Net batch
+        self._unet_fn, self._dift_fn = getattr(self.lib, self._RUN + "unet_forward"), getattr(self.lib, self._RUN + "dift")
         self.device_index = int(device)
         self.device = torch.device("cuda", self.device_index)
         h = C.c_void_p()
-        if self.lib.dm_engine_create(self.device_index, C.byref(h)):
-            raise EngineError("dm_engine_create: " + self.lib.dm_last_error(None).decode())
+        if getattr(self.lib, self._OBJ + "create")(self.device_index, C.byref(h)):
+            raise EngineError(f"{self._OBJ}create: " + getattr(self.lib, self._RUN + "last_error")(None).decode())
         self._h = h
         self.n_prompts = 0
         self.prompt_generation = 0          # bumped by every set_prompts: callers that cache slots compare it
@@ -236,7 +263,11 @@ class UNetEngine:
     # -- plumbing --------------------------------------------------------------------------------
     def _check(self, rc: int, what: str):
         if rc:
-            raise EngineError(f"{what}: {self.lib.dm_last_error(self._h).decode()}")
+            raise EngineError(f"{what}: {getattr(self.lib, self._RUN + 'last_error')(self._h).decode()}")
+
+    def _call(self, prefix: str, name: str, *args):
+        """A call on the handle that is not in the hot path: <prefix><name>(handle, *args), checked."""
+        self._check(getattr(self.lib, prefix + name)(self._h, *args), self._RUN[3:] + name)
 
     def _stream(self):
         return C.c_void_p(self._torch.cuda.current_stream(self.device).cuda_stream)
@@ -263,7 +294,7 @@ class UNetEngine:
 
     def close(self):
         if getattr(self, "_h", None):
-            self.lib.dm_engine_destroy(self._h)
+            getattr(self.lib, self._OBJ + "destroy")(self._h)
             self._h = None
 
     def __del__(self):
@@ -273,8 +304,11 @@ class UNetEngine:
             pass
 
     # -- weights ---------------------------------------------------------------------------------
-    def _load(self, fn, sd, what):
+    def _load(self, what: str, sd):
+        """Every tensor of a state dict (numpy or torch; fp16 and fp32 as they are, anything else widened to fp32) to
+        <_OBJ>load<what>_weight, then <_OBJ>finalize<what>; what = "" (the U-Net), "_vae", "_clip", "_clip_vision"."""
         torch = self._torch
+        fn = getattr(self.lib, f"{self._OBJ}load{what}_weight")
         for name, t in sd.items():
             if hasattr(t, "detach"):
                 t = t.detach().to("cpu")
@@ -288,26 +322,124 @@ class UNetEngine:
                 a = a.astype(np.float32)
                 dt = 1
             shape = (C.c_int64 * a.ndim)(*a.shape)
-            self._check(fn(self._h, name.encode(), a.ctypes.data_as(C.c_void_p), dt, shape, a.ndim), f"{what}({name})")
+            self._check(fn(self._h, name.encode(), a.ctypes.data_as(C.c_void_p), dt, shape, a.ndim),
+                        f"{self._RUN[3:]}load{what}_weight({name})")
+        self._call(self._OBJ, f"finalize{what}")
 
     def load_state_dict(self, sd: Dict[str, "np.ndarray"]):
-        """sd: diffusers-named U-Net state dict (numpy or torch tensors, fp16/fp32/bf16)."""
-        self._load(self.lib.dm_engine_load_weight, sd, "load_weight")
-        self._check(self.lib.dm_engine_finalize(self._h), "finalize")
+        """sd: diffusers-named U-Net state dict (numpy or torch tensors, fp16/fp32/bf16; the fp32 engine keeps fp32 as it is and
+        widens fp16 / bf16 exactly)."""
+        self._load("", sd)
         self._finalized = True
 
     def load_vae_state_dict(self, sd: Dict[str, "np.ndarray"]):
         """sd: `AutoencoderKL.state_dict()` (`pipe.vae`, compute.py:73); only `encoder.*` and
         `quant_conv.*` are used, the decoder half is ignored.  Optional: scoring needs only the U-Net."""
-        self._load(self.lib.dm_engine_load_vae_weight, sd, "load_vae_weight")
-        self._check(self.lib.dm_engine_finalize_vae(self._h), "finalize_vae")
+        self._load("_vae", sd)
         self._vae_ready = True
 
     def load_clip_state_dict(self, sd: Dict[str, "np.ndarray"]):
-        """sd: `CLIPTextModel.state_dict()` (`pipe.text_encoder`, compute.py:68).  Optional."""
-        self._load(self.lib.dm_engine_load_clip_weight, sd, "load_clip_weight")
-        self._check(self.lib.dm_engine_finalize_clip(self._h), "finalize_clip")
+        """sd: `CLIPTextModel.state_dict()` (`pipe.text_encoder`, compute.py:68; the featuriser's pipeline keeps it in fp32,
+        dift.py:197-199).  Optional."""
+        self._load("_clip", sd)
         self._clip_ready = True
+
+    # -- prompts ---------------------------------------------------------------------------------
+    def set_prompts(self, ctx):
+        """ctx [P,77,768] (`prompt_embeds`, dift.py:222-227): distinct prompt embeddings, kept in the engine's element type;
+        precomputes cross-attention K/V for them."""
+        ctx = ctx.to(self.device, self.dtype).contiguous()
+        assert ctx.dim() == 3 and ctx.shape[1] == 77 and ctx.shape[2] == 768, ctx.shape
+        self._call(self._OBJ, "set_prompts", _p(ctx), ctx.shape[0], self._stream())
+        self._ctx_keepalive = ctx
+        self.n_prompts = ctx.shape[0]
+        self.prompt_generation += 1
+
+    def _slots(self, slots, batch):
+        """Prompt slots of a batch -> int32 on the device.  Host-side inputs (lists, CPU tensors) are range-checked against
+        the registered prompts here (a slot beyond them would read another prompt set's stale K/V rows); a tensor that
+        already lives on the device is not pulled back for the check — that would be two blocking syncs in the hot path
+        (`TypicalityScorer.compute_loss` passes `torch.unique`'s inverse, in range by construction) — the kernels clamp
+        device-side slots to the registered range instead (memory-safe, never another engine's rows)."""
+        torch = self._torch
+        s = torch.as_tensor(slots)
+        assert s.shape == (batch,), (s.shape, batch)
+        if s.numel() and (not s.is_cuda or _CHECK_DEVICE_SLOTS):      # DM_CHECK_SLOTS=1: also range-check device tensors (two syncs)
+            lo, hi = int(s.min()), int(s.max())
+            if lo < 0 or hi >= self.n_prompts:
+                raise EngineError(f"prompt slot {lo if lo < 0 else hi} outside the {self.n_prompts} prompts registered "
+                                  "by set_prompts")
+        return s.to(self.device, torch.int32).contiguous()
+
+    def _timesteps(self, t, batch):
+        """t (a number, a list or a tensor; one value is broadcast) -> int64 [batch] on the device."""
+        torch = self._torch
+        t = torch.as_tensor(t, device=self.device).to(torch.int64).reshape(-1)
+        if t.numel() == 1:
+            t = t.expand(batch)
+        assert t.shape == (batch,), (t.shape, batch)
+        return t.contiguous()
+
+    def _x_index(self, x_index, n_x, batch):
+        """The row of x each sample reads -> int32 [batch] on the device, or None for the identity; one x serves every sample."""
+        torch = self._torch
+        if x_index is not None:
+            xi = torch.as_tensor(x_index, device=self.device).to(torch.int32).contiguous()
+            assert xi.shape == (batch,)
+            return xi
+        if n_x == batch:
+            return None
+        assert n_x == 1, "x must have 1 or B rows when x_index is not given"
+        return torch.zeros(batch, dtype=torch.int32, device=self.device)
+
+    # -- the U-Net -------------------------------------------------------------------------------
+    def unet(self, sample, t, slots):
+        """`unet(sample, t, ctx).sample` (compute.py:100) -> [B,4,h,w] in the engine's element type."""
+        torch = self._torch
+        sample = sample.to(self.device, self.dtype).contiguous()
+        B, _, h, w = sample.shape
+        t = self._timesteps(t, B)
+        s = self._slots(slots, B)
+        out = torch.empty(B, 4, h, w, dtype=self.dtype, device=self.device)
+        self._check(self._unet_fn(self._h, _p(sample), _p(t), _p(s), B, h, w, _p(out), self._stream()), self._unet_fn.__name__)
+        return out
+
+    def dift(self, noisy, t, slots, up_ft_index: int = 1, ensemble: Optional[int] = None):
+        """MyUNet2DConditionModel.forward tap (dift.py:24-169).  Returns (features [B,C,h',w'] in the engine's element type,
+        ensemble mean fp32 [B/ens,C,h',w'] or None)."""
+        torch = self._torch
+        noisy = noisy.to(self.device, self.dtype).contiguous()
+        B, _, h, w = noisy.shape
+        t = self._timesteps(t, B)
+        s = self._slots(slots, B)
+        c, oh, ow = dift_shape(h, w, up_ft_index)
+        feat = torch.empty(B, c, oh, ow, dtype=self.dtype, device=self.device)
+        mean = torch.empty(B // ensemble, c, oh, ow, dtype=torch.float32, device=self.device) if ensemble else None
+        self._check(self._dift_fn(self._h, _p(noisy), _p(t), _p(s), B, h, w, up_ft_index, _p(feat), _p(mean), int(ensemble or 1),
+                                  self._stream()), self._dift_fn.__name__)
+        return feat, mean
+
+    # -- measurement -----------------------------------------------------------------------------
+    def prof_enable(self, on: bool = True):
+        self._call(self._RUN, "prof_enable", 1 if on else 0)
+
+    def prof_read(self) -> dict:
+        a, b, c2 = C.c_double(), C.c_double(), C.c_int64()
+        d, e, f = C.c_double(), C.c_double(), C.c_int64()
+        self._call(self._RUN, "prof_read", C.byref(a), C.byref(b), C.byref(c2), C.byref(d), C.byref(e), C.byref(f))
+        return {"igemm_ms": a.value, "igemm_flops": b.value, "igemm_launches": c2.value,
+                "attn_ms": d.value, "attn_flops": e.value, "attn_launches": f.value}
+
+    def memory(self) -> dict:
+        a, b = C.c_size_t(), C.c_size_t()
+        self._call(self._OBJ, "memory", C.byref(a), C.byref(b))
+        return {"weights_bytes": a.value, "arena_bytes": b.value}
+
+
+class UNetEngine(_EngineBase):
+    """The fp16 engine of the typicality path (C ABI: dm_engine_* / dm_*): fp16 weights and activations, fp32 accumulation — the
+    arithmetic of the reference's autocast run (compute.py:98)."""
+    _OBJ, _RUN, _DTYPE = "dm_engine_", "dm_", "float16"
 
     def clip_encode(self, input_ids, out_dtype=None):
         """`self.clip(tokens)[0]` (compute.py:51): input_ids [n, 77] (tokenizer output, padding="max_length")
@@ -317,10 +449,10 @@ class UNetEngine:
         ids = torch.as_tensor(input_ids).to(self.device, torch.int32).contiguous()
         assert ids.dim() == 2 and ids.shape[1] == 77, ids.shape
         out = torch.empty(ids.shape[0], 77, 768, dtype=out_dtype, device=self.device)
-        p16 = C.c_void_p(out.data_ptr()) if out_dtype == torch.float16 else None
-        p32 = C.c_void_p(out.data_ptr()) if out_dtype == torch.float32 else None
+        p16 = _p(out) if out_dtype == torch.float16 else None
+        p32 = _p(out) if out_dtype == torch.float32 else None
         assert p16 or p32
-        self._check(self.lib.dm_clip_encode(self._h, C.c_void_p(ids.data_ptr()), ids.shape[0], 77, p16, p32, self._stream()),
+        self._check(self.lib.dm_clip_encode(self._h, _p(ids), ids.shape[0], 77, p16, p32, self._stream()),
                     "dm_clip_encode")
         return out
 
@@ -346,13 +478,13 @@ class UNetEngine:
             assert noise.shape == (B * draws_per_image, 4, h, w), noise.shape
         lat = torch.empty(B * draws_per_image, 4, h, w, dtype=out_dtype, device=self.device)
         mom = torch.empty(B, 8, h, w, dtype=torch.float32, device=self.device) if return_moments else None
-        p16 = C.c_void_p(lat.data_ptr()) if out_dtype == torch.float16 else None
-        p32 = C.c_void_p(lat.data_ptr()) if out_dtype == torch.float32 else None
+        p16 = _p(lat) if out_dtype == torch.float16 else None
+        p32 = _p(lat) if out_dtype == torch.float32 else None
         assert p16 or p32, "out_dtype must be torch.float16 or torch.float32"
-        self._check(self.lib.dm_vae_encode(self._h, C.c_void_p(image.data_ptr()),
-                                           C.c_void_p(noise.data_ptr()) if noise is not None else None, B,
+        self._check(self.lib.dm_vae_encode(self._h, _p(image),
+                                           _p(noise), B,
                                            int(draws_per_image), H, W, float(scaling_factor), p16, p32,
-                                           C.c_void_p(mom.data_ptr()) if mom is not None else None, self._stream()),
+                                           _p(mom), self._stream()),
                     "dm_vae_encode")
         return (lat, mom) if return_moments else lat
 
@@ -377,9 +509,9 @@ class UNetEngine:
         if resample:
             tab_d = torch.from_numpy(tables).to(self.device)
             tmp = torch.empty(n * 3 * tmp_rows * out_w, dtype=torch.uint8, device=self.device)
-        rc = self.lib.dm_resize_lanczos(C.c_void_p(src.data_ptr()), C.c_void_p(desc_d.data_ptr()),
-                                        C.c_void_p(tab_d.data_ptr()) if resample else None, n, out_w, out_h, tmp_rows if resample else 0,
-                                        C.c_void_p(tmp.data_ptr()) if resample else None, C.c_void_p(out.data_ptr()), self._stream())
+        rc = self.lib.dm_resize_lanczos(_p(src), _p(desc_d),
+                                        _p(tab_d), n, out_w, out_h, tmp_rows if resample else 0,
+                                        _p(tmp), _p(out), self._stream())
         if rc:
             raise EngineError(f"dm_resize_lanczos: {'bad argument' if rc == 1 else 'HIP launch failed'} (rc {rc})")
         return out
@@ -414,34 +546,6 @@ class UNetEngine:
             from safetensors.numpy import load_file
             self.load_clip_state_dict(load_file(c))
 
-    # -- prompts ---------------------------------------------------------------------------------
-    def set_prompts(self, ctx):
-        """ctx [P,77,768]: distinct prompt embeddings; precomputes cross-attention K/V for them."""
-        torch = self._torch
-        ctx = ctx.to(self.device, torch.float16).contiguous()
-        assert ctx.dim() == 3 and ctx.shape[1] == 77 and ctx.shape[2] == 768, ctx.shape
-        self._check(self.lib.dm_engine_set_prompts(self._h, C.c_void_p(ctx.data_ptr()), ctx.shape[0], self._stream()),
-                    "set_prompts")
-        self._ctx_keepalive = ctx
-        self.n_prompts = ctx.shape[0]
-        self.prompt_generation += 1
-
-    def _slots(self, slots, batch):
-        """Prompt slots of a batch -> int32 on the device.  Host-side inputs (lists, CPU tensors) are range-checked against
-        the registered prompts here (a slot beyond them would read another prompt set's stale K/V rows); a tensor that
-        already lives on the device is not pulled back for the check — that would be two blocking syncs in the hot path
-        (`TypicalityScorer.compute_loss` passes `torch.unique`'s inverse, in range by construction) — the kernels clamp
-        device-side slots to the registered range instead (memory-safe, never another engine's rows)."""
-        torch = self._torch
-        s = torch.as_tensor(slots)
-        assert s.shape == (batch,), (s.shape, batch)
-        if s.numel() and (not s.is_cuda or _CHECK_DEVICE_SLOTS):      # DM_CHECK_SLOTS=1: also range-check device tensors (two syncs)
-            lo, hi = int(s.min()), int(s.max())
-            if lo < 0 or hi >= self.n_prompts:
-                raise EngineError(f"prompt slot {lo if lo < 0 else hi} outside the {self.n_prompts} prompts registered "
-                                  "by set_prompts")
-        return s.to(self.device, torch.int32).contiguous()
-
     def _latents(self, x, eps, latent_dtype):
         """x / eps in the element type the engine's add_noise and MSE run in: fp32 (the reference's flow, also
         the default for anything that is not fp16 already) or fp16 (both must then be fp16-valued)."""
@@ -463,18 +567,10 @@ class UNetEngine:
         t = t.to(self.device, torch.int64).contiguous()
         assert t.shape == (B,)
         s = self._slots(slots, B)
-        xi = None
-        if x_index is not None:
-            xi = torch.as_tensor(x_index, device=self.device).to(torch.int32).contiguous()
-            assert xi.shape == (B,)
-        elif x.shape[0] != B:
-            assert x.shape[0] == 1, "x must have 1 or B rows when x_index is not given"
-            xi = torch.zeros(B, dtype=torch.int32, device=self.device)
+        xi = self._x_index(x_index, x.shape[0], B)
         out = torch.empty(B, 4, h, w, dtype=torch.float32, device=self.device)
-        self._check(self.lib.dm_score(self._h, C.c_void_p(x.data_ptr()),
-                                      C.c_void_p(xi.data_ptr()) if xi is not None else None,
-                                      C.c_void_p(eps.data_ptr()), C.c_void_p(t.data_ptr()), C.c_void_p(s.data_ptr()),
-                                      B, x.shape[0], h, w, ld, C.c_void_p(out.data_ptr()), self._stream()), "dm_score")
+        self._check(self.lib.dm_score(self._h, _p(x), _p(xi), _p(eps), _p(t), _p(s), B, x.shape[0], h, w, ld, _p(out),
+                                      self._stream()), "dm_score")
         return out
 
     def score_conds(self, x, eps, t, n_cond: int, x_index=None, latent_dtype=None, slot_table=None):
@@ -493,59 +589,11 @@ class UNetEngine:
             st = self._slots(torch.as_tensor(slot_table).reshape(-1), n_cond * U)
         else:
             assert n_cond <= self.n_prompts
-        xi = None
-        if x_index is not None:
-            xi = torch.as_tensor(x_index, device=self.device).to(torch.int32).contiguous()
-            assert xi.shape == (U,)
-        elif x.shape[0] != U:
-            assert x.shape[0] == 1
-            xi = torch.zeros(U, dtype=torch.int32, device=self.device)
+        xi = self._x_index(x_index, x.shape[0], U)
         out = torch.empty(n_cond * U, 4, h, w, dtype=torch.float32, device=self.device)
-        self._check(self.lib.dm_score_conds_slots(self._h, C.c_void_p(x.data_ptr()),
-                                                  C.c_void_p(xi.data_ptr()) if xi is not None else None,
-                                                  C.c_void_p(eps.data_ptr()), C.c_void_p(t.data_ptr()),
-                                                  C.c_void_p(st.data_ptr()) if st is not None else None, n_cond, U,
-                                                  x.shape[0], h, w, ld, C.c_void_p(out.data_ptr()), self._stream()),
-                    "dm_score_conds")
+        self._check(self.lib.dm_score_conds_slots(self._h, _p(x), _p(xi), _p(eps), _p(t), _p(st), n_cond, U, x.shape[0], h, w, ld,
+                                                  _p(out), self._stream()), "dm_score_conds")
         return out
-
-    def unet(self, sample, t, slots):
-        """`unet(sample, t, ctx).sample` (compute.py:100) -> [B,4,h,w] fp16."""
-        torch = self._torch
-        sample = sample.to(self.device, torch.float16).contiguous()
-        B, _, h, w = sample.shape
-        t = torch.as_tensor(t, device=self.device).to(torch.int64).reshape(-1)
-        if t.numel() == 1:
-            t = t.expand(B)
-        t = t.contiguous()
-        s = self._slots(slots, B)
-        out = torch.empty(B, 4, h, w, dtype=torch.float16, device=self.device)
-        self._check(self.lib.dm_unet_forward(self._h, C.c_void_p(sample.data_ptr()), C.c_void_p(t.data_ptr()),
-                                             C.c_void_p(s.data_ptr()), B, h, w, C.c_void_p(out.data_ptr()),
-                                             self._stream()), "dm_unet_forward")
-        return out
-
-    def dift(self, noisy, t, slots, up_ft_index: int = 1, ensemble: Optional[int] = None):
-        """MyUNet2DConditionModel.forward tap (dift.py:24-169).  Returns (features fp16 [B,C,h',w'],
-        ensemble mean fp32 [B/ens,C,h',w'] or None)."""
-        torch = self._torch
-        noisy = noisy.to(self.device, torch.float16).contiguous()
-        B, _, h, w = noisy.shape
-        t = torch.as_tensor(t, device=self.device).to(torch.int64).reshape(-1)
-        if t.numel() == 1:
-            t = t.expand(B)
-        t = t.contiguous()
-        s = self._slots(slots, B)
-        c, oh, ow = dift_shape(h, w, up_ft_index)
-        feat = torch.empty(B, c, oh, ow, dtype=torch.float16, device=self.device)
-        mean = None
-        if ensemble:
-            mean = torch.empty(B // ensemble, c, oh, ow, dtype=torch.float32, device=self.device)
-        self._check(self.lib.dm_dift(self._h, C.c_void_p(noisy.data_ptr()), C.c_void_p(t.data_ptr()),
-                                     C.c_void_p(s.data_ptr()), B, h, w, up_ft_index, C.c_void_p(feat.data_ptr()),
-                                     C.c_void_p(mean.data_ptr()) if mean is not None else None,
-                                     int(ensemble or 1), self._stream()), "dm_dift")
-        return feat, mean
 
     def reduce_typicality(self, grid):
         """grid [N,n_cond,4,h,w] (fp32 or fp16, on the GPU) -> (map [h,w] fp32, scalar [1] fp32)."""
@@ -556,9 +604,9 @@ class UNetEngine:
         N, nc, _, h, w = grid.shape
         m = torch.empty(h, w, dtype=torch.float32, device=self.device)
         sc = torch.empty(1, dtype=torch.float32, device=self.device)
-        self._check(self.lib.dm_reduce_typicality(self._h, C.c_void_p(grid.data_ptr()),
+        self._check(self.lib.dm_reduce_typicality(self._h, _p(grid),
                                                   1 if grid.dtype == torch.float16 else 0, N, nc, h, w,
-                                                  C.c_void_p(m.data_ptr()), C.c_void_p(sc.data_ptr()), self._stream()),
+                                                  _p(m), _p(sc), self._stream()),
                     "dm_reduce_typicality")
         return m, sc
 
@@ -573,10 +621,10 @@ class UNetEngine:
         assert loss.shape[-3] == 4 and loss.numel() == n_images * n_draws * n_cond * 4 * h * w, loss.shape
         maps = torch.empty(n_images, h, w, dtype=torch.float32, device=self.device)
         sc = torch.empty(n_images, dtype=torch.float32, device=self.device)
-        self._check(self.lib.dm_reduce_typicality_batched(self._h, C.c_void_p(loss.data_ptr()),
+        self._check(self.lib.dm_reduce_typicality_batched(self._h, _p(loss),
                                                           1 if loss.dtype == torch.float16 else 0, n_images, n_draws,
                                                           n_cond, h, w, 1 if cond_major else 0,
-                                                          C.c_void_p(maps.data_ptr()), C.c_void_p(sc.data_ptr()),
+                                                          _p(maps), _p(sc),
                                                           self._stream()), "dm_reduce_typicality_batched")
         return maps, sc
 
@@ -591,9 +639,9 @@ class UNetEngine:
         H, W = int(image_size[0]), int(image_size[1])
         work = torch.empty(h * w + H * W, dtype=torch.float32, device=self.device)
         out = torch.empty(H - kx + 1, W - ky + 1, dtype=torch.float32, device=self.device)
-        self._check(self.lib.dm_typicality_image(self._h, C.c_void_p(grid.data_ptr()),
+        self._check(self.lib.dm_typicality_image(self._h, _p(grid),
                                                  1 if grid.dtype == torch.float16 else 0, N, nc, h, w, H, W, kx, ky,
-                                                 C.c_void_p(work.data_ptr()), C.c_void_p(out.data_ptr()), self._stream()),
+                                                 _p(work), _p(out), self._stream()),
                     "dm_typicality_image")
         return out
 
@@ -626,12 +674,10 @@ class UNetEngine:
         desc_d = torch.from_numpy(desc.view(np.uint8)).to(self.device)
         work = torch.empty(w_at, dtype=torch.float32, device=self.device)
         maps = torch.empty(m_at, dtype=torch.float32, device=self.device)
-        self._check(self.lib.dm_typicality_image_batched(self._h, C.c_void_p(loss.data_ptr()), 1 if dt == torch.float16 else 0,
-                                                         C.c_void_p(desc_d.data_ptr()), len(grids), int(kx), int(ky),
-                                                         C.c_void_p(work.data_ptr()), C.c_void_p(maps.data_ptr()), self._stream()),
+        self._check(self.lib.dm_typicality_image_batched(self._h, _p(loss), 1 if dt == torch.float16 else 0, _p(desc_d), len(grids),
+                                                         int(kx), int(ky), _p(work), _p(maps), self._stream()),
                     "dm_typicality_image_batched")
-        return [maps[int(d["map_offset"]):int(d["map_offset"]) + (int(d["H"]) - kx + 1) * (int(d["W"]) - ky + 1)]
-                .view(int(d["H"]) - kx + 1, int(d["W"]) - ky + 1) for d in desc]
+        return _views(maps, desc, kx, ky)
 
     def mine_patches(self, maps, kx: int, ky: int, k_per_image: int = 5, ascending: bool = False, priority=None):
         """`sort` + `get_non_overlapping` (utils.py:82-102) on the candidate frame of `Cluster.df_D` (cluster.py:194-201), for a list
@@ -643,37 +689,24 @@ class UNetEngine:
         shapes that supply the sort key instead (D is still read from `maps`) — the ranks of a permutation give the reference's
         shuffled arm."""
         torch = self._torch
-        if len(maps) < 1:
+        n = len(maps)
+        if n < 1:
             raise ValueError("no maps")
-        if priority is not None and len(priority) != len(maps):
-            raise ValueError(f"{len(maps)} maps but {len(priority)} priority maps")
-        k_per_image = int(k_per_image)
-        if k_per_image < 1 or k_per_image > MINE_MAX_K:
-            raise EngineError(f"mine_patches: k_per_image {k_per_image} outside [1, {MINE_MAX_K}]")
+        k_per_image = _check_mine_args("mine_patches", k_per_image, priority, n, "maps")
         maps = [torch.as_tensor(m) for m in maps]
-        desc = np.zeros(len(maps), dtype=MINE_DESC_DTYPE)
-        at = 0
         for b, m in enumerate(maps):
             if m.dim() != 2 or m.numel() < 1:
                 raise ValueError(f"map {b} must be [OH, OW], got {tuple(m.shape)}")
-            if priority is not None and tuple(priority[b].shape) != tuple(m.shape):
-                raise ValueError(f"priority map {b} is {tuple(priority[b].shape)}, the map {tuple(m.shape)}")
-            desc[b]["map_offset"], desc[b]["H"], desc[b]["W"] = at, m.shape[0] + kx - 1, m.shape[1] + ky - 1
-            at += m.numel()
-
-        def pack(ts):
-            return torch.cat([torch.as_tensor(t).to(self.device, torch.float32).reshape(-1) for t in ts])
-        packed = pack(maps)
-        prio = pack(priority) if priority is not None else None
+        shapes = [m.shape for m in maps]
+        desc, _ = _mine_desc(shapes, kx, ky)
+        packed = torch.cat([m.to(self.device, torch.float32).reshape(-1) for m in maps])
+        prio = _pack_priority(torch, self.device, priority, shapes, "map")
         desc_d = torch.from_numpy(desc.view(np.uint8)).to(self.device)
-        n = len(maps)
         boxes = torch.empty(n, k_per_image, 4, dtype=torch.int32, device=self.device)
         dvals = torch.empty(n, k_per_image, dtype=torch.float32, device=self.device)
         count = torch.empty(n, dtype=torch.int32, device=self.device)
-        self._check(self.lib.dm_mine_patches(self._h, C.c_void_p(packed.data_ptr()), C.c_void_p(prio.data_ptr()) if prio is not None else None,
-                                             C.c_void_p(desc_d.data_ptr()), n, int(kx), int(ky), k_per_image, 1 if ascending else 0,
-                                             C.c_void_p(boxes.data_ptr()), C.c_void_p(dvals.data_ptr()), C.c_void_p(count.data_ptr()),
-                                             self._stream()), "dm_mine_patches")
+        self._check(self.lib.dm_mine_patches(self._h, _p(packed), _p(prio), _p(desc_d), n, int(kx), int(ky), k_per_image,
+                                             1 if ascending else 0, _p(boxes), _p(dvals), _p(count), self._stream()), "dm_mine_patches")
         return boxes, dvals, count
 
     @staticmethod
@@ -708,46 +741,32 @@ class UNetEngine:
             raise EngineError(f"mine_parallel: n_sets {n_sets} outside [1, {MINE_MAX_SETS}]")
         if any(len(g) != n_sets for g in maps_by_group):
             raise ValueError(f"every group must hold {n_sets} maps, got {[len(g) for g in maps_by_group]}")
-        if priority is not None and len(priority) != G:
-            raise ValueError(f"{G} groups but {len(priority)} priority maps")
-        k_per_image = int(k_per_image)
-        if k_per_image < 1 or k_per_image > MINE_MAX_K:
-            raise EngineError(f"mine_parallel: k_per_image {k_per_image} outside [1, {MINE_MAX_K}]")
+        k_per_image = _check_mine_args("mine_parallel", k_per_image, priority, G, "groups")
         flat = [torch.as_tensor(m) for g in maps_by_group for m in g]
         for b, m in enumerate(flat):
             if m.dim() != 2 or m.numel() < 1:
                 raise ValueError(f"map {b % n_sets} of group {b // n_sets} must be [OH, OW], got {tuple(m.shape)}")
-        desc = np.zeros(G * n_sets, dtype=MINE_DESC_DTYPE)
-        gdesc = np.zeros(G, dtype=MINE_DESC_DTYPE)
-        at = 0
-        for g in range(G):
-            m0 = flat[g * n_sets]
-            for c in range(n_sets):
-                m = flat[g * n_sets + c]
-                if tuple(m.shape) != tuple(m0.shape):
-                    raise EngineError(f"mine_parallel: set {c} of group {g} is {tuple(m.shape)}, the group {tuple(m0.shape)}")
-                desc[g * n_sets + c]["H"], desc[g * n_sets + c]["W"] = m.shape[0] + kx - 1, m.shape[1] + ky - 1
-            if priority is not None and tuple(priority[g].shape) != tuple(m0.shape):
-                raise ValueError(f"priority map {g} is {tuple(priority[g].shape)}, the group's maps {tuple(m0.shape)}")
-            gdesc[g]["map_offset"], gdesc[g]["H"], gdesc[g]["W"] = at, m0.shape[0] + kx - 1, m0.shape[1] + ky - 1
-            at += m0.numel()
+        shapes = [flat[g * n_sets].shape for g in range(G)]
+        for b, m in enumerate(flat):
+            if m.shape != shapes[b // n_sets]:
+                raise EngineError(f"mine_parallel: set {b % n_sets} of group {b // n_sets} is {tuple(m.shape)}, "
+                                  f"the group {tuple(shapes[b // n_sets])}")
+        desc, _ = _mine_desc([m.shape for m in flat], kx, ky)
+        gdesc, n_med = _mine_desc(shapes, kx, ky)
         packed, offsets, _ = self._place_maps(torch, flat, self.device)
         desc["map_offset"] = offsets
-        prio = torch.cat([torch.as_tensor(t).to(self.device, torch.float32).reshape(-1) for t in priority]) if priority is not None else None
+        prio = _pack_priority(torch, self.device, priority, shapes, "group's maps")
         up = torch.from_numpy(np.concatenate([desc, gdesc]).view(np.uint8)).to(self.device)          # both tables in one upload
         desc_d, gdesc_d = up[:desc.nbytes], up[desc.nbytes:]
-        med = torch.empty(at, dtype=torch.float32, device=self.device)
+        med = torch.empty(n_med, dtype=torch.float32, device=self.device)
         boxes = torch.empty(G, k_per_image, 4, dtype=torch.int32, device=self.device)
         dvals = torch.empty(G, k_per_image, dtype=torch.float32, device=self.device)
         set_d = torch.empty(G, k_per_image, n_sets, dtype=torch.float32, device=self.device)
         count = torch.empty(G, dtype=torch.int32, device=self.device)
-        p = lambda t: C.c_void_p(t.data_ptr())          # noqa: E731
-        self._check(self.lib.dm_mine_parallel(self._h, p(packed), p(desc_d), G, n_sets, p(gdesc_d), int(kx), int(ky), k_per_image,
-                                              1 if ascending else 0, p(prio) if prio is not None else None, p(med), p(boxes), p(dvals),
-                                              p(set_d), p(count), self._stream()), "dm_mine_parallel")
-        medians = [med[int(d["map_offset"]):int(d["map_offset"]) + (int(d["H"]) - kx + 1) * (int(d["W"]) - ky + 1)]
-                   .view(int(d["H"]) - kx + 1, int(d["W"]) - ky + 1) for d in gdesc]
-        return boxes, dvals, set_d, count, medians
+        self._check(self.lib.dm_mine_parallel(self._h, _p(packed), _p(desc_d), G, n_sets, _p(gdesc_d), int(kx), int(ky), k_per_image,
+                                              1 if ascending else 0, _p(prio), _p(med), _p(boxes), _p(dvals), _p(set_d), _p(count),
+                                              self._stream()), "dm_mine_parallel")
+        return boxes, dvals, set_d, count, _views(med, gdesc, kx, ky)
 
     NORM_MODES = {"signed": 1, "maxabs": 2, "positive": 3, "split": 4}
 
@@ -761,9 +780,9 @@ class UNetEngine:
         out = torch.empty_like(dm)
         neg = torch.empty_like(dm) if mode == "split" else None
         work = torch.empty(2, dtype=torch.float32, device=self.device)
-        self._check(self.lib.dm_normalize_map(self._h, C.c_void_p(dm.data_ptr()), dm.numel(), self.NORM_MODES[mode],
-                                              C.c_void_p(work.data_ptr()), C.c_void_p(out.data_ptr()),
-                                              C.c_void_p(neg.data_ptr()) if neg is not None else None, self._stream()),
+        self._check(self.lib.dm_normalize_map(self._h, _p(dm), dm.numel(), self.NORM_MODES[mode],
+                                              _p(work), _p(out),
+                                              _p(neg), self._stream()),
                     "dm_normalize_map")
         return (out, neg) if mode == "split" else out
 
@@ -779,14 +798,11 @@ class UNetEngine:
         b = torch.as_tensor(boxes, device=self.device).to(torch.int32).contiguous()
         assert b.dim() == 2 and b.shape[1] == 4, b.shape
         out = torch.empty(b.shape[0], Cc, dtype=torch.float32, device=self.device)
-        self._check(self.lib.dm_patch_embed(self._h, C.c_void_p(feat.data_ptr()), Cc, h, w, C.c_void_p(b.data_ptr()),
-                                            b.shape[0], C.c_void_p(out.data_ptr()), self._stream()), "dm_patch_embed")
+        self._check(self.lib.dm_patch_embed(self._h, _p(feat), Cc, h, w, _p(b),
+                                            b.shape[0], _p(out), self._stream()), "dm_patch_embed")
         return out
 
     # -- measurement -----------------------------------------------------------------------------
-    def prof_enable(self, on: bool = True):
-        self._check(self.lib.dm_prof_enable(self._h, 1 if on else 0), "prof_enable")
-
     def measure_mfma_rate(self, steps: int = 20000, zero_operands: bool = False) -> dict:
         """Measurement only: TFLOP/s and shader clock the matrix cores sustain on the igemm tile's MFMA stream alone (dm_measure_mfma_rate;
         ~10 us per 100 steps).  bench.py quotes the kernel family against it beside the nominal peak."""
@@ -795,15 +811,11 @@ class UNetEngine:
         return {"tflops": tf.value, "sclk_ghz": ghz.value}
 
     def prof_read(self) -> dict:
-        a, b, c2 = C.c_double(), C.c_double(), C.c_int64()
-        d, e, f = C.c_double(), C.c_double(), C.c_int64()
-        self._check(self.lib.dm_prof_read(self._h, C.byref(a), C.byref(b), C.byref(c2), C.byref(d), C.byref(e),
-                                          C.byref(f)), "prof_read")
-        out = {"igemm_ms": a.value, "igemm_flops": b.value, "igemm_launches": c2.value,
-               "attn_ms": d.value, "attn_flops": e.value, "attn_launches": f.value, "igemm_flops_folded": 0.0}
+        out = super().prof_read()
+        out["igemm_flops_folded"] = 0.0
         if hasattr(self.lib, "dm_prof_read_folded"):       # (absent only from older A/B libraries loaded through DM_ENGINE_LIB)
             g = C.c_double()
-            self._check(self.lib.dm_prof_read_folded(self._h, C.byref(g)), "prof_read_folded")
+            self._call("dm_", "prof_read_folded", C.byref(g))
             out["igemm_flops_folded"] = g.value
         return out
 
@@ -819,91 +831,16 @@ class UNetEngine:
         self._check(self.lib.dm_engine_stats(self._h, C.byref(a), C.byref(b), C.byref(g)), "dm_engine_stats")
         return {"device_allocs": a.value, "schedule_dry_runs": b.value, "graph_launches": g.value}
 
-    def memory(self) -> dict:
-        a, b = C.c_size_t(), C.c_size_t()
-        self._check(self.lib.dm_engine_memory(self._h, C.byref(a), C.byref(b)), "memory")
-        return {"weights_bytes": a.value, "arena_bytes": b.value}
 
-
-class UNetEngineF32:
+class UNetEngineF32(_EngineBase):
     """The SDv1.5 U-Net in plain fp32 on the fp32 matrix cores (C ABI: dm_f32_*) — the arithmetic of the reference's DIFT
     featuriser, which loads its pipeline without torch_dtype and runs without autocast (dift.py:191,197-199).  Same
-    diffusers-named state dict and prompt-slot mechanism as `UNetEngine`; every tensor at this boundary is fp32.
-    No fallback: raises without the library or a GPU."""
-
-    def __init__(self, device: int = 0):
-        import torch
-        self._torch = torch
-        self.lib = load_library()
-        if not torch.cuda.is_available():
-            raise EngineError("no GPU visible: the MI355X engine has no CPU fallback")
-        self.device_index = int(device)
-        self.device = torch.device("cuda", self.device_index)
-        h = C.c_void_p()
-        if self.lib.dm_f32_create(self.device_index, C.byref(h)):
-            raise EngineError("dm_f32_create: " + self.lib.dm_f32_last_error(None).decode())
-        self._h = h
-        self.n_prompts = 0
-        self.prompt_generation = 0
-
-    def _check(self, rc: int, what: str):
-        if rc:
-            raise EngineError(f"{what}: {self.lib.dm_f32_last_error(self._h).decode()}")
-
-    def _stream(self):
-        return C.c_void_p(self._torch.cuda.current_stream(self.device).cuda_stream)
-
-    def kmeans_fit(self, X, k: int = 32, seed: int = 10, max_iter: int = 300, tol: float = 1e-4, init_index=None, work=None):
-        """scikit-learn's `KMeans(n_clusters=k, random_state=seed).fit(X)` on this engine's device and current stream
-        (dm_kmeans_fit; see `clustering.kmeans_fit`)."""
-        from . import clustering
-        with self._torch.cuda.device(self.device):
-            return clustering.kmeans_fit(X, k, seed, max_iter, tol, init_index, work)
-
-    def cluster_rank(self, X, labels, centers, D, aggregate: str = "median", order_by: str = "centroid", rank_features=None, work=None):
-        """The tail of the reference's `cluster()` on the device (dm_cluster_rank; see `clustering.rank_clusters`)."""
-        from . import clustering
-        with self._torch.cuda.device(self.device):
-            return clustering.rank_clusters(X, labels, centers, D, aggregate, order_by, rank_features, work)
-
-    def xray_eval(self, maps, boxes, thresholds=None, work=None):
-        """The counts of the X-ray application's AUC-PR and the box sums for a batch of heat-maps on this engine's device and
-        current stream (dm_xray_eval; see `xray.xray_eval`)."""
-        from . import xray
-        with self._torch.cuda.device(self.device):
-            return xray.xray_eval(maps, boxes, thresholds, work)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self.lib.dm_f32_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def load_state_dict(self, sd: Dict[str, "np.ndarray"]):
-        """sd: diffusers-named U-Net state dict (numpy or torch; fp32 kept as is, fp16 / bf16 widened exactly)."""
-        UNetEngine._load(self, self.lib.dm_f32_load_weight, sd, "f32_load_weight")
-        self._check(self.lib.dm_f32_finalize(self._h), "f32_finalize")
+    diffusers-named state dict and prompt-slot mechanism as `UNetEngine`; every tensor at this boundary is fp32."""
+    _OBJ, _RUN, _DTYPE = "dm_f32_", "dm_f32_", "float32"
 
     def load_safetensors(self, path: str):
         from safetensors.numpy import load_file
         self.load_state_dict(load_file(path))
-
-    def load_vae_state_dict(self, sd: Dict[str, "np.ndarray"]):
-        """sd: `AutoencoderKL.state_dict()` (`pipe.vae`); only `encoder.*` and `quant_conv.*` are used.  Optional."""
-        UNetEngine._load(self, self.lib.dm_f32_load_vae_weight, sd, "f32_load_vae_weight")
-        self._check(self.lib.dm_f32_finalize_vae(self._h), "f32_finalize_vae")
-        self._vae_ready = True
-
-    def load_clip_state_dict(self, sd: Dict[str, "np.ndarray"]):
-        """sd: `CLIPTextModel.state_dict()` (`pipe.text_encoder`); the featuriser's pipeline keeps it in fp32 (dift.py:197-199).  Optional."""
-        UNetEngine._load(self, self.lib.dm_f32_load_clip_weight, sd, "f32_load_clip_weight")
-        self._check(self.lib.dm_f32_finalize_clip(self._h), "f32_finalize_clip")
-        self._clip_ready = True
 
     def clip_encode(self, input_ids, out_dtype=None):
         """`text_encoder(input_ids)[0]` in fp32 — `pipe.encode_prompt(prompt)[0]` of the reference's featuriser (dift.py:222-226):
@@ -915,7 +852,7 @@ class UNetEngineF32:
         if ids.dim() != 2 or ids.shape[1] != 77:
             raise ValueError(f"input_ids must be [n, 77], got {tuple(ids.shape)}")
         out = torch.empty(ids.shape[0], 77, 768, dtype=torch.float32, device=self.device)
-        self._check(self.lib.dm_f32_clip_encode(self._h, C.c_void_p(ids.data_ptr()), ids.shape[0], 77, C.c_void_p(out.data_ptr()),
+        self._check(self.lib.dm_f32_clip_encode(self._h, _p(ids), ids.shape[0], 77, _p(out),
                                                 self._stream()), "dm_f32_clip_encode")
         return out
 
@@ -929,8 +866,7 @@ class UNetEngineF32:
         except ValueError as e:
             raise EngineError(f"CLIP vision state dict: {e}") from None
         names = {k: (k if k == "visual_projection.weight" else "vision_model." + k) for k in canon}
-        UNetEngine._load(self, self.lib.dm_f32_load_clip_vision_weight, {names[k]: v for k, v in canon.items()}, "f32_load_clip_vision_weight")
-        self._check(self.lib.dm_f32_finalize_clip_vision(self._h), "f32_finalize_clip_vision")
+        self._load("_clip_vision", {names[k]: v for k, v in canon.items()})
         self._clip_vision_ready = True
 
     def load_clip_vision_dir(self, path: str):
@@ -981,8 +917,8 @@ class UNetEngineF32:
         torch = self._torch
         src, desc_d, tab_d, P = self._clip_batch(images, boxes)
         out = torch.empty(P, 3, 224, 224, dtype=torch.float32, device=self.device)
-        self._check(self.lib.dm_f32_clip_preprocess(self._h, C.c_void_p(src.data_ptr()), C.c_void_p(desc_d.data_ptr()),
-                                                    C.c_void_p(tab_d.data_ptr()), P, C.c_void_p(out.data_ptr()), self._stream()),
+        self._check(self.lib.dm_f32_clip_preprocess(self._h, _p(src), _p(desc_d),
+                                                    _p(tab_d), P, _p(out), self._stream()),
                     "dm_f32_clip_preprocess")
         return out
 
@@ -999,8 +935,8 @@ class UNetEngineF32:
         torch = self._torch
         pv = self._pixel_values(pixel_values)
         out = torch.empty(pv.shape[0], 512, dtype=torch.float32, device=self.device)
-        self._check(self.lib.dm_f32_clip_image_features(self._h, C.c_void_p(pv.data_ptr()), pv.shape[0], int(bool(normalize)),
-                                                        C.c_void_p(out.data_ptr()), self._stream()), "dm_f32_clip_image_features")
+        self._check(self.lib.dm_f32_clip_image_features(self._h, _p(pv), pv.shape[0], int(bool(normalize)),
+                                                        _p(out), self._stream()), "dm_f32_clip_image_features")
         return out
 
     def clip_vision_hidden(self, pixel_values):
@@ -1008,7 +944,7 @@ class UNetEngineF32:
         torch = self._torch
         pv = self._pixel_values(pixel_values)
         out = torch.empty(pv.shape[0], 50, 768, dtype=torch.float32, device=self.device)
-        self._check(self.lib.dm_f32_clip_vision_hidden(self._h, C.c_void_p(pv.data_ptr()), pv.shape[0], C.c_void_p(out.data_ptr()),
+        self._check(self.lib.dm_f32_clip_vision_hidden(self._h, _p(pv), pv.shape[0], _p(out),
                                                        self._stream()), "dm_f32_clip_vision_hidden")
         return out
 
@@ -1018,8 +954,8 @@ class UNetEngineF32:
         torch = self._torch
         src, desc_d, tab_d, P = self._clip_batch(images, boxes)
         out = torch.empty(P, 512, dtype=torch.float32, device=self.device)
-        self._check(self.lib.dm_f32_clip_patch_features(self._h, C.c_void_p(src.data_ptr()), C.c_void_p(desc_d.data_ptr()),
-                                                        C.c_void_p(tab_d.data_ptr()), P, int(bool(normalize)), C.c_void_p(out.data_ptr()),
+        self._check(self.lib.dm_f32_clip_patch_features(self._h, _p(src), _p(desc_d),
+                                                        _p(tab_d), P, int(bool(normalize)), _p(out),
                                                         self._stream()), "dm_f32_clip_patch_features")
         return out
 
@@ -1037,44 +973,10 @@ class UNetEngineF32:
             assert noise.shape == (B * draws_per_image, 4, h, w), noise.shape
         lat = torch.empty(B * draws_per_image, 4, h, w, dtype=torch.float32, device=self.device)
         mom = torch.empty(B, 8, h, w, dtype=torch.float32, device=self.device) if return_moments else None
-        self._check(self.lib.dm_f32_vae_encode(self._h, C.c_void_p(image.data_ptr()), C.c_void_p(noise.data_ptr()) if noise is not None else None,
-                                               B, int(draws_per_image), H, W, float(scaling_factor), C.c_void_p(lat.data_ptr()),
-                                               C.c_void_p(mom.data_ptr()) if mom is not None else None, self._stream()), "dm_f32_vae_encode")
+        self._check(self.lib.dm_f32_vae_encode(self._h, _p(image), _p(noise),
+                                               B, int(draws_per_image), H, W, float(scaling_factor), _p(lat),
+                                               _p(mom), self._stream()), "dm_f32_vae_encode")
         return (lat, mom) if return_moments else lat
-
-    def set_prompts(self, ctx):
-        """ctx [P,77,768] (`prompt_embeds`, dift.py:222-227), kept in fp32."""
-        torch = self._torch
-        ctx = ctx.to(self.device, torch.float32).contiguous()
-        assert ctx.dim() == 3 and ctx.shape[1] == 77 and ctx.shape[2] == 768, ctx.shape
-        self._check(self.lib.dm_f32_set_prompts(self._h, C.c_void_p(ctx.data_ptr()), ctx.shape[0], self._stream()), "f32_set_prompts")
-        self._ctx_keepalive = ctx
-        self.n_prompts = ctx.shape[0]
-        self.prompt_generation += 1
-
-    def _tsl(self, t, slots, B):
-        torch = self._torch
-        t = torch.as_tensor(t, device=self.device).to(torch.int64).reshape(-1)
-        if t.numel() == 1:
-            t = t.expand(B)
-        s = torch.as_tensor(slots)
-        assert s.shape == (B,) and t.shape == (B,), (s.shape, t.shape, B)
-        if s.numel() and not s.is_cuda:
-            lo, hi = int(s.min()), int(s.max())
-            if lo < 0 or hi >= self.n_prompts:
-                raise EngineError(f"prompt slot {lo if lo < 0 else hi} outside the {self.n_prompts} prompts registered by set_prompts")
-        return t.contiguous(), s.to(self.device, torch.int32).contiguous()
-
-    def unet(self, sample, t, slots):
-        """`unet(sample, t, ctx).sample` in fp32 -> [B,4,h,w] fp32."""
-        torch = self._torch
-        sample = sample.to(self.device, torch.float32).contiguous()
-        B, _, h, w = sample.shape
-        t, s = self._tsl(t, slots, B)
-        out = torch.empty(B, 4, h, w, dtype=torch.float32, device=self.device)
-        self._check(self.lib.dm_f32_unet_forward(self._h, C.c_void_p(sample.data_ptr()), C.c_void_p(t.data_ptr()), C.c_void_p(s.data_ptr()),
-                                                 B, h, w, C.c_void_p(out.data_ptr()), self._stream()), "dm_f32_unet_forward")
-        return out
 
     def score(self, x, eps, t, slots, x_index=None):
         """SD.compute_loss (compute.py:95-102) with no autocast: fp32 add_noise, fp32 U-Net, fp32 squared error -> [B,4,h,w] fp32.
@@ -1083,18 +985,12 @@ class UNetEngineF32:
         x = x.to(self.device, torch.float32).contiguous()
         eps = eps.to(self.device, torch.float32).contiguous()
         B, _, h, w = eps.shape
-        t, s = self._tsl(t, slots, B)
-        xi = None
-        if x_index is not None:
-            xi = torch.as_tensor(x_index, device=self.device).to(torch.int32).contiguous()
-            assert xi.shape == (B,)
-        elif x.shape[0] != B:
-            assert x.shape[0] == 1, "x must have 1 or B rows when x_index is not given"
-            xi = torch.zeros(B, dtype=torch.int32, device=self.device)
+        t = self._timesteps(t, B)
+        s = self._slots(slots, B)
+        xi = self._x_index(x_index, x.shape[0], B)
         out = torch.empty(B, 4, h, w, dtype=torch.float32, device=self.device)
-        self._check(self.lib.dm_f32_score(self._h, C.c_void_p(x.data_ptr()), C.c_void_p(xi.data_ptr()) if xi is not None else None,
-                                          C.c_void_p(eps.data_ptr()), C.c_void_p(t.data_ptr()), C.c_void_p(s.data_ptr()), B, x.shape[0], h, w,
-                                          C.c_void_p(out.data_ptr()), self._stream()), "dm_f32_score")
+        self._check(self.lib.dm_f32_score(self._h, _p(x), _p(xi), _p(eps), _p(t), _p(s), B, x.shape[0], h, w, _p(out), self._stream()),
+                    "dm_f32_score")
         return out
 
     def score_conds(self, x, eps, t, n_cond: int, x_index=None, latent_dtype=None, slot_table=None):
@@ -1116,33 +1012,3 @@ class UNetEngineF32:
         else:
             slots = torch.arange(n_cond, dtype=torch.int32).repeat_interleave(U)
         return self.score(xx, eps.repeat(n_cond, 1, 1, 1), t.repeat(n_cond), slots, x_index=xi)
-
-    def dift(self, noisy, t, slots, up_ft_index: int = 1, ensemble: Optional[int] = None):
-        """MyUNet2DConditionModel.forward tap (dift.py:24-169) in the reference's fp32.  Returns (features fp32 [B,C,h',w'],
-        ensemble mean fp32 [B/ens,C,h',w'] or None)."""
-        torch = self._torch
-        noisy = noisy.to(self.device, torch.float32).contiguous()
-        B, _, h, w = noisy.shape
-        t, s = self._tsl(t, slots, B)
-        c, oh, ow = dift_shape(h, w, up_ft_index)
-        feat = torch.empty(B, c, oh, ow, dtype=torch.float32, device=self.device)
-        mean = torch.empty(B // ensemble, c, oh, ow, dtype=torch.float32, device=self.device) if ensemble else None
-        self._check(self.lib.dm_f32_dift(self._h, C.c_void_p(noisy.data_ptr()), C.c_void_p(t.data_ptr()), C.c_void_p(s.data_ptr()), B, h, w,
-                                         up_ft_index, C.c_void_p(feat.data_ptr()), C.c_void_p(mean.data_ptr()) if mean is not None else None,
-                                         int(ensemble or 1), self._stream()), "dm_f32_dift")
-        return feat, mean
-
-    def prof_enable(self, on: bool = True):
-        self._check(self.lib.dm_f32_prof_enable(self._h, 1 if on else 0), "f32_prof_enable")
-
-    def prof_read(self) -> dict:
-        a, b, c2 = C.c_double(), C.c_double(), C.c_int64()
-        d, e, f = C.c_double(), C.c_double(), C.c_int64()
-        self._check(self.lib.dm_f32_prof_read(self._h, C.byref(a), C.byref(b), C.byref(c2), C.byref(d), C.byref(e), C.byref(f)), "f32_prof_read")
-        return {"igemm_ms": a.value, "igemm_flops": b.value, "igemm_launches": c2.value,
-                "attn_ms": d.value, "attn_flops": e.value, "attn_launches": f.value}
-
-    def memory(self) -> dict:
-        a, b = C.c_size_t(), C.c_size_t()
-        self._check(self.lib.dm_f32_memory(self._h, C.byref(a), C.byref(b)), "f32_memory")
-        return {"weights_bytes": a.value, "arena_bytes": b.value}

@@ -30,6 +30,8 @@ import warnings
 
 import numpy as np
 
+from .engine import EngineError, UNetEngine, _p, load_library as _lib
+
 XRAY_MAX_THRESHOLDS = 4096       # DM_XRAY_MAX_THRESHOLDS
 XRAY_MAX_PIXELS = 1 << 24        # H W >= 2^24 is refused
 # dm_xray_desc of include/dm_engine.h (32 bytes)
@@ -129,16 +131,6 @@ def xray_scores_from_counts(tp, fp, n_in, box_sum):
 # ------------------------------------------------------------------------------------------------------------------------------
 # the device path
 # ------------------------------------------------------------------------------------------------------------------------------
-def _lib():
-    from .engine import load_library
-    lib = load_library()
-    vp, i32 = C.c_void_p, C.c_int
-    lib.dm_xray_eval_workspace_bytes.argtypes = [i32, i32, C.c_int64]
-    lib.dm_xray_eval_workspace_bytes.restype = C.c_size_t
-    lib.dm_xray_eval.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp]
-    return lib
-
-
 def workspace_bytes(n_rows: int, n_thresholds: int, max_pixels: int) -> int:
     need = _lib().dm_xray_eval_workspace_bytes(int(n_rows), int(n_thresholds), int(max_pixels))
     if not need:
@@ -155,7 +147,6 @@ def xray_eval(maps, boxes, thresholds=None, work=None):
     not matter).  Returns device tensors (tp int32 [n, T], fp int32 [n, T], n_in int32 [n], box_sum float64 [n]); bit-reproducible.
     A list of numpy arrays takes `xray_counts_host` and returns numpy arrays; anything else that is not on a GPU raises."""
     import torch
-    from .engine import EngineError, UNetEngine
     if len(maps) and all(isinstance(m, np.ndarray) for m in maps):
         return xray_counts_host(maps, boxes, thresholds)
     thr = _check_thresholds(thresholds)
@@ -184,9 +175,8 @@ def xray_eval(maps, boxes, thresholds=None, work=None):
     fp = torch.empty((n, T), dtype=torch.int32, device=dev)
     n_in = torch.empty(n, dtype=torch.int32, device=dev)
     box_sum = torch.empty(n, dtype=torch.float64, device=dev)
-    p = lambda t: C.c_void_p(t.data_ptr())          # noqa: E731
     with torch.cuda.device(dev):
-        rc = _lib().dm_xray_eval(p(packed), p(desc_d), n, p(thr_d), T, p(work), p(tp), p(fp), p(n_in), p(box_sum),
+        rc = _lib().dm_xray_eval(_p(packed), _p(desc_d), n, _p(thr_d), T, _p(work), _p(tp), _p(fp), _p(n_in), _p(box_sum),
                                  C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
     if rc:
         raise EngineError(f"dm_xray_eval: {ERRORS.get(rc, 'error')} (code {rc})")

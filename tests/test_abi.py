@@ -32,6 +32,93 @@ def test_header_symbols_are_exported(lib):
     assert b"gfx950" in lib.dm_version()
 
 
+def _header_signatures():
+    """name -> (return kind, [argument kinds]) of every dm_* declaration of include/dm_engine.h (plain C, comments stripped)."""
+    hdr = open(os.path.join(ROOT, "include", "dm_engine.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    hdr = re.sub(r"//[^\n]*", "", hdr)
+    scalar = {"float": "f32", "double": "f64", "int64_t": "i64", "size_t": "size", "int": "i32", "int32_t": "i32"}
+    out = {}
+    for ret, name, args in re.findall(r"^\s*((?:const\s+)?\w+\s*\*?)\s*(dm_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", hdr, flags=re.M):
+        ret = {"const char *": "char_p", "size_t": "size", "void": "void", "int": "i32"}[" ".join(ret.replace("*", " * ").split())]
+        args = [] if args.strip() == "void" else args.split(",")
+        out[name] = (ret, ["ptr" if "*" in a else scalar[" ".join(a.split()[:-1])] for a in args])
+    return out
+
+
+def _ctypes_kind(t):
+    C = E.C
+    if t is None:
+        return "void"
+    if t in (C.c_void_p, C.c_char_p) or issubclass(t, C._Pointer):
+        return "ptr"
+    if t in (C.c_float, C.c_double, C.c_size_t):
+        return {C.c_float: "f32", C.c_double: "f64", C.c_size_t: "size"}[t]
+    assert t._type_ in "ilq", t                   # a signed integer: told apart by its width
+    return {4: "i32", 8: "i64"}[C.sizeof(t)]
+
+
+def _signature_mismatches(table):
+    """Every way `table` (name -> (restype, argtypes)) disagrees with the header: count, kind per argument, kind of the return."""
+    bad = []
+    declared = _header_signatures()
+    if set(declared) != set(table):
+        bad.append(("symbols", sorted(set(declared) ^ set(table))))
+    for name, (ret, kinds) in declared.items():
+        if name not in table:
+            continue
+        restype, argtypes = table[name]
+        got_ret = "char_p" if restype is E.C.c_char_p else _ctypes_kind(restype)
+        got = [_ctypes_kind(t) for t in argtypes]
+        if got_ret != ret:
+            bad.append((name, "returns", got_ret, ret))
+        if got != kinds:
+            bad.append((name, got, kinds))
+    return bad
+
+
+def test_signature_table_matches_the_header():
+    """Argument count, the kind of every argument (pointer / fp32 / fp64 / 32-bit / 64-bit integer / size_t) and the return kind of
+    every symbol, table against header.  (Checked the same way, the lists the binding carried before the table had no mismatch; two
+    symbols, dm_version and dm_op_igemm_head_rows, had no list at all.)"""
+    declared = _header_signatures()
+    assert len(declared) >= 92 and declared["dm_version"] == ("char_p", [])
+    assert declared["dm_xray_eval_workspace_bytes"] == ("size", ["i32", "i32", "i64"])
+    assert declared["dm_kmeans_fit"][1][8:11] == ["f32", "ptr", "size"] and declared["dm_engine_destroy"][0] == "void"
+    assert E.SYMBOLS == list(E.SIGNATURES)
+    assert _signature_mismatches(E.SIGNATURES) == []
+
+
+def test_signature_check_sees_a_wrong_entry():
+    """The comparison itself: one i32 too few, an i32 where the header says int64_t, a pointer for a float, a wrong return type."""
+    C = E.C
+    for name, edit in (("dm_score", lambda r, a: (r, a[:-3] + a[-2:])),
+                       ("dm_normalize_map", lambda r, a: (r, a[:2] + [C.c_int] + a[3:])),
+                       ("dm_op_attention", lambda r, a: (r, a[:9] + [C.c_int] + a[10:])),
+                       ("dm_op_layernorm", lambda r, a: (r, a[:6] + [C.c_void_p] + a[7:])),
+                       ("dm_xray_eval_workspace_bytes", lambda r, a: (C.c_int, a)),
+                       ("dm_f32_destroy", lambda r, a: (C.c_int, a))):
+        table = dict(E.SIGNATURES)
+        table[name] = edit(table[name][0], list(table[name][1]))
+        bad = _signature_mismatches(table)
+        assert len(bad) == 1 and bad[0][0] == name, (name, bad)
+    table = dict(E.SIGNATURES)
+    del table["dm_mine_parallel"]
+    assert _signature_mismatches(table) == [("symbols", ["dm_mine_parallel"])]
+
+
+def test_load_library_applies_the_whole_table(lib):
+    """Every symbol carries its table entry once the library is loaded — the k-means and X-ray ones too, whether or not the modules
+    that call them have been imported."""
+    for name, (restype, argtypes) in E.SIGNATURES.items():
+        fn = getattr(lib, name)
+        assert list(fn.argtypes) == list(argtypes), name
+        assert fn.restype is restype, name
+    for name in ("dm_kmeans_workspace_bytes", "dm_kmeans_fit", "dm_cluster_rank", "dm_xray_eval_workspace_bytes", "dm_xray_eval"):
+        assert name in E.SYMBOLS and getattr(lib, name).argtypes is not None
+    assert lib.dm_xray_eval_workspace_bytes.restype is E.C.c_size_t
+
+
 def test_scheduler_table_matches_oracle(lib):
     a = E.scheduler_alphas_cumprod()
     b = R.alphas_cumprod().numpy()

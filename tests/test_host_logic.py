@@ -253,14 +253,48 @@ def test_dift_featurizer_registers_a_prompt_once():
 
 
 def test_slot_range_is_checked_before_the_call():
-    from diff_mining_amd.engine import EngineError, UNetEngine
-    e = UNetEngine.__new__(UNetEngine)
-    e._torch, e.device, e.n_prompts = torch, torch.device("cpu"), 2
-    assert e._slots([0, 1, 1, 0], 4).dtype == torch.int32
-    with pytest.raises(EngineError, match="prompt slot 2"):
-        e._slots(torch.tensor([0, 2]), 2)
-    with pytest.raises(EngineError, match="prompt slot -1"):
-        e._slots([-1, 0], 2)
+    from diff_mining_amd.engine import EngineError, UNetEngine, UNetEngineF32
+    for cls in (UNetEngine, UNetEngineF32):          # one check, in the class both engines derive from
+        e = cls.__new__(cls)
+        e._torch, e.device, e.n_prompts = torch, torch.device("cpu"), 2
+        assert e._slots([0, 1, 1, 0], 4).dtype == torch.int32
+        with pytest.raises(EngineError, match="prompt slot 2"):
+            e._slots(torch.tensor([0, 2]), 2)
+        with pytest.raises(EngineError, match="prompt slot -1"):
+            e._slots([-1, 0], 2)
+
+
+def test_map_views_are_cut_out_of_the_packed_buffer():
+    """`_views` (the tail of typicality_image_batched and mine_parallel): two images of different sizes, window 3 x 2."""
+    from diff_mining_amd import engine as E
+    kx, ky = 3, 2
+    desc = np.zeros(2, dtype=E.MINE_DESC_DTYPE)
+    desc["H"], desc["W"] = [7, 5], [6, 9]                    # maps [5, 5] and [3, 8]
+    desc["map_offset"] = [4, 29]                             # the first map does not start the buffer
+    buf = torch.arange(60, dtype=torch.float32)
+    a, b = E._views(buf, desc, kx, ky)
+    assert a.shape == (5, 5) and b.shape == (3, 8)
+    assert torch.equal(a, buf[4:29].reshape(5, 5)) and torch.equal(b, buf[29:53].reshape(3, 8))
+    assert a.data_ptr() == buf[4:].data_ptr() and b.data_ptr() == buf[29:].data_ptr()        # views, not copies
+    assert a[2, 3] == 4 + 2 * 5 + 3 and b[1, 7] == 29 + 1 * 8 + 7
+    table, total = E._mine_desc([a.shape, b.shape], kx, ky)  # the table the mining calls build for such maps packed back to back
+    assert total == 49 and list(table["map_offset"]) == [0, 25] and list(table["H"]) == [7, 5] and list(table["W"]) == [6, 9]
+    assert [tuple(v.shape) for v in E._views(buf, table, kx, ky)] == [(5, 5), (3, 8)]
+
+
+def test_place_maps_in_place_or_packed():
+    from diff_mining_amd.engine import UNetEngine
+    buf = torch.arange(64, dtype=torch.float32)
+    views = [buf[8:20].view(3, 4), buf[30:50].view(4, 5), buf[20:26].view(2, 3)]
+    base, off, copied = UNetEngine._place_maps(torch, views, "cpu")
+    assert copied is False and off == [0, 22, 12] and base.data_ptr() == buf[8:].data_ptr() and base.numel() == 42
+    for v, o in zip(views, off):
+        assert torch.equal(base[o:o + v.numel()].view(v.shape), v)
+    for mixed in (views[:2] + [buf[20:26].view(2, 3).half()], views[:2] + [buf[:24].view(4, 6)[:, 1:4]]):
+        base, off, copied = UNetEngine._place_maps(torch, mixed, "cpu")
+        assert copied is True and base.dtype == torch.float32 and off == [0, 12, 32] and base.numel() == 32 + mixed[2].numel()
+        for v, o in zip(mixed, off):
+            assert torch.equal(base[o:o + v.numel()].view(v.shape), v.float())
 
 
 def test_bench_gpus_flag_launches_its_own_ranks():
