@@ -1,0 +1,403 @@
+"""The Doersch-2012 HOG+SVM baseline's dense detector search (doersch/hog.py:124-185, `dense_search_cuda`) on the GPU: every
+detector against every cell of every image of the data set, keeping per detector the `top_k` images by their best cell.  Kernels:
+csrc/dense_search.hip; C ABI: dm_dense_search_workspace_bytes / _winners / _topk / _gather (include/dm_engine.h).
+
+The reference forms `(data.reshape(B*W*H, C).unsqueeze(1) * w.unsqueeze(0)).sum(-1)`, a [B W H, K, C] fp16 tensor, takes
+`torch.topk(..., 1)` per (detector, image) and merges Python tuples on the host.  Here the product is an fp16 GEMM on the matrix
+cores whose output never leaves the registers; what grows with the data set is two [K][n_images] tables.  The rules, which
+`dense_search_host` (numpy) and the kernels share:
+
+  score     s(k, b, i) = the sum over c of the exact products data[b, i, c] * w[k, c] of the fp16 operands, in fp32 (the device: MFMA
+            fp32 accumulation; the host: fp64 products and sum, rounded to fp32).  -0 counts as +0.
+  mask      a cell whose mask byte is 0 scores +0 exactly (the reference multiplies by the mask, hog.py:153: a masked cell beats
+            every negative score), unless its score is NaN, which stays NaN (NaN * 0).
+  winner    per (detector, image): the largest score, the lowest cell index among equal scores.  A NaN score never wins (the
+            reference's `normalize` divides an all-zero cell by its zero norm, so NaN rows occur in real caches); an image with no
+            non-NaN cell has score -inf and cell -1.
+  top-k     per detector: descending score, ascending image index among equal scores (the reference's stable `sorted(...,
+            reverse=True)` over entries in image order); -inf is never admitted; `only_pos` admits score > 0 only (hog.py:177).
+  limits    1 <= K <= 128 detectors, 1 <= top_k <= 128, C >= 8 and C % 8 == 0, W H < 2^24.
+
+An entry of the result is the reference's tuple `(score, (a * 8, b * 8), path)` with cell = a * H + b, plus the cell's feature row
+with `ret_ws`.  Ranking is always by the fp32 score.  What an entry SHOWS is, with scores="f32", that fp32 score; by default
+(scores="f16") a numpy.float16 scalar in the reference's own arithmetic, `reference_score_f16`: every product rounded to fp16, the
+products summed, the sum rounded to fp16 — computed on the host from the winning cell's feature row, for the K top_k listed entries
+only.  (Rounding the fp32 score instead would land one fp16 unit beside the reference's value wherever the exact sum lies near the
+middle between two fp16 numbers.)  A masked winner shows 0.  Because the shown value is another sum than the ranked one, two
+neighbours of a list that are closer than the reference's own error can show in ascending order.  (With `fold` the reference's
+scores are float32 scalars that hold fp16 values, because its float32 mask promotes them; here the type does not depend on `fold`.)
+
+Not here: the HOG-LAB features themselves (the entry takes the cached, normalised features the reference writes), the SVM rounds,
+`accept_patch_neighbor`, the plots.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from .engine import EngineError, _p, load_library as _lib
+
+DENSE_MAX_DETECTORS = 128        # DM_DENSE_MAX_DETECTORS
+DENSE_MAX_TOPK = 128             # DM_DENSE_MAX_TOPK
+DENSE_MAX_CELLS = 1 << 24        # W H >= 2^24 is refused
+# DM_DENSE_E_* (include/dm_engine.h)
+ERRORS = {1: "null argument", 2: "B, n_images or n < 1", 3: "cells < 1", 4: "cells >= 2^24", 5: f"K outside [1, {DENSE_MAX_DETECTORS}]",
+          6: f"top_k outside [1, {DENSE_MAX_TOPK}]", 7: "C < 8 or not a multiple of 8", 8: "ld < image_offset + B", 9: "workspace too small",
+          10: "misaligned pointer", 11: "HIP error"}
+
+
+def _check(rc: int, what: str):
+    if rc:
+        raise EngineError(f"{what}: {ERRORS.get(rc, 'error')} (code {rc})")
+
+
+def _check_shape(B, cells, C_, K, top_k=1):
+    if B < 1 or cells < 1:
+        raise ValueError(f"dense search: {B} images of {cells} cells")
+    if cells >= DENSE_MAX_CELLS:
+        raise ValueError(f"dense search: {cells} cells per image, 2^24 or more")
+    if not 1 <= K <= DENSE_MAX_DETECTORS:
+        raise ValueError(f"dense search: {K} detectors, need 1 ... {DENSE_MAX_DETECTORS}")
+    if not 1 <= top_k <= DENSE_MAX_TOPK:
+        raise ValueError(f"dense search: top_k {top_k}, need 1 ... {DENSE_MAX_TOPK}")
+    if C_ < 8 or C_ % 8:
+        raise ValueError(f"dense search: {C_} channels, need a multiple of 8 (2112 = 8 * 264)")
+
+
+def fold_mask(path_id: int, B: int, cells: int, fold, device="cpu"):
+    """The reference's fold mask of one shard key (hog.py:149-152) by its own calls: `torch.manual_seed(path_id)`, then one
+    `torch.randperm(cells, device=device)[: i * cells // l]` per image, fold = (i, l); uint8 [B, cells] on `device`, 1 = the cell
+    takes part.  Reseeds torch's global generators, as the reference does.  The bits of a permutation drawn on a GPU are
+    torch-ROCm's: they equal neither the CPU's nor CUDA's, so a fold drawn on the device selects other cells than the reference did
+    on its machine (the same share of them); draw on "cpu" where the cells themselves have to agree."""
+    import torch
+    i, l = int(fold[0]), int(fold[1])
+    torch.manual_seed(int(path_id))
+    indices = torch.stack([torch.randperm(cells, device=device)[:(i * cells) // l] for _ in range(B)])
+    return torch.zeros(B, cells, dtype=torch.uint8, device=device).scatter_(1, indices, 1)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the numpy restatement: the CPU-tier yardstick, and the path a numpy input takes
+# ------------------------------------------------------------------------------------------------------------------------------
+def winners_host(data, w, mask=None):
+    """data fp16 [B, cells, C] (or [B, W, H, C]), w fp16 [K, C], mask [B, cells] or None -> (score float32 [K, B], cell int32
+    [K, B]) by the rules at the top of this module."""
+    data, w = np.asarray(data), np.asarray(w)
+    if data.dtype != np.float16 or w.dtype != np.float16:
+        raise ValueError("dense search: data and w must be float16")
+    data = data.reshape(data.shape[0], -1, data.shape[-1])
+    B, cells, C_ = data.shape
+    K = w.shape[0]
+    _check_shape(B, cells, C_, K)
+    if w.ndim != 2 or w.shape[1] != C_:
+        raise ValueError(f"dense search: w {w.shape} against {C_} channels")
+    score, cell = np.empty((K, B), dtype=np.float32), np.empty((K, B), dtype=np.int32)
+    w64 = w.astype(np.float64).T
+    with np.errstate(all="ignore"):
+        for b in range(B):
+            s = (data[b].astype(np.float64) @ w64).astype(np.float32) + np.float32(0)      # [cells, K]; -0 -> +0
+            valid = ~np.isnan(s)
+            if mask is not None:
+                s[np.asarray(mask)[b].reshape(-1) == 0] = 0
+            t = np.where(valid, s, -np.inf)
+            best = t.max(axis=0)                                                            # [K]
+            first = (valid & (t == best[None, :])).argmax(axis=0)                          # the lowest cell among equals
+            none = ~valid.any(axis=0)
+            score[:, b] = np.where(none, -np.inf, best)
+            cell[:, b] = np.where(none, -1, first)
+    return score, cell
+
+
+def reference_score_f16(row, w_k, score_f32=None):
+    """The reference's fp16 value of one (cell, detector) pair (hog.py:144): `(row * w_k).sum()` with fp16 products (each the
+    correctly rounded product of two fp16 numbers) and an fp16 result; the products are summed in fp64 here, in fp32 by torch on a
+    CPU, which differ only where the sum lies within an fp32 rounding of the middle between two fp16 numbers.  A winner whose fp32
+    score is exactly 0 is a masked cell (`scores * mask`): 0."""
+    if score_f32 is not None and score_f32 == 0:
+        return np.float16(0)
+    with np.errstate(all="ignore"):
+        return np.float16((np.asarray(row, dtype=np.float16) * np.asarray(w_k, dtype=np.float16)).astype(np.float64).sum())
+
+
+def topk_host(score, cell, top_k: int, only_pos: bool = False):
+    """score float32 [K, n], cell int32 [K, n] -> (top_score float32 [K, top_k], top_image int32, top_cell int32, count int32
+    [K]); slots from count on hold NaN / -1 / -1."""
+    score, cell = np.asarray(score, dtype=np.float32), np.asarray(cell, dtype=np.int32)
+    K, n = score.shape
+    top_score = np.full((K, top_k), np.nan, dtype=np.float32)
+    top_image, top_cell = np.full((K, top_k), -1, dtype=np.int32), np.full((K, top_k), -1, dtype=np.int32)
+    count = np.zeros(K, dtype=np.int32)
+    for k in range(K):
+        s = score[k]
+        ok = ~np.isnan(s) & (s != -np.inf)
+        if only_pos:
+            ok &= s > 0
+        idx = np.nonzero(ok)[0]
+        idx = idx[np.argsort(-s[idx].astype(np.float64), kind="stable")][:top_k]            # stable: ascending image among equals
+        count[k] = len(idx)
+        top_score[k, :len(idx)], top_image[k, :len(idx)], top_cell[k, :len(idx)] = s[idx], idx, cell[k, idx]
+    return top_score, top_image, top_cell, count
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the device calls
+# ------------------------------------------------------------------------------------------------------------------------------
+def workspace_bytes(B: int, cells: int, K: int) -> int:
+    need = _lib().dm_dense_search_workspace_bytes(int(B), int(cells), int(K))
+    if not need:
+        raise ValueError(f"dense search: no workspace for {B} images of {cells} cells and {K} detectors")
+    return need
+
+
+def _stream(torch, dev):
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def winners(data, w, score, cell, image_offset: int = 0, mask=None, work=None):
+    """dm_dense_search_winners on the current stream: data fp16 [B, cells, C] and w fp16 [K, C] on the GPU, contiguous; writes
+    column image_offset + b of the tables score fp32 / cell int32 [K, ld].  work: a uint8 workspace of at least
+    `workspace_bytes(B, cells, K)` to reuse."""
+    import torch
+    B, cells, C_ = data.shape
+    K, ld = score.shape
+    dev = data.device
+    need = workspace_bytes(B, cells, K)
+    if work is None:
+        work = torch.empty(need, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib().dm_dense_search_winners(_stream(torch, dev), _p(data), _p(w), _p(mask), B, cells, C_, K, int(image_offset), ld,
+                                            _p(work), work.numel() * work.element_size(), _p(score), _p(cell))
+    _check(rc, "dm_dense_search_winners")
+    return work
+
+
+def topk(score, cell, n_images: int, top_k: int, only_pos: bool = False):
+    """dm_dense_search_topk on the current stream over columns [0, n_images) of the tables -> device tensors (top_score fp32
+    [K, top_k], top_image int32, top_cell int32, count int32 [K])."""
+    import torch
+    K, ld = score.shape
+    dev = score.device
+    top_score = torch.empty((K, top_k), dtype=torch.float32, device=dev)
+    top_image = torch.empty((K, top_k), dtype=torch.int32, device=dev)
+    top_cell = torch.empty((K, top_k), dtype=torch.int32, device=dev)
+    count = torch.empty(K, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib().dm_dense_search_topk(_stream(torch, dev), _p(score), _p(cell), K, int(n_images), ld, int(top_k), int(bool(only_pos)),
+                                         _p(top_score), _p(top_image), _p(top_cell), _p(count))
+    _check(rc, "dm_dense_search_topk")
+    return top_score, top_image, top_cell, count
+
+
+def gather(data, pairs):
+    """dm_dense_search_gather: data fp16 [B, cells, C] on the GPU, pairs int32 [n, 2] = (image in the chunk, cell) on the GPU ->
+    fp16 [n, C], bit copies."""
+    import torch
+    B, cells, C_ = data.shape
+    n = pairs.shape[0]
+    out = torch.empty((n, C_), dtype=torch.float16, device=data.device)
+    with torch.cuda.device(data.device):
+        rc = _lib().dm_dense_search_gather(_stream(torch, data.device), _p(data), B, cells, C_, _p(pairs), n, _p(out))
+    _check(rc, "dm_dense_search_gather")
+    return out
+
+
+class DenseSearch:
+    """The search of one set of detectors over a data set that arrives in chunks.
+
+        ds = DenseSearch(w, top_k=50)
+        for paths, data in chunks: ds.add(paths, data)          # data: fp16 [B, W, H, C] on the GPU
+        lists = ds.result()                                     # per detector [(score, (a * 8, b * 8), path), ...], score descending
+
+    w: [K, C], any float type, rounded to fp16 as the reference does.  State that grows with the data set: the two [K][n_images]
+    tables of winners (grown by doubling) and the list of paths.  The winning rows are kept when `result(ret_ws=True)` needs them
+    (keep_rows=True) or the shown scores do (scores="f16", the default): after every chunk the running top-k is taken and the
+    feature rows of this chunk's entries in it are gathered, rows that fell out are dropped — at most K top_k rows are alive, never
+    [K][n_images][C]; it costs one top-k launch and one small device-to-host copy per chunk.  scores="f32" without keep_rows keeps
+    no rows and never synchronises before `result`.
+    A numpy `data` takes the host restatement (`winners_host` / `topk_host`); chunks must be all numpy or all on one GPU."""
+
+    def __init__(self, w, top_k: int = 50, only_pos: bool = False, keep_rows: bool = False, scores: str = "f16"):
+        if scores not in ("f16", "f32"):
+            raise ValueError(f"dense search: scores={scores!r}, need 'f16' or 'f32'")
+        w = w.detach().cpu().numpy() if hasattr(w, "detach") else np.asarray(w)
+        if w.ndim != 2:
+            raise ValueError(f"dense search: w must be [K, C], got {w.shape}")
+        self.w = np.ascontiguousarray(w.astype(np.float16))
+        self.K, self.C = self.w.shape
+        self.top_k, self.only_pos, self.keep_rows, self.scores = int(top_k), bool(only_pos), bool(keep_rows) or scores == "f16", scores
+        _check_shape(1, 1, self.C, self.K, self.top_k)
+        self.paths, self.dims = [], []           # per image: its path and (W, H)
+        self.n = 0
+        self._host = None                        # True: numpy chunks; False: device chunks
+        self._score = self._cell = self._w_dev = self._work = None
+        self._rows = {}                          # (detector, image) -> feature row, while the entry is inside the running top-k
+
+    # -- chunks ----------------------------------------------------------------------------------------------------------------
+    def add(self, paths, data, mask=None):
+        """One chunk: `paths` of its B images, data fp16 [B, W, H, C], mask [B, W H] (0 = the cell scores 0) or None."""
+        if data.ndim != 4 or data.shape[0] != len(paths) or data.shape[3] != self.C:
+            raise ValueError(f"dense search: chunk {tuple(data.shape)} for {len(paths)} paths and {self.C} channels")
+        B, W, H, _ = data.shape
+        _check_shape(B, W * H, self.C, self.K, self.top_k)
+        if mask is not None and tuple(mask.shape) != (B, W * H):
+            raise ValueError(f"dense search: mask {tuple(mask.shape)}, need {(B, W * H)}")
+        host = isinstance(data, np.ndarray)
+        if self._host is None:
+            self._host = host
+        elif self._host != host:
+            raise ValueError("dense search: numpy and device chunks in one search")
+        (self._add_host if host else self._add_device)(data, mask, B, W * H)
+        self.paths += list(paths)
+        self.dims += [(W, H)] * B
+        self.n += B
+
+    def _grow(self, B, empty, copy):
+        cap = 0 if self._score is None else self._score.shape[1]
+        if self.n + B <= cap:
+            return
+        cap = max(2 * cap, self.n + B, 64)
+        score, cell = empty((self.K, cap), "float32"), empty((self.K, cap), "int32")
+        if self.n:
+            copy(score, self._score)
+            copy(cell, self._cell)
+        self._score, self._cell = score, cell
+
+    def _add_host(self, data, mask, B, cells):
+        if data.dtype != np.float16:
+            raise ValueError("dense search: data must be float16")
+
+        def copy(dst, src):
+            dst[:, :self.n] = src[:, :self.n]
+        self._grow(B, lambda s, dt: np.empty(s, dtype=dt), copy)
+        data = data.reshape(B, cells, self.C)
+        s, c = winners_host(data, self.w, None if mask is None else np.asarray(mask))
+        self._score[:, self.n:self.n + B], self._cell[:, self.n:self.n + B] = s, c
+        if self.keep_rows:
+            _, img, cell, count = topk_host(self._score[:, :self.n + B], self._cell[:, :self.n + B], self.top_k, self.only_pos)
+            self._keep(img, cell, count, lambda pairs: data[pairs[:, 0], pairs[:, 1]].copy())
+
+    def _add_device(self, data, mask, B, cells):
+        import torch
+        if not (isinstance(data, torch.Tensor) and data.is_cuda):
+            raise EngineError("DenseSearch.add: data must be a torch tensor on the GPU, or numpy for the host restatement")
+        if data.dtype != torch.float16:
+            raise ValueError("dense search: data must be float16")
+        dev = data.device
+        if self._w_dev is None:
+            self._w_dev = torch.from_numpy(self.w).to(dev)
+        elif self._w_dev.device != dev:
+            raise ValueError(f"dense search: a chunk on {dev}, earlier ones on {self._w_dev.device}")
+        data = data.contiguous().view(B, cells, self.C)
+        if mask is not None:
+            mask = mask.to(device=dev, dtype=torch.uint8).contiguous()
+
+        def copy(dst, src):
+            dst[:, :self.n].copy_(src[:, :self.n])
+        self._grow(B, lambda s, dt: torch.empty(s, dtype=getattr(torch, dt), device=dev), copy)
+        need = workspace_bytes(B, cells, self.K)
+        if self._work is None or self._work.numel() < need:
+            self._work = torch.empty(need, dtype=torch.uint8, device=dev)
+        winners(data, self._w_dev, self._score, self._cell, self.n, mask, self._work)
+        if self.keep_rows:
+            _, img, cell, count = topk(self._score, self._cell, self.n + B, self.top_k, self.only_pos)
+            img, cell, count = img.cpu().numpy(), cell.cpu().numpy(), count.cpu().numpy()
+            self._keep(img, cell, count,
+                       lambda pairs: gather(data, torch.from_numpy(np.ascontiguousarray(pairs, dtype=np.int32)).to(dev)).cpu().numpy())
+
+    def _keep(self, img, cell, count, rows_of):
+        """The running top-k after a chunk: fetch the rows of its entries that lie in this chunk, drop the rows that fell out."""
+        alive, want = set(), []
+        for k in range(self.K):
+            for j in range(int(count[k])):
+                key = (k, int(img[k, j]))
+                alive.add(key)
+                if key[1] >= self.n:
+                    want.append((key, (key[1] - self.n, int(cell[k, j]))))
+        self._rows = {key: row for key, row in self._rows.items() if key in alive}
+        if want:
+            rows = rows_of(np.array([p for _, p in want], dtype=np.int64))
+            for (key, _), row in zip(want, rows):
+                self._rows[key] = row
+
+    # -- the answer ------------------------------------------------------------------------------------------------------------
+    def tables(self):
+        """(score float32 [K, n_images], cell int32 [K, n_images]) as numpy arrays: the winner of every (detector, image) so far."""
+        if not self.n:
+            raise ValueError("dense search: no chunk yet")
+        if self._host:
+            return self._score[:, :self.n].copy(), self._cell[:, :self.n].copy()
+        return self._score[:, :self.n].cpu().numpy(), self._cell[:, :self.n].cpu().numpy()
+
+    def topk(self):
+        """(top_score float32 [K, top_k], top_image int32, top_cell int32, count int32 [K]) as numpy arrays."""
+        if not self.n:
+            raise ValueError("dense search: no chunk yet")
+        if self._host:
+            return topk_host(self._score[:, :self.n], self._cell[:, :self.n], self.top_k, self.only_pos)
+        return tuple(t.cpu().numpy() for t in topk(self._score, self._cell, self.n, self.top_k, self.only_pos))
+
+    def result(self, ret_ws: bool = False):
+        """The reference's return value: per detector a list, score descending, of (score, (a * 8, b * 8), path), with the winning
+        cell's feature row (numpy float16 [C]) appended under ret_ws (needs keep_rows=True or scores="f16").  Unlike the reference, a detector
+        without an admissible entry gives an empty list instead of a failed assertion."""
+        if ret_ws and not self.keep_rows:
+            raise ValueError("dense search: result(ret_ws=True) with scores='f32' needs DenseSearch(..., keep_rows=True)")
+        top_score, top_image, top_cell, count = self.topk()
+        out = []
+        for k in range(self.K):
+            entries = []
+            for j in range(int(count[k])):
+                img, cell = int(top_image[k, j]), int(top_cell[k, j])
+                W, H = self.dims[img]
+                s = top_score[k, j] if self.scores == "f32" else reference_score_f16(self._rows[(k, img)], self.w[k], top_score[k, j])
+                bbox = ((cell // H) * 8, (cell % H) * 8)                 # make_bbox: np.unravel_index(cell, (W, H)) * 8
+                entries.append((s, bbox, self.paths[img]) + ((self._rows[(k, img)],) if ret_ws else ()))
+            out.append(entries)
+        return out
+
+
+def dense_search_host(w, chunks, top_k: int = 50, ret_ws: bool = False, only_pos: bool = False, scores: str = "f16"):
+    """The numpy restatement of the whole search.  chunks: an iterable of (paths, data fp16 [B, W, H, C]) or (paths, data, mask).
+    Returns what `DenseSearch.result` returns."""
+    ds = DenseSearch(w, top_k=top_k, only_pos=only_pos, keep_rows=ret_ws, scores=scores)
+    for chunk in chunks:
+        paths, data = chunk[0], np.asarray(chunk[1])
+        mask = None if len(chunk) < 3 or chunk[2] is None else np.asarray(chunk[2])
+        ds.add(paths, data, mask)
+    return ds.result(ret_ws=ret_ws)
+
+
+def dense_search(w, sft_paths, top_k: int = 50, ret_ws: bool = False, fold=None, only_pos: bool = False, device_id: str = "cuda",
+                 scores: str = "f16"):
+    """`dense_search_cuda(w, sft_paths, top_k, ret_ws=, fold=, only_pos=, device_id=)` of doersch/hog.py: w [K, C] numpy; sft_paths:
+    the reference's safetensors shards, each key `';;'.join(paths)` with a tensor [B, W, H, C] (read with `safetensors.safe_open`
+    straight onto the device).  fold = (i, l) masks each key as the reference does — `fold_mask(path_id, ...)` with path_id the
+    shard's position in sft_paths, drawn on the device the data is on.  The bits of a mask drawn on a GPU are torch-ROCm's, not
+    CUDA's: the fold holds the same share of cells as the reference's but not the same cells.  device_id "cpu" takes the numpy
+    restatement.  Returns the reference's list of K lists."""
+    import torch
+    from safetensors import safe_open
+    host = device_id == "cpu"
+    ds = DenseSearch(w, top_k=top_k, only_pos=only_pos, keep_rows=ret_ws, scores=scores)
+    device = torch.device(device_id)
+    for path_id, sft_path in enumerate(sft_paths):
+        with safe_open(sft_path, framework="pt", device=device_id if device_id in ("cuda", "cpu") else device.index) as f:
+            for key in f.keys():
+                paths = key.split(";;")
+                data = f.get_tensor(key).to(device).half()
+                B, W, H, _ = data.shape
+                mask = None if fold is None else fold_mask(path_id, B, W * H, fold, device)
+                if host:
+                    ds.add(paths, data.numpy(), None if mask is None else mask.numpy())
+                else:
+                    ds.add(paths, data, mask)
+    return ds.result(ret_ws=ret_ws)
+
+
+def discriminative_20(result, positive_paths):
+    """`search_batch`'s d20 (doersch/doersch.py:95): per detector, how many of its first 20 entries name a path of the positive
+    set.  result: what `dense_search` returns; -> list of K ints."""
+    positive = set(positive_paths)
+    return [sum(1 for entry in entries[:20] if entry[2] in positive) for entries in result]

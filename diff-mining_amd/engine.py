@@ -52,6 +52,10 @@ SIGNATURES = {
     "dm_cluster_rank": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _sz] + [_vp] * 5),
     "dm_xray_eval_workspace_bytes": (_sz, [_i32, _i32, _i64]),
     "dm_xray_eval": (_i32, [_vp, _vp, _i32, _vp, _i32] + [_vp] * 6),
+    "dm_dense_search_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "dm_dense_search_winners": (_i32, [_vp] * 4 + [_i32] * 6 + [_vp, _sz, _vp, _vp]),
+    "dm_dense_search_topk": (_i32, [_vp] * 3 + [_i32] * 5 + [_vp] * 4),
+    "dm_dense_search_gather": (_i32, [_vp, _vp] + [_i32] * 3 + [_vp, _i32, _vp]),
     "dm_prof_enable": (_i32, [_vp, _i32]),
     "dm_measure_mfma_rate": (_i32, [_vp, _i32, _i32, _pf64, _pf64]),
     "dm_prof_read": (_i32, _PROF),

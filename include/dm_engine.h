@@ -313,6 +313,55 @@ int dm_xray_eval(const void* maps_dev, const dm_xray_desc* desc_dev, int n_rows,
                  void* work_dev, int32_t* tp_out_dev /*[n_rows][T]*/, int32_t* fp_out_dev /*[n_rows][T]*/,
                  int32_t* n_in_out_dev /*[n_rows]*/, double* box_sum_out_dev /*[n_rows]*/, void* stream);
 
+/* ---- Doersch baseline: dense detector search, winners and top-k (csrc/dense_search.hip) --------------------------
+ * The device half of `dense_search_cuda` (doersch/hog.py:124-185): every detector against every cell of every image, of which only
+ * the best cell per (detector, image) and then the best images per detector are kept.  Stream-plus-workspace functions (no engine
+ * handle); nothing synchronises the stream.
+ *
+ * dm_dense_search_winners, once per chunk of B images.  data_f16 [B][cells][C] fp16 row-major (the reference's [B, W, H, C] with
+ * cells = W H, cell i = a H + b); w_f16 [K][C] fp16; mask_u8_or_null [B][cells] uint8 or NULL.  Both fp16 pointers 16-byte aligned.
+ *   s(k, b, i) = the fp32 sum of the exact products data[b][i][c] w[k][c] (v_mfma_f32_16x16x32_f16, fp32 accumulation from +0) in
+ *     an order that depends on C alone: not on B, K, the chunk, the position in it or the other detectors of the call;
+ *   a cell whose mask byte is 0 scores +0 exactly (the reference multiplies by the mask: a masked cell beats every negative score),
+ *     unless its score is NaN, which stays NaN (NaN * 0);
+ *   the winner of (k, b) is the largest s, the lowest cell among equal values (-0 = +0); a NaN score never wins; an image without
+ *     a non-NaN cell gives (-inf, -1).
+ * score_f32 / cell_i32 are tables [K][ld] that live across chunks: this call writes column image_offset + b of every row k < K and
+ * nothing else.  work: dm_dense_search_workspace_bytes(B, cells, K) bytes (0 = bad arguments), 8-byte aligned, contents free: one
+ * packed (ordered score bits, inverted cell) key per detector and 64-cell tile, merged by an integer max.  The [cells][K] scores
+ * never reach memory; a feature row is read once.  No floating-point atomics: the same input gives the same bits on every run.
+ *
+ * dm_dense_search_topk, once after the last chunk.  Per detector k over columns [0, n_images) of the two tables: the top_k entries
+ * by descending score, ascending image among equal scores (the reference's stable `sorted(..., reverse=True)` over entries in
+ * image order).  Never admitted: -inf or NaN scores; with only_pos != 0, scores that are not > 0 (hog.py:177).  top_score_f32,
+ * top_image_i32, top_cell_i32 [K][top_k], count_i32 [K]; slots from count on hold NaN / -1 / -1.
+ *
+ * dm_dense_search_gather: pairs_i32 [n][2] = (image in the chunk, cell) on the device -> out_f16 [n][C], bit copies of
+ * data[image][cell] (the reference's `ret_ws`); a pair outside [0, B) x [0, cells) reads nothing and gives a zero row.
+ *
+ * Refused without a launch (DM_DENSE_E_*): a null pointer; B, n_images, n, cells, K or top_k < 1; K > DM_DENSE_MAX_DETECTORS;
+ * top_k > DM_DENSE_MAX_TOPK; C < 8 or C % 8 != 0 (rows are then 16-byte aligned); cells >= 2^24; image_offset < 0 or
+ * ld < image_offset + B (top-k: ld < n_images); a workspace that is too small; a misaligned pointer. */
+#define DM_DENSE_MAX_DETECTORS 128
+#define DM_DENSE_MAX_TOPK 128
+#define DM_DENSE_E_NULL 1
+#define DM_DENSE_E_IMAGES 2
+#define DM_DENSE_E_CELLS 3
+#define DM_DENSE_E_CELLS_LARGE 4
+#define DM_DENSE_E_K 5
+#define DM_DENSE_E_TOPK 6
+#define DM_DENSE_E_C 7
+#define DM_DENSE_E_LD 8
+#define DM_DENSE_E_WORK 9
+#define DM_DENSE_E_ALIGN 10
+#define DM_DENSE_E_HIP 11
+size_t dm_dense_search_workspace_bytes(int B, int cells, int K);
+int dm_dense_search_winners(void* stream, const void* data_f16, const void* w_f16, const void* mask_u8_or_null, int B, int cells, int C,
+                            int K, int image_offset, int ld, void* work, size_t work_bytes, float* score_f32, int32_t* cell_i32);
+int dm_dense_search_topk(void* stream, const float* score_f32, const int32_t* cell_i32, int K, int n_images, int ld, int top_k,
+                         int only_pos, float* top_score_f32, int32_t* top_image_i32, int32_t* top_cell_i32, int32_t* count_i32);
+int dm_dense_search_gather(void* stream, const void* data_f16, int B, int cells, int C, const int32_t* pairs_i32, int n, void* out_f16);
+
 /* Profiling support for bench.py: when enabled, every launch of the dominant (implicit-GEMM)
  * kernel is bracketed by hipEvents on the launch stream.  dm_prof_read synchronises and returns
  * the accumulated kernel milliseconds, launch count and algorithmic FLOPs since the last reset. */
