@@ -27,8 +27,9 @@ middle between two fp16 numbers.)  A masked winner shows 0.  Because the shown v
 neighbours of a list that are closer than the reference's own error can show in ascending order.  (With `fold` the reference's
 scores are float32 scalars that hold fp16 values, because its float32 mask promotes them; here the type does not depend on `fold`.)
 
-Not here: the HOG-LAB features themselves (the entry takes the cached, normalised features the reference writes), the SVM rounds,
-`accept_patch_neighbor`, the plots.
+The features themselves come from pixels by csrc/hoglab.hip (`hoglab`, `dense_search_images` below; C ABI dm_hoglab_*, DESIGN.md 4s);
+`dense_search` still takes the cached, normalised features the reference writes.  Not here: the SVM rounds, `random_sample`,
+`accept_patch_neighbor`, `filter_by_contrast`, the plots.
 """
 from __future__ import annotations
 
@@ -393,6 +394,272 @@ def dense_search(w, sft_paths, top_k: int = 50, ret_ws: bool = False, fold=None,
                     ds.add(paths, data.numpy(), None if mask is None else mask.numpy())
                 else:
                     ds.add(paths, data, mask)
+    return ds.result(ret_ws=ret_ws)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# HOG-LAB features from pixels (csrc/hoglab.hip): `get_hoglab_single` + `normalize` of doersch/hog.py:24-87
+# ------------------------------------------------------------------------------------------------------------------------------
+HOGLAB_BINS = 31                 # DM_HOGLAB_BINS
+HOGLAB_FEATURE = 2112            # DM_HOGLAB_FEATURE: 8 * 8 * 31 HOG values, then 2 * 8 * 8 Lab values
+HOGLAB_MAX_SIDE = 65535          # DM_HOGLAB_MAX_SIDE
+# DM_HOGLAB_E_* (include/dm_engine.h)
+HOGLAB_ERRORS = {1: "null argument", 2: "B < 1, or a batch of 2^23 or more workgroups", 3: f"H or W outside [64, {HOGLAB_MAX_SIDE}]",
+                 4: "2^24 or more blocks per image", 5: "workspace too small", 6: "misaligned pointer", 7: "HIP error"}
+_XYZ_FROM_RGB = ((0.412453, 0.357580, 0.180423), (0.212671, 0.715160, 0.072169), (0.019334, 0.119193, 0.950227))
+_WHITE_D65_2 = (0.95047, 1.0, 1.08883)
+_bin_table = None
+_bin_table_dev = {}
+
+
+def _check_hoglab(rc: int, what: str):
+    if rc:
+        raise EngineError(f"{what}: {HOGLAB_ERRORS.get(rc, 'error')} (code {rc})")
+
+
+def hoglab_bin_table():
+    """uint8 [511, 511], entry [g_row + 255, g_col + 255] = the orientation bin of an integer gradient, by skimage's rule in fp64:
+    o = rad2deg(arctan2(g_row, g_col)) % 180, bin i iff (180.0 / 31) i <= o < (180.0 / 31) (i + 1).  Read-only, built once.  The
+    kernels and `hoglab_host` both bin by this table: integer gradients come as close as 3e-6 degrees to a bin edge, which fp32
+    arctan2 does not resolve."""
+    global _bin_table
+    if _bin_table is None:
+        g = np.arange(-255, 256, dtype=np.float64)
+        o = np.rad2deg(np.arctan2(g[:, None], g[None, :])) % 180
+        per = 180.0 / HOGLAB_BINS
+        t = np.full(o.shape, 255, dtype=np.uint8)
+        for i in range(HOGLAB_BINS):
+            t[(per * i <= o) & (o < per * (i + 1))] = i
+        if t.max() >= HOGLAB_BINS:
+            raise AssertionError("hoglab: an integer gradient without a bin")
+        t.setflags(write=False)
+        _bin_table = t
+    return _bin_table
+
+
+def _hoglab_image(image):
+    image = np.asarray(image)
+    if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3:
+        raise ValueError(f"hoglab: an image must be uint8 [H, W, 3], got {image.dtype} {image.shape}")
+    H, W = image.shape[:2]
+    if not (64 <= H <= HOGLAB_MAX_SIDE and 64 <= W <= HOGLAB_MAX_SIDE):
+        raise ValueError(f"hoglab: {H} x {W} pixels, sides must lie in [64, {HOGLAB_MAX_SIDE}]")
+    if (H // 8 - 7) * (W // 8 - 7) >= DENSE_MAX_CELLS:
+        raise ValueError(f"hoglab: {H} x {W} pixels give 2^24 or more blocks")
+    return image
+
+
+def hoglab_shape(H: int, W: int):
+    """(bc, br) = (W // 8 - 7, H // 8 - 7): the first two dimensions of one image's features (block column first)."""
+    return W // 8 - 7, H // 8 - 7
+
+
+def _lab_ab(rgb_u8, dt):
+    """(a, b) of skimage's rgb2lab (D65, 2 degree observer) of uint8 pixels [..., 3], every operation in `dt`."""
+    x = rgb_u8.astype(dt) / dt(255)
+    lin = np.where(x > dt(0.04045), ((x + dt(0.055)) / dt(1.055)) ** dt(2.4), x / dt(12.92))
+    xyz = lin @ np.array(_XYZ_FROM_RGB, dtype=dt).T
+    xyz = xyz / np.array(_WHITE_D65_2, dtype=dt)
+    f = np.where(xyz > dt(0.008856), np.cbrt(xyz), dt(7.787) * xyz + dt(16.0 / 116.0))
+    return dt(500) * (f[..., 0] - f[..., 1]), dt(200) * (f[..., 1] - f[..., 2])
+
+
+def hoglab_cells_host(image, dtype=np.float64):
+    """Stage one in numpy: image uint8 [H, W, 3] -> (hog cells `dtype` [nr, nc, 31], lab cells `dtype` [2, nr, nc]); nr = H // 8,
+    nc = W // 8.  Gradients, the channel choice and the bin are integer work; magnitudes, sums and Lab run in `dtype`."""
+    image = _hoglab_image(image)
+    dt = np.dtype(dtype).type
+    H, W = image.shape[:2]
+    nr, nc = H // 8, W // 8
+    I = image.astype(np.int32)
+    g_row, g_col = np.zeros_like(I), np.zeros_like(I)
+    g_row[1:-1] = I[2:] - I[:-2]
+    g_col[:, 1:-1] = I[:, 2:] - I[:, :-2]
+    m2 = g_row * g_row + g_col * g_col
+    ch = m2.argmax(axis=2)[..., None]                                          # the lowest channel among equal magnitudes
+    g_row, g_col, m2 = (np.take_along_axis(a, ch, 2)[:8 * nr, :8 * nc, 0] for a in (g_row, g_col, m2))
+    mag = np.sqrt(m2.astype(dt))
+    bins = hoglab_bin_table()[g_row + 255, g_col + 255]
+    hist = np.zeros((nr, nc, HOGLAB_BINS), dtype=dt)
+    for i in range(HOGLAB_BINS):
+        hist[:, :, i] = np.where(bins == i, mag, dt(0)).reshape(nr, 8, nc, 8).sum(axis=(1, 3), dtype=dt)
+    hist = hist / dt(64)
+    rows = (8 * np.arange(nr)[:, None] + np.array([3, 4])).reshape(-1)
+    cols = (8 * np.arange(nc)[:, None] + np.array([3, 4])).reshape(-1)
+    ab = np.stack(_lab_ab(image[rows][:, cols], dt)).reshape(2, nr, 2, nc, 2)
+    lab = ((ab[:, :, 0, :, 0] + ab[:, :, 0, :, 1]) + (ab[:, :, 1, :, 0] + ab[:, :, 1, :, 1])) * dt(0.25)
+    return hist, lab
+
+
+def hoglab_blocks_host(hog_cells, lab_cells, normalized=True):
+    """Stage two in numpy, in the dtype of the maps: cell maps -> [bc, br, 2112]; L2-Hys (eps 1e-5, clip 0.2) on the 8 x 8 x 31
+    HOG values of a block, ((a, b) + 128) / 255 of its 64 cells, and with `normalized` the division by the norm over all 2112."""
+    from numpy.lib.stride_tricks import sliding_window_view
+    dt = hog_cells.dtype.type
+    nr, nc = hog_cells.shape[:2]
+    br, bc = nr - 7, nc - 7
+    eps2 = dt(1e-5) * dt(1e-5)
+    v = sliding_window_view(hog_cells, (8, 8), axis=(0, 1)).transpose(0, 1, 3, 4, 2).reshape(br, bc, 64 * HOGLAB_BINS)
+    v = v / np.sqrt((v * v).sum(-1, keepdims=True) + eps2)
+    v = np.minimum(v, dt(0.2))
+    v = v / np.sqrt((v * v).sum(-1, keepdims=True) + eps2)
+    l = sliding_window_view(lab_cells, (8, 8), axis=(1, 2)).transpose(1, 2, 0, 3, 4).reshape(br, bc, 128)
+    x = np.concatenate([v, (l + dt(128)) / dt(255)], axis=-1)
+    if normalized:
+        x = x / np.sqrt((x * x).sum(-1, keepdims=True))
+    return np.ascontiguousarray(x.transpose(1, 0, 2))
+
+
+def hoglab_host(image, normalized=True, dtype=np.float64):
+    """The numpy restatement of `get_hoglab_single` (normalized=False: what the reference's .npy cache holds) and of
+    `normalize(get_hoglab_single(...))` (normalized=True: what the search reads, before the fp16 cast): image uint8 [H, W, 3] ->
+    `dtype` [bc, br, 2112].  With dtype=np.float32 every floating-point operation runs in fp32."""
+    return hoglab_blocks_host(*hoglab_cells_host(image, dtype), normalized=normalized)
+
+
+def _hoglab_batch(images):
+    images = np.asarray(images)
+    if images.ndim == 3:
+        images = images[None]
+    if images.ndim != 4 or images.shape[0] < 1:
+        raise ValueError(f"hoglab: images must be uint8 [B, H, W, 3], got {images.shape}")
+    return images
+
+
+def hoglab_workspace_bytes(B: int, H: int, W: int) -> int:
+    need = _lib().dm_hoglab_workspace_bytes(int(B), int(H), int(W))
+    if not need:
+        raise ValueError(f"hoglab: no workspace for {B} images of {H} x {W} pixels")
+    return need
+
+
+def _hoglab_device_args(images):
+    import torch
+    if not (isinstance(images, torch.Tensor) and images.is_cuda):
+        raise EngineError("hoglab: images must be a uint8 torch tensor on the GPU, or numpy for the host restatement")
+    if images.ndim == 3:
+        images = images[None]
+    if images.dtype != torch.uint8 or images.ndim != 4 or images.shape[3] != 3 or images.shape[0] < 1:
+        raise ValueError(f"hoglab: images must be uint8 [B, H, W, 3], got {images.dtype} {tuple(images.shape)}")
+    images = images.contiguous()
+    dev = images.device
+    key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
+    if key not in _bin_table_dev:
+        _bin_table_dev[key] = torch.from_numpy(hoglab_bin_table().copy()).to(dev)
+    return torch, images, dev, _bin_table_dev[key]
+
+
+def hoglab_cells(images):
+    """dm_hoglab_cells on the current stream: uint8 [B, H, W, 3] on the GPU -> device tensors (hog cells fp32 [B, nr, nc, 31], lab
+    cells fp32 [B, 2, nr, nc]).  A numpy input takes `hoglab_cells_host` per image (fp64 arithmetic, fp32 result)."""
+    if isinstance(images, np.ndarray):
+        maps = [hoglab_cells_host(im) for im in _hoglab_batch(images)]
+        return np.stack([m[0] for m in maps]).astype(np.float32), np.stack([m[1] for m in maps]).astype(np.float32)
+    torch, images, dev, bins = _hoglab_device_args(images)
+    B, H, W, _ = images.shape
+    hoglab_workspace_bytes(B, H, W)                      # the shape check
+    hog = torch.empty((B, H // 8, W // 8, HOGLAB_BINS), dtype=torch.float32, device=dev)
+    lab = torch.empty((B, 2, H // 8, W // 8), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib().dm_hoglab_cells(_stream(torch, dev), _p(images), B, H, W, _p(bins), _p(hog), _p(lab))
+    _check_hoglab(rc, "dm_hoglab_cells")
+    return hog, lab
+
+
+def hoglab_features(images, normalized=True, raw=False, work=None):
+    """dm_hoglab_features on the current stream: uint8 [B, H, W, 3] on the GPU -> (fp16 [B, bc, br, 2112] or None, fp32 of the same
+    shape or None): the normalised features the search reads and / or the raw ones `get_hoglab_single` returns.  work: a uint8
+    workspace of at least `hoglab_workspace_bytes(B, H, W)` to reuse."""
+    if not (normalized or raw):
+        raise ValueError("hoglab: neither output asked for")
+    torch, images, dev, bins = _hoglab_device_args(images)
+    B, H, W, _ = images.shape
+    need = hoglab_workspace_bytes(B, H, W)
+    if work is None:
+        work = torch.empty(need, dtype=torch.uint8, device=dev)
+    bc, br = hoglab_shape(H, W)
+    out = torch.empty((B, bc, br, HOGLAB_FEATURE), dtype=torch.float16, device=dev) if normalized else None
+    rawt = torch.empty((B, bc, br, HOGLAB_FEATURE), dtype=torch.float32, device=dev) if raw else None
+    with torch.cuda.device(dev):
+        rc = _lib().dm_hoglab_features(_stream(torch, dev), _p(images), B, H, W, _p(bins), _p(out), _p(rawt), _p(work),
+                                       work.numel() * work.element_size())
+    _check_hoglab(rc, "dm_hoglab_features")
+    return out, rawt
+
+
+def hoglab(images, normalized=True):
+    """HOG-LAB features of a batch of same-sized images: uint8 [B, H, W, 3] on the GPU -> fp16 [B, bc, br, 2112] (normalized: ready
+    for `DenseSearch.add`) or fp32 of the same shape (normalized=False: the raw features).  A numpy input takes `hoglab_host` per
+    image and gives numpy arrays of the same types."""
+    if isinstance(images, np.ndarray):
+        x = np.stack([hoglab_host(im, normalized=normalized) for im in _hoglab_batch(images)])
+        return x.astype(np.float16) if normalized else x.astype(np.float32)
+    out, raw = hoglab_features(images, normalized=normalized, raw=not normalized)
+    return out if normalized else raw
+
+
+def read_images(paths):
+    """The images of `paths` as the reference's `imread` delivers them for 8-bit RGB JPEG / PNG files: PIL, `convert("RGB")`, no
+    resize.  (A grey or RGBA file comes out of `imread` with another shape, on which the reference's `hog(channel_axis=-1)` fails
+    or treats alpha as a colour; here it is converted to RGB.)  -> [(indices into paths, uint8 [n, H, W, 3]), ...], one entry per
+    image size in order of first appearance."""
+    from PIL import Image
+    groups = {}
+    for j, path in enumerate(paths):
+        with Image.open(path) as im:
+            a = np.asarray(im.convert("RGB"), dtype=np.uint8)
+        groups.setdefault(a.shape, ([], []))
+        groups[a.shape][0].append(j)
+        groups[a.shape][1].append(a)
+    return [(idx, np.stack(arrs)) for idx, arrs in groups.values()]
+
+
+def detector_from_patch(features, bbox):
+    """The reference's initial detector of a patch (doersch/doersch.py:337): `normalize(feat)[bbox[0] // 8, bbox[1] // 8]`, the row
+    of the NORMALISED features [bc, br, C] (or [1, bc, br, C]) of the patch's image at block (bbox[0] // 8, bbox[1] // 8) — what
+    `hoglab(image)` gives.  Device features: one row by dm_dense_search_gather -> fp16 [C] on the device; numpy: a copy of the row."""
+    if features.ndim == 4 and features.shape[0] == 1:
+        features = features[0]
+    if features.ndim != 3:
+        raise ValueError(f"detector_from_patch: features of ONE image [bc, br, C], got {tuple(features.shape)}")
+    bc, br, C_ = features.shape
+    a, b = int(bbox[0]) // 8, int(bbox[1]) // 8
+    if not (0 <= a < bc and 0 <= b < br):
+        raise ValueError(f"detector_from_patch: bbox {tuple(bbox)} outside {bc} x {br} blocks")
+    if isinstance(features, np.ndarray):
+        return features[a, b].copy()
+    import torch
+    pairs = torch.tensor([[0, a * br + b]], dtype=torch.int32, device=features.device)
+    return gather(features.contiguous().view(1, bc * br, C_), pairs)[0]
+
+
+def dense_search_images(w, image_paths, top_k: int = 50, ret_ws: bool = False, fold=None, only_pos: bool = False, batch: int = 16,
+                        device_id: str = "cuda", scores: str = "f16"):
+    """`dense_search`, fed from image files instead of the reference's feature shards: per batch of `batch` paths the images are
+    read (`read_images`), their features computed on the device (`hoglab`) and handed to `DenseSearch.add` — no cache, no
+    safetensors, no skimage.  Images of a batch that differ in size are added size by size (order of first appearance), so with
+    mixed sizes the image order that breaks score ties is that order.  fold = (i, l): `fold_mask(path_id, ...)` with path_id = the
+    batch's index, drawn on the device the features are on, once per size group: every group of a batch reseeds with the same
+    path_id, so the masks of two size groups of one batch come from the same permutation stream and are correlated (equal where the
+    cell counts are equal).  The reference's batches hold one size, where this is its own draw.  device_id "cpu" takes the numpy
+    restatements.
+    Returns what `dense_search` returns."""
+    import torch
+    if batch < 1:
+        raise ValueError(f"dense search: batch {batch}")
+    host = device_id == "cpu"
+    ds = DenseSearch(w, top_k=top_k, only_pos=only_pos, keep_rows=ret_ws, scores=scores)
+    device = torch.device(device_id)
+    image_paths = list(image_paths)
+    for path_id, at in enumerate(range(0, len(image_paths), batch)):
+        names = image_paths[at:at + batch]
+        for idx, images in read_images(names):
+            data = hoglab(images) if host else hoglab(torch.from_numpy(images).to(device))
+            B, W_, H_, _ = data.shape
+            mask = None if fold is None else fold_mask(path_id, B, W_ * H_, fold, device)
+            if host and mask is not None:
+                mask = mask.numpy()
+            ds.add([names[j] for j in idx], data, mask)
     return ds.result(ret_ws=ret_ws)
 
 

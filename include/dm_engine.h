@@ -362,6 +362,47 @@ int dm_dense_search_topk(void* stream, const float* score_f32, const int32_t* ce
                          int only_pos, float* top_score_f32, int32_t* top_image_i32, int32_t* top_cell_i32, int32_t* count_i32);
 int dm_dense_search_gather(void* stream, const void* data_f16, int B, int cells, int C, const int32_t* pairs_i32, int n, void* out_f16);
 
+/* ---- Doersch baseline: HOG-LAB features from pixels (csrc/hoglab.hip) ------------------------------------------------
+ * `get_hoglab_single` + `normalize` of doersch/hog.py:24-87 on the device: B RGB uint8 images [B][H][W][3] of one size -> per image
+ * the [bc][br][2112] tensor the dense search reads (nr = H / 8, nc = W / 8 cells of 8 x 8 pixels, br = nr - 7, bc = nc - 7 blocks of
+ * 8 x 8 cells; block COLUMN first, cell = q br + p).  A feature is 1984 HOG values (skimage.feature.hog: 31 orientations, unsigned
+ * gradients, no interpolation, L2-Hys) followed by 128 Lab values ((a, b) of rgb2lab at the centres of the block's 64 cells).
+ * Stream-plus-workspace functions (no engine handle); nothing synchronises the stream; no atomics: every float sum runs in a fixed
+ * order, so an image gives the same bits on every run, alone or at any position of any batch, whichever outputs are asked for.
+ *
+ * dm_hoglab_bin_table (host only, needs no GPU): fills uint8 [511][511], entry (g_row + 255) 511 + (g_col + 255) = the orientation
+ * bin of the integer gradient (g_row, g_col): o = fmod(atan2(g_row, g_col) 180 / pi, 180) made non-negative, in fp64; bin i holds o iff
+ * (180.0 / 31) i <= o < (180.0 / 31) (i + 1).  The kernels take the bin from this table on the device (`bins`): fp32 atan2 places
+ * integer gradients that lie 3e-6 degrees from a bin edge on the wrong side.
+ * dm_hoglab_cells: the first kernel alone.  hog_cells fp32 [B][nr][nc][31]: per cell and bin the sum of the gradient magnitudes of
+ * the cell's pixels in that bin / 64 (per pixel the channel of the largest g_row^2 + g_col^2, the lowest among equals; the sum in
+ * ascending pixel order in fp64, rounded once).  lab_cells fp32 [B][2][nr][nc]: (a, b) averaged over pixels (8R+3..4, 8C+3..4).
+ * dm_hoglab_features: both kernels.  work: dm_hoglab_workspace_bytes(B, H, W) bytes (0 = bad arguments), contents free (the two cell
+ * maps).  out_f16 [B][bc][br][2112] fp16: feature / its L2 norm over the 2112 values; raw_f32, same shape, fp32: the feature before
+ * that division; either may be NULL, not both.
+ *
+ * Refused without a launch (DM_HOGLAB_E_*): a null required pointer; B < 1, or a batch whose one-dimensional grid would reach 2^23
+ * workgroups (grid x block stays below 2^32 threads: 33.5 million cells, 8192 images of 512 x 512); H or W below 64 or
+ * above DM_HOGLAB_MAX_SIDE (every pixel, cell and block coordinate then fits 16 bits; offsets are 64-bit throughout); more than
+ * 2^24 - 1 blocks per image (the search's limit); a workspace that is too small; images / bins are read by bytes and need no
+ * alignment, out_f16 / raw_f32 / work must be 16-byte aligned, hog_cells / lab_cells 4-byte aligned. */
+#define DM_HOGLAB_MAX_SIDE 65535
+#define DM_HOGLAB_BINS 31
+#define DM_HOGLAB_FEATURE 2112
+#define DM_HOGLAB_E_NULL 1
+#define DM_HOGLAB_E_BATCH 2
+#define DM_HOGLAB_E_SIDE 3
+#define DM_HOGLAB_E_BLOCKS 4
+#define DM_HOGLAB_E_WORK 5
+#define DM_HOGLAB_E_ALIGN 6
+#define DM_HOGLAB_E_HIP 7
+int dm_hoglab_bin_table(void* host_u8_511x511);
+size_t dm_hoglab_workspace_bytes(int B, int H, int W);
+int dm_hoglab_cells(void* stream, const void* images_u8, int B, int H, int W, const void* bins_u8, float* hog_cells_f32,
+                    float* lab_cells_f32);
+int dm_hoglab_features(void* stream, const void* images_u8, int B, int H, int W, const void* bins_u8, void* out_f16_or_null,
+                       float* raw_f32_or_null, void* work, size_t work_bytes);
+
 /* Profiling support for bench.py: when enabled, every launch of the dominant (implicit-GEMM)
  * kernel is bracketed by hipEvents on the launch stream.  dm_prof_read synchronises and returns
  * the accumulated kernel milliseconds, launch count and algorithmic FLOPs since the last reset. */
