@@ -28,8 +28,43 @@ neighbours of a list that are closer than the reference's own error can show in 
 scores are float32 scalars that hold fp16 values, because its float32 mask promotes them; here the type does not depend on `fold`.)
 
 The features themselves come from pixels by csrc/hoglab.hip (`hoglab`, `dense_search_images` below; C ABI dm_hoglab_*, DESIGN.md 4s);
-`dense_search` still takes the cached, normalised features the reference writes.  Not here: the SVM rounds, `random_sample`,
-`accept_patch_neighbor`, `filter_by_contrast`, the plots.
+`dense_search` still takes the cached, normalised features the reference writes.
+
+Between two searches the baseline fits one linear SVM per detector (`train_svm`, doersch/doersch.py:66-79: scikit-learn's
+`SVC(C=0.1, kernel='linear')` on 5 positives and 10 000 - 25 000 negatives) and mines hard negatives.  Kernels: csrc/svm.hip; C ABI:
+dm_svm_workspace_bytes / _fit / _hard_negatives; here `train_svms`, `train_svm`, `svm_round`, `sample_negatives`
+(`random_sample`, hog.py:187-212).  The pin is scikit-learn's own iterate, not "an SVM optimum": at tol 1e-3 libsvm stops after a few
+dozen steps, 6 - 35 % (rel-L2) short of the optimum.  The rules, which `svm_fit_host` (numpy) and the kernels share:
+
+  problem   one detector: n_pos >= 1 rows labelled +1, then n_neg >= 1 rows labelled -1; fp16 rows, converted exactly; cost C
+            (0.1), eps 1e-3, max_iter = libsvm's max(10 000 000, 100 n) unless given.
+  order     libsvm sees the classes in ascending order: the negatives first, in their own order, as y = +1, then the positives as
+            y = -1.  Ties are broken in that order; the sign is flipped at the end: w = -sum alpha_t y_t x_t, b = rho.
+  state     alpha = 0 and G = -1 in fp64; QD[t] = x_t . x_t in fp64; Q_i[t] = (float)(y_i y_t (x_i . x_t)): libsvm's Qfloat is fp32
+            and that rounding is part of the trajectory.  A dot is the sum of the exact products of the fp16 values in fp64 in a
+            fixed order that depends on the feature count alone: lane l of 64 adds the products of the 8-feature chunks l, l + 64,
+            ... one by one, then the 64 partials meet in an xor tree (`_svm_dots`).
+  select i  the largest of -G[t] over y = +1 rows below the upper bound and G[t] over y = -1 rows above the lower bound; the LAST
+            index among equals (libsvm compares with >=).
+  select j  over y = +1 rows above the lower bound and y = -1 rows below the upper bound: grad_diff = Gmax + G[t] (y = +1) or
+            Gmax - G[t] (y = -1); Gmax2 = the largest G[t] (y = +1) or -G[t] (y = -1); among those with grad_diff > 0 the lowest
+            -grad_diff^2 / quad, quad = QD[i] + QD[t] - 2 y_i y_t Q_i[t], 1e-12 where that is not > 0; the LAST index among equals
+            (libsvm compares with <=).
+  stop      iter >= max_iter (status 1), else Gmax + Gmax2 < eps or no j (status 0).
+  update    libsvm's two-variable update with its four clipping branches (Solver::Solve, one C for both classes), then
+            G[t] += Q_i[t] d_alpha_i + Q_j[t] d_alpha_j in fp64 without fused multiply-add.
+  rho       the mean of y_t G[t] over the free variables, summed in index order; with none free, the midpoint of libsvm's ub / lb.
+  w         over the support vectors in ascending index, in fp64.
+  shrinking not restated: the trajectory is SVC(shrinking=False)'s, which equals the default's at least while n_iter < min(n, 1000)
+            (libsvm's first shrinking step); tests/golden/svm_ref.npz records per case whether it does.
+  hard neg. over rows first = n_pos + n_hn ... n - 1 only: s = x . w + b in fp64 over all features in the fixed order (its own
+            pass: y (G + 1) would carry the fp32 rounding of Q); admitted: s > 0; descending s, ascending position among equals (the
+            reference's argsort leaves ties open); at most max_samples, as positions in the detector's sample list.
+  refused   NaN / inf rows (status 2, w = NaN; the wrapper raises ValueError as scikit-learn does); n_pos < 1 or n_neg < 1; more
+            than 128 detectors; a feature count below 8, above 8192 (the score pass stages w in 64 KB of LDS) or not a multiple of 8;
+            n >= 2^24.
+
+Not here: `accept_patch_neighbor`, `filter_by_contrast`, the plots.
 """
 from __future__ import annotations
 
@@ -668,3 +703,465 @@ def discriminative_20(result, positive_paths):
     set.  result: what `dense_search` returns; -> list of K ints."""
     positive = set(positive_paths)
     return [sum(1 for entry in entries[:20] if entry[2] in positive) for entries in result]
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the detectors' SVMs (csrc/svm.hip; DESIGN.md 4t): `train_svm` of doersch/doersch.py:66-79 and `random_sample` of hog.py:187-212
+# ------------------------------------------------------------------------------------------------------------------------------
+SVM_MAX_DETECTORS = 128          # DM_SVM_MAX_DETECTORS
+SVM_MAX_FEATURES = 8192          # DM_SVM_MAX_FEATURES
+SVM_MAX_SAMPLES = 1 << 24        # n >= 2^24 is refused
+SVM_CONVERGED, SVM_MAX_ITER, SVM_NAN, SVM_BAD_LIST = 0, 1, 2, 3          # DM_SVM_* status
+SVM_TAU = 1e-12                  # libsvm's TAU
+# DM_SVM_E_* (include/dm_engine.h)
+SVM_ERRORS = {1: "null argument", 2: f"K outside [1, {SVM_MAX_DETECTORS}]", 3: f"C < 8, not a multiple of 8 or above {SVM_MAX_FEATURES}",
+              4: "R < 1", 5: "ld < 2", 6: "ld >= 2^24", 7: "cost or eps not > 0", 8: "workspace too small", 9: "misaligned pointer",
+              10: "HIP error"}
+
+
+def _check_svm(rc: int, what: str):
+    if rc:
+        raise EngineError(f"{what}: {SVM_ERRORS.get(rc, 'error')} (code {rc})")
+
+
+def _check_svm_shape(n, n_pos, C_, K=1):
+    if not 1 <= K <= SVM_MAX_DETECTORS:
+        raise ValueError(f"svm: {K} detectors, need 1 ... {SVM_MAX_DETECTORS}")
+    if C_ < 8 or C_ % 8 or C_ > SVM_MAX_FEATURES:
+        raise ValueError(f"svm: {C_} features, need a multiple of 8 in [8, {SVM_MAX_FEATURES}] (2112 = 8 * 264)")
+    if n >= SVM_MAX_SAMPLES:
+        raise ValueError(f"svm: {n} samples, 2^24 or more")
+    if n_pos < 1 or n - n_pos < 1:
+        raise ValueError(f"svm: {n_pos} positives and {n - n_pos} negatives, need at least one of each")
+
+
+def _svm_default_max_iter(n: int) -> int:
+    return max(10_000_000, 100 * n)
+
+
+def _svm_dots(Z, x):
+    """The kernels' dot: Z float64 [n, C] times x float64 [C] (or row by row, [n, C]) -> [n].  Lane l of 64 adds the products of the
+    8-feature chunks l, l + 64, ... one by one in ascending order, then the 64 partials meet in an xor tree (32, 16, ... 1)."""
+    n, C_ = Z.shape
+    J = -(-(C_ // 8) // 64)
+    lanes = np.arange(64)
+    out = np.empty(n)
+    for r0 in range(0, n, 1024):
+        Zr = Z[r0:r0 + 1024]
+        P = np.zeros((len(Zr), J * 512))
+        P[:, :C_] = Zr * (x if x.ndim == 1 else x[r0:r0 + 1024])
+        P = P.reshape(len(Zr), J, 64, 8)
+        a = np.zeros((len(Zr), 64))
+        for j in range(J):
+            for e in range(8):
+                a = a + P[:, j, :, e]
+        for o in (32, 16, 8, 4, 2, 1):
+            a = a + a[:, lanes ^ o]
+        out[r0:r0 + 1024] = a[:, 0]
+    return out
+
+
+def svm_fit_host(X, n_pos: int, C: float = 0.1, tol: float = 1e-3, max_iter: int = -1, trace=None):
+    """The numpy restatement of SVC(C=C, kernel='linear', tol=tol, shrinking=False).fit(X, [1] * n_pos + [-1] * (n - n_pos)) by the
+    rules at the top of this module: X fp16 [n, C] -> (w float64 [C], b float, n_iter int, alpha float64 [n] in the order of X's
+    rows, status).  Raises ValueError on a NaN or an infinity, as scikit-learn does.  trace(n_iter, "i" or "j", values, chosen) sees
+    every selection step: the candidates' values in libsvm's order (-inf: no candidate; the largest wins) and the index chosen."""
+    X = np.asarray(X)
+    if X.dtype != np.float16 or X.ndim != 2:
+        raise ValueError(f"svm: X must be float16 [n, C], got {X.dtype} {X.shape}")
+    n, C_ = X.shape
+    n_pos = int(n_pos)
+    _check_svm_shape(n, n_pos, C_)
+    cost, eps = float(C), float(tol)
+    if not (cost > 0 and eps > 0):
+        raise ValueError(f"svm: C {C} and tol {tol} must be positive")
+    if not np.isfinite(X).all():
+        raise ValueError("svm: X contains NaN or infinity")
+    max_iter = _svm_default_max_iter(n) if max_iter <= 0 else int(max_iter)
+    n_neg = n - n_pos
+    Z = np.concatenate([X[n_pos:], X[:n_pos]]).astype(np.float64)          # libsvm's order: the negatives as y = +1, the positives as -1
+    y = np.concatenate([np.ones(n_neg), -np.ones(n_pos)])
+    pos_y = y > 0
+    alpha, G = np.zeros(n), -np.ones(n)
+    QD = _svm_dots(Z, Z)
+    cache = {}
+
+    def column(i):
+        if i not in cache:
+            cache[i] = (y[i] * y * _svm_dots(Z, Z[i])).astype(np.float32)
+        return cache[i]
+
+    def last_argmax(v):
+        return n - 1 - int(np.argmax(v[::-1]))
+
+    n_iter, status = 0, SVM_CONVERGED
+    while True:
+        if n_iter >= max_iter:
+            status = SVM_MAX_ITER
+            break
+        up = np.where(pos_y, alpha < cost, alpha > 0)                      # candidates for i
+        if not up.any():
+            break
+        viol = np.where(up, np.where(pos_y, -G, G), -np.inf)
+        i = last_argmax(viol)
+        Gmax = viol[i]
+        if trace is not None:
+            trace(n_iter, "i", viol, i)
+        Qi = column(i)
+        low = np.where(pos_y, alpha > 0, alpha < cost)                     # candidates for j
+        if not low.any():
+            break
+        Gmax2 = np.where(low, np.where(pos_y, G, -G), -np.inf).max()
+        grad_diff = np.where(pos_y, Gmax + G, Gmax - G)
+        quad = QD[i] + QD - 2.0 * (y[i] * y) * Qi.astype(np.float64)
+        quad = np.where(quad > 0, quad, SVM_TAU)
+        ok = low & (grad_diff > 0)
+        if Gmax + Gmax2 < eps or not ok.any():
+            break
+        gain = np.where(ok, (grad_diff * grad_diff) / quad, -np.inf)
+        j = last_argmax(gain)                                              # the lowest -grad_diff^2 / quad, the last among equals
+        if trace is not None:
+            trace(n_iter, "j", gain, j)
+        n_iter += 1
+        Qj = column(j)
+        ai, aj = alpha[i], alpha[j]
+        if y[i] != y[j]:
+            q = QD[i] + QD[j] + 2.0 * float(Qi[j])
+            if q <= 0:
+                q = SVM_TAU
+            delta = (-G[i] - G[j]) / q
+            diff = ai - aj
+            ai, aj = ai + delta, aj + delta
+            if diff > 0:
+                if aj < 0:
+                    aj, ai = 0.0, diff
+            elif ai < 0:
+                ai, aj = 0.0, -diff
+            if diff > 0:                                                   # C_i - C_j = 0
+                if ai > cost:
+                    ai, aj = cost, cost - diff
+            elif aj > cost:
+                aj, ai = cost, cost + diff
+        else:
+            q = QD[i] + QD[j] - 2.0 * float(Qi[j])
+            if q <= 0:
+                q = SVM_TAU
+            delta = (G[i] - G[j]) / q
+            total = ai + aj
+            ai, aj = ai - delta, aj + delta
+            if total > cost:
+                if ai > cost:
+                    ai, aj = cost, total - cost
+            elif aj < 0:
+                aj, ai = 0.0, total
+            if total > cost:
+                if aj > cost:
+                    aj, ai = cost, total - cost
+            elif ai < 0:
+                ai, aj = 0.0, total
+        dai, daj = ai - alpha[i], aj - alpha[j]
+        alpha[i], alpha[j] = ai, aj
+        G = G + (Qi.astype(np.float64) * dai + Qj.astype(np.float64) * daj)
+    upper, lower = alpha >= cost, alpha <= 0
+    free = ~upper & ~lower
+    yG = y * G
+    if free.any():
+        s = 0.0
+        for v in yG[free]:
+            s += float(v)
+        rho = s / int(free.sum())
+    else:
+        ub_set = (upper & ~pos_y) | (lower & ~upper & pos_y)
+        lb_set = (upper & pos_y) | (lower & ~upper & ~pos_y)
+        ub = yG[ub_set].min() if ub_set.any() else np.inf
+        lb = yG[lb_set].max() if lb_set.any() else -np.inf
+        rho = (ub + lb) / 2
+    w = np.zeros(C_)
+    for t in np.flatnonzero(alpha > 0):
+        w = w - (alpha[t] * y[t]) * Z[t]
+    return w, float(rho), n_iter, np.concatenate([alpha[n_neg:], alpha[:n_neg]]), status
+
+
+def hard_negatives_host(X, w, b, first: int, max_samples: int):
+    """doersch.py:75-78 by the rules at the top of this module: X fp16 [n, C] -> (positions int64 [count] in X, score float64
+    [n - first] of rows first ... n - 1)."""
+    X = np.asarray(X)
+    first = int(first)
+    if X.dtype != np.float16 or X.ndim != 2 or not 0 <= first <= len(X):
+        raise ValueError(f"svm: X must be float16 [n, C] and first in [0, n], got {X.dtype} {X.shape}, {first}")
+    s = _svm_dots(X[first:].astype(np.float64), np.asarray(w, dtype=np.float64)) + float(b)
+    idx = np.flatnonzero(s > 0)
+    idx = idx[np.argsort(-s[idx], kind="stable")][:max(int(max_samples), 0)]
+    return idx + first, s
+
+
+def svm_workspace_bytes(K: int, ld: int) -> int:
+    need = _lib().dm_svm_workspace_bytes(int(K), int(ld))
+    if not need:
+        raise ValueError(f"svm: no workspace for {K} detectors of up to {ld} samples")
+    return need
+
+
+def _svm_counts(K, ld, **named):
+    """Per-detector counts as int64 numpy [K]: an int stands for every detector; a device tensor is read back."""
+    out = []
+    for name, v in named.items():
+        v = v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)
+        v = np.broadcast_to(v, (K,)) if v.ndim == 0 else v
+        if v.shape != (K,) or not np.issubdtype(v.dtype, np.integer):
+            raise ValueError(f"svm: {name} must be an int or {K} ints, got {v.dtype} {v.shape}")
+        out.append(v.astype(np.int64))
+    return out
+
+
+def _svm_table(pool, table):
+    if pool.ndim != 2 or table.ndim != 2:
+        raise ValueError(f"svm: pool must be [R, C] and table [K, ld], got {tuple(pool.shape)} and {tuple(table.shape)}")
+    (R, C_), (K, ld) = pool.shape, table.shape
+    _check_svm_shape(2, 1, C_, K)
+    if R < 1 or ld < 2:
+        raise ValueError(f"svm: a pool of {R} rows and a table of {ld} columns")
+    if ld >= SVM_MAX_SAMPLES:
+        raise ValueError(f"svm: {ld} samples, 2^24 or more")
+    return R, C_, K, ld
+
+
+def _svm_device_args(pool, table):
+    import torch
+    if not (isinstance(pool, torch.Tensor) and pool.is_cuda):
+        raise EngineError("svm: pool must be a float16 torch tensor on the GPU, or numpy for the host restatement")
+    if pool.dtype != torch.float16:
+        raise ValueError("svm: pool must be float16")
+    dev = pool.device
+    table = torch.as_tensor(table).to(device=dev, dtype=torch.int32).contiguous()
+    return torch, pool.contiguous(), table, dev
+
+
+def svm_fit(pool, table, n, n_pos, C: float = 0.1, tol: float = 1e-3, max_iter: int = -1, work=None, want_alpha: bool = False):
+    """dm_svm_fit on the current stream: pool fp16 [R, C] and table int32 [K, ld] on the GPU, n / n_pos ints or [K] -> device tensors
+    (w float64 [K, C], b float64 [K], n_iter int32 [K], status int32 [K], alpha float64 [K, ld] or None).  Does not raise on a
+    status; `train_svms` does.  Synchronises the stream."""
+    torch, pool, table, dev = _svm_device_args(pool, table)
+    R, C_, K, ld = _svm_table(pool, table)
+    n, n_pos = _svm_counts(K, ld, n=n, n_pos=n_pos)
+    for k in range(K):
+        _check_svm_shape(int(n[k]), int(n_pos[k]), C_, K)
+        if n[k] > ld:
+            raise ValueError(f"svm: detector {k} lists {n[k]} samples in a table of {ld} columns")
+    if not (C > 0 and tol > 0):
+        raise ValueError(f"svm: C {C} and tol {tol} must be positive")
+    need = svm_workspace_bytes(K, ld)
+    if work is None:
+        work = torch.empty(need, dtype=torch.uint8, device=dev)
+    n_d, n_pos_d = (torch.from_numpy(v.astype(np.int32)).to(dev) for v in (n, n_pos))
+    w = torch.empty((K, C_), dtype=torch.float64, device=dev)
+    b = torch.empty(K, dtype=torch.float64, device=dev)
+    n_iter, status = torch.empty(K, dtype=torch.int32, device=dev), torch.empty(K, dtype=torch.int32, device=dev)
+    alpha = torch.empty((K, ld), dtype=torch.float64, device=dev) if want_alpha else None
+    with torch.cuda.device(dev):
+        rc = _lib().dm_svm_fit(_stream(torch, dev), _p(pool), R, C_, _p(table), ld, _p(n_d), _p(n_pos_d), K, float(C), float(tol),
+                               int(max_iter), _p(work), work.numel() * work.element_size(), _p(w), _p(b), _p(n_iter), _p(status), _p(alpha))
+    _check_svm(rc, "dm_svm_fit")
+    return w, b, n_iter, status, alpha
+
+
+def svm_hard_negatives(pool, table, n, first, max_samples, w, b, work=None):
+    """dm_svm_hard_negatives on the current stream -> device tensors (score float64 [K, ld], hard int32 [K, ld], count int32 [K])."""
+    torch, pool, table, dev = _svm_device_args(pool, table)
+    R, C_, K, ld = _svm_table(pool, table)
+    n, first, max_samples = _svm_counts(K, ld, n=n, first=first, max_samples=max_samples)
+    if tuple(w.shape) != (K, C_) or tuple(b.shape) != (K,) or w.dtype != torch.float64 or b.dtype != torch.float64:
+        raise ValueError(f"svm: w must be float64 [{K}, {C_}] and b float64 [{K}]")
+    need = svm_workspace_bytes(K, ld)
+    if work is None:
+        work = torch.empty(need, dtype=torch.uint8, device=dev)
+    n_d, first_d, max_d = (torch.from_numpy(np.clip(v, -1, 2 ** 31 - 1).astype(np.int32)).to(dev) for v in (n, first, max_samples))
+    score = torch.empty((K, ld), dtype=torch.float64, device=dev)
+    hard = torch.empty((K, ld), dtype=torch.int32, device=dev)
+    count = torch.empty(K, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib().dm_svm_hard_negatives(_stream(torch, dev), _p(pool), R, C_, _p(table), ld, _p(n_d), _p(first_d), _p(max_d), K,
+                                          _p(w.contiguous()), _p(b.contiguous()), _p(work), work.numel() * work.element_size(),
+                                          _p(score), _p(hard), _p(count))
+    _check_svm(rc, "dm_svm_hard_negatives")
+    return score, hard, count
+
+
+def _svm_raise(status):
+    bad = np.flatnonzero(np.asarray(status) >= SVM_NAN)
+    if len(bad):
+        k = int(bad[0])
+        if int(np.asarray(status)[k]) == SVM_NAN:
+            raise ValueError(f"svm: the samples of detector {k} contain NaN or infinity")
+        raise ValueError(f"svm: the sample list of detector {k} cannot be used: no positive, no negative, more samples than the table "
+                         f"has columns, or a sample outside the pool")
+
+
+def train_svms(pool, table, n, n_pos, n_hn, max_samples, C: float = 0.1, tol: float = 1e-3, max_iter: int = -1):
+    """`train_svm` for K detectors at once.  pool fp16 [R, C]; row k of table int32 [K, ld] lists detector k's n[k] samples as pool
+    rows: n_pos[k] positives, n_hn[k] hard negatives of earlier rounds, then the new negatives, among which at most max_samples[k]
+    hard negatives are mined (n, n_pos, n_hn, max_samples: an int or K ints).  Returns (w float64 [K, C], b float64 [K], n_iter
+    int32 [K], status int32 [K], hard int32 [K, ld] — positions in the detector's list, -1 from count on —, count int32 [K]):
+    device tensors for a pool on the GPU, numpy arrays (by `svm_fit_host` / `hard_negatives_host`) for a numpy pool.  Raises
+    ValueError where a detector's samples hold a NaN or an infinity, as scikit-learn does."""
+    if isinstance(pool, np.ndarray):
+        table = np.asarray(table)
+        R, C_, K, ld = _svm_table(pool, table)
+        n, n_pos, n_hn, max_samples = _svm_counts(K, ld, n=n, n_pos=n_pos, n_hn=n_hn, max_samples=max_samples)
+        w, b = np.empty((K, C_)), np.empty(K)
+        n_iter, status, count = (np.zeros(K, dtype=np.int32) for _ in range(3))
+        hard = np.full((K, ld), -1, dtype=np.int32)
+        for k in range(K):
+            if n[k] > ld or table[k, :n[k]].min() < 0 or table[k, :n[k]].max() >= R:
+                raise ValueError(f"svm: detector {k} names a sample outside the pool")
+            X = pool[table[k, :n[k]]]
+            w[k], b[k], n_iter[k], _, status[k] = svm_fit_host(X, n_pos[k], C, tol, max_iter)
+            idx, _ = hard_negatives_host(X, w[k], b[k], n_pos[k] + n_hn[k], max_samples[k])
+            count[k] = len(idx)
+            hard[k, :len(idx)] = idx
+        return w, b, n_iter, status, hard, count
+    torch, pool, table, dev = _svm_device_args(pool, table)
+    K, ld = table.shape
+    n, n_pos, n_hn, max_samples = _svm_counts(K, ld, n=n, n_pos=n_pos, n_hn=n_hn, max_samples=max_samples)
+    work = torch.empty(svm_workspace_bytes(K, ld), dtype=torch.uint8, device=dev)
+    w, b, n_iter, status, _ = svm_fit(pool, table, n, n_pos, C, tol, max_iter, work)
+    _svm_raise(status.cpu().numpy())
+    _, hard, count = svm_hard_negatives(pool, table, n, n_pos + n_hn, max_samples, w, b, work)
+    return w, b, n_iter, status, hard, count
+
+
+def train_svm(X, split, max_samples):
+    """`train_svm(X, split, max_samples)` of doersch/doersch.py:66-79: X = the rows of len_p positives, len_hn earlier hard negatives
+    and len_n new negatives, split = (len_p, len_hn, len_n) -> (coef float64 [C], hard_negatives.tolist()): the new negatives that
+    score above 0, highest first, at most max_samples.  The intercept is dropped, as the reference drops it.  Rows are taken as
+    fp16 (what the reference's caches hold).  A numpy X (or a list of rows) takes the host restatement, a torch tensor on the GPU
+    the kernels."""
+    len_p, len_hn, len_n = (int(v) for v in split)
+    if hasattr(X, "is_cuda") and X.is_cuda:
+        import torch
+        if X.shape[0] != len_p + len_hn + len_n:
+            raise ValueError(f"svm: {X.shape[0]} rows for split {tuple(split)}")
+        X = X.to(torch.float16).contiguous()
+        table = torch.arange(max(X.shape[0], 2), dtype=torch.int32, device=X.device)[None]
+        w, _, _, _, hard, count = train_svms(X, table, X.shape[0], len_p, len_hn, max_samples)
+        return w[0].cpu().numpy(), X[hard[0, :int(count[0])].long()].cpu().numpy().tolist()
+    X = np.stack([np.asarray(x) for x in X], axis=0).astype(np.float16)
+    if len(X) != len_p + len_hn + len_n:
+        raise ValueError(f"svm: {len(X)} rows for split {tuple(split)}")
+    w, b, _, _, _ = svm_fit_host(X, len_p)
+    idx, _ = hard_negatives_host(X, w, b, len_p + len_hn, max_samples)
+    return w, X[idx].tolist()
+
+
+def svm_round(positives, negatives, hard_negatives, C: float = 0.1, tol: float = 1e-3, max_iter: int = -1, max_samples=None):
+    """One batch of doersch/doersch.py:462-471.  positives: what `DenseSearch.result(ret_ws=True)` returns (per detector its entries
+    (score, bbox, path, row)); negatives: per detector the rows `sample_negatives` drew, fp16 [m, C] — all numpy or all on one GPU,
+    and one array may serve several detectors (it enters the pool once); hard_negatives: per detector the running list of rows,
+    extended here by the round's new hard negatives (numpy rows on the host path, rows of a device tensor on the GPU).
+    max_samples: per detector, default the reference's max(25000 - len(hard_negatives[k]), 10000).  Builds the pool and the index
+    table, calls `train_svms` and returns ws float64 [K, C] (numpy / a device tensor): the next search's detectors."""
+    K = len(positives)
+    if not (K == len(negatives) == len(hard_negatives)) or K < 1:
+        raise ValueError(f"svm: {K} detectors, {len(negatives)} negative sets and {len(hard_negatives)} hard-negative lists")
+    host = isinstance(negatives[0], np.ndarray)
+    if host:
+        to_rows = lambda rows: np.stack([np.asarray(r, dtype=np.float16) for r in rows])                      # noqa: E731
+        cat = np.concatenate
+    else:
+        import torch
+        dev = negatives[0].device
+
+        def to_rows(rows):
+            """numpy rows (a search's `ret_ws` rows) and device rows (earlier rounds' hard negatives) in their order -> fp16 [m, C] on
+            `dev`: the numpy rows travel in one copy."""
+            out = torch.empty((len(rows), len(rows[0])), dtype=torch.float16, device=dev)
+            on_dev = [j for j, r in enumerate(rows) if isinstance(r, torch.Tensor)]
+            on_host = [j for j, r in enumerate(rows) if not isinstance(r, torch.Tensor)]
+            if on_dev:
+                out[torch.tensor(on_dev, device=dev)] = torch.stack([rows[j].to(device=dev, dtype=torch.float16) for j in on_dev])
+            if on_host:
+                out[torch.tensor(on_host, device=dev)] = torch.from_numpy(np.stack([np.asarray(rows[j], dtype=np.float16) for j in on_host])).to(dev)
+            return out
+        cat = torch.cat
+    parts, at, shared = [], 0, {}
+    lists, n, n_pos, n_hn = [], [], [], []
+    for k in range(K):
+        pos = [entry[3] for entry in positives[k]]
+        if not pos:
+            raise ValueError(f"svm: detector {k} has no positive")
+        own = to_rows(pos + list(hard_negatives[k]))
+        idx = [np.arange(at, at + len(own))]
+        parts.append(own)
+        at += len(own)
+        if id(negatives[k]) not in shared:
+            shared[id(negatives[k])] = at
+            parts.append(negatives[k].reshape(-1, negatives[k].shape[-1]))
+            at += len(parts[-1])
+        idx.append(shared[id(negatives[k])] + np.arange(negatives[k].reshape(-1, negatives[k].shape[-1]).shape[0]))
+        lists.append(np.concatenate(idx))
+        n.append(len(lists[-1]))
+        n_pos.append(len(pos))
+        n_hn.append(len(hard_negatives[k]))
+    pool = cat(parts)
+    table = np.zeros((K, max(max(n), 2)), dtype=np.int32)
+    for k in range(K):
+        table[k, :n[k]] = lists[k]
+    if max_samples is None:
+        max_samples = [max(25000 - h, 10000) for h in n_hn]
+    w, _, _, _, hard, count = train_svms(pool, table, np.array(n), np.array(n_pos), np.array(n_hn), np.asarray(max_samples), C, tol, max_iter)
+    if host:
+        for k in range(K):
+            hard_negatives[k] += list(pool[table[k, hard[k, :count[k]]]])
+    else:
+        count_h = count.cpu().numpy()
+        if count_h.any():
+            table_d = torch.from_numpy(table).to(dev)
+            for k in np.flatnonzero(count_h):
+                hard_negatives[k] += list(pool[table_d[k, hard[k, :int(count_h[k])].long()].long()])
+    return w
+
+
+def fold_pool(n: int, fold):
+    """The positions `random_sample` draws from under fold = (i, l) (hog.py:206-207): the first i n // l entries of the CPU
+    `torch.randperm(n)` under `torch.manual_seed(0)`, as a numpy int64 array.  Reseeds torch's global generator, as the reference does."""
+    import torch
+    i, l = int(fold[0]), int(fold[1])
+    torch.manual_seed(0)
+    return torch.randperm(n, device="cpu")[:(i * n) // l].numpy()
+
+
+def sample_negatives(chunks, num_samples: int, fold=None, rng=None):
+    """`random_sample(sft_paths, fold, num_samples)` of doersch/hog.py:187-212.  chunks: the shards, each a sequence of the shard's
+    keys' tensors fp16 [B, W, H, C] — all numpy or all on one GPU.  Every shard gives num_samples // len(chunks) rows, spread over its
+    keys as max(1, that // keys) rows per key, drawn without replacement from the key's B W H cells or, with fold, from `fold_pool`
+    of them; shards and keys are visited in a shuffled order.  The positions are drawn on the host from `rng` (a numpy Generator;
+    default a fresh unseeded one, as the reference draws from Python's unseeded `random`); the rows are fetched by `gather` on the
+    device.  Returns fp16 [total, C], numpy or on the device of the chunks."""
+    rng = np.random.default_rng() if rng is None else rng
+    chunks = [list(shard) for shard in chunks]
+    if not chunks or any(not shard for shard in chunks):
+        raise ValueError("sample_negatives: no shard, or a shard without a key")
+    per_shard = int(num_samples) // len(chunks)
+    out = []
+    for s in rng.permutation(len(chunks)):
+        shard = chunks[s]
+        per_key = max(1, per_shard // len(shard))
+        for q in rng.permutation(len(shard)):
+            data = shard[q]
+            if data.ndim != 4:
+                raise ValueError(f"sample_negatives: a key's tensor must be [B, W, H, C], got {tuple(data.shape)}")
+            B, cells, C_ = data.shape[0], data.shape[1] * data.shape[2], data.shape[3]
+            population = np.arange(B * cells) if fold is None else fold_pool(B * cells, fold)
+            if per_key > len(population):
+                raise ValueError(f"sample_negatives: {per_key} rows from a key of {len(population)} cells")
+            at = rng.choice(population, size=per_key, replace=False)
+            if isinstance(data, np.ndarray):
+                out.append(data.reshape(B * cells, C_)[at].astype(np.float16))
+            else:
+                import torch
+                pairs = torch.from_numpy(np.stack([at // cells, at % cells], axis=1).astype(np.int32)).to(data.device)
+                out.append(gather(data.half().contiguous().view(B, cells, C_), pairs))
+    if isinstance(out[0], np.ndarray):
+        return np.concatenate(out)
+    import torch
+    return torch.cat(out)

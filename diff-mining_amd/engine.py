@@ -16,8 +16,8 @@ LIB_PATH = os.path.join(_HERE, "lib", "libdm_engine.so")
 _lib = None
 _CHECK_DEVICE_SLOTS = os.environ.get("DM_CHECK_SLOTS", "0") not in ("", "0")     # debug: validate prompt slots that live on the GPU
 
-_vp, _cp, _i32, _i64, _f32, _sz = C.c_void_p, C.c_char_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
-_pvp, _pi32, _pi64, _pf32, _pf64, _psz = (C.POINTER(t) for t in (_vp, _i32, _i64, _f32, C.c_double, _sz))
+_vp, _cp, _i32, _i64, _f32, _f64, _sz = C.c_void_p, C.c_char_p, C.c_int, C.c_int64, C.c_float, C.c_double, C.c_size_t
+_pvp, _pi32, _pi64, _pf32, _pf64, _psz = (C.POINTER(t) for t in (_vp, _i32, _i64, _f32, _f64, _sz))
 _WEIGHT = [_vp, _cp, _vp, _i32, _pi64, _i32]        # (handle, name, host_ptr, dtype, shape, ndim) of every *_load_*weight
 _PROF = [_vp, _pf64, _pf64, _pi64, _pf64, _pf64, _pi64]
 
@@ -60,6 +60,9 @@ SIGNATURES = {
     "dm_hoglab_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "dm_hoglab_cells": (_i32, [_vp, _vp] + [_i32] * 3 + [_vp] * 3),
     "dm_hoglab_features": (_i32, [_vp, _vp] + [_i32] * 3 + [_vp] * 4 + [_sz]),
+    "dm_svm_workspace_bytes": (_sz, [_i32, _i32]),
+    "dm_svm_fit": (_i32, [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _f64, _f64, _i32, _vp, _sz] + [_vp] * 5),
+    "dm_svm_hard_negatives": (_i32, [_vp, _vp, _i32, _i32, _vp, _i32] + [_vp] * 3 + [_i32, _vp, _vp, _vp, _sz] + [_vp] * 3),
     "dm_prof_enable": (_i32, [_vp, _i32]),
     "dm_measure_mfma_rate": (_i32, [_vp, _i32, _i32, _pf64, _pf64]),
     "dm_prof_read": (_i32, _PROF),

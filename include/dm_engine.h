@@ -403,6 +403,62 @@ int dm_hoglab_cells(void* stream, const void* images_u8, int B, int H, int W, co
 int dm_hoglab_features(void* stream, const void* images_u8, int B, int H, int W, const void* bins_u8, void* out_f16_or_null,
                        float* raw_f32_or_null, void* work, size_t work_bytes);
 
+/* ---- Doersch baseline: the detectors' linear SVMs, batched SMO (csrc/svm.hip) ---------------------------------------
+ * `train_svm` (doersch/doersch.py:66-79) for K detectors at once: scikit-learn's SVC(C=cost, kernel='linear', shrinking=False).fit
+ * as libsvm's Solver::Solve iterates it, step for step, then the hard negatives by decision_function > 0.  Stream-plus-workspace
+ * functions (no engine handle).  rows_f16 [R][C] fp16 row-major is a pool of feature rows; detector k's samples are the pool rows
+ * sample_i32[k][0 .. n_i32[k]), the first n_pos_i32[k] of them labelled +1, the rest -1.  Detectors may share pool rows, list them
+ * in any order and repeat one; nothing is copied into per-detector matrices.  sample_i32, alpha_f64, score_f64 and hard_i32 are
+ * tables [K][ld]; n_i32, n_pos_i32, first_i32 and max_samples_i32 are device arrays [K].
+ *
+ * dm_svm_fit.  The solver works in libsvm's internal order (the negatives, in their own order, as y = +1, then the positives as
+ * y = -1) and breaks ties by it: i = the LAST index of the largest violation, j = the LAST index of the lowest second-order gain.
+ * alpha and G are fp64; QD_t = x_t . x_t in fp64; Q_i[t] = (float)(y_i y_t (x_i . x_t)) (libsvm's Qfloat); a dot is the sum of the
+ * exact products of the fp16 values in fp64, in an order that depends on C alone; G_t += Q_i[t] d_alpha_i + Q_j[t] d_alpha_j in
+ * fp64 without fused multiply-add.  Stop: Gmax + Gmax2 < eps, no j, or max_iter iterations (max_iter <= 0: libsvm's
+ * max(10 000 000, 100 n)).  Outputs (device): w_f64 [K][C] = -sum_t alpha_t y_t x_t over the support vectors in ascending
+ * internal index; b_f64 [K] = rho (the mean of y_t G_t over the free variables, else the midpoint of libsvm's ub / lb);
+ * n_iter_i32 [K]; status_i32 [K] = DM_SVM_CONVERGED, DM_SVM_MAX_ITER, DM_SVM_NAN (a row with a NaN or an infinity; w and b are
+ * NaN) or DM_SVM_BAD_LIST (n_pos < 1, n - n_pos < 1 or n > ld: nothing of the pool is read; or a sample outside [0, R): that row is
+ * never dereferenced, the detector's other rows are read once and it stops before the first iteration; w and b are NaN); alpha_f64_or_null [K][ld], entry p = the alpha of sample p (slots from n on hold 0).  Every decision is made on the
+ * device; the host enqueues a group of iterations and reads the K stop flags once per group, so the call synchronises `stream`
+ * and returns with it synchronised.  work: dm_svm_workspace_bytes(K, ld) bytes (0 = bad arguments), 16-byte aligned, contents free.
+ *
+ * dm_svm_hard_negatives (doersch.py:75-78).  Per detector over the samples p in [first_i32[k], n_i32[k]): s_p = x_p . w_k + b_k in
+ * fp64 (fp16 row value times fp64 weight, summed in an order that depends on C alone).  Admitted: s_p > 0.  hard_i32[k] = the
+ * admitted p by descending s, ascending p among equals, at most max_samples_i32[k] of them; count_i32[k] = how many; slots from
+ * count on hold -1.  score_f64[k][p] = s_p, NaN for p outside [first, n) and for a sample outside [0, R).  It does not synchronise.
+ *
+ * No floating-point atomics and no wait on another workgroup; every output of detector k depends on detector k's inputs alone:
+ * not on K, on its place in the call or on the other detectors.
+ * Refused without a launch (DM_SVM_E_*): a null required pointer; K outside [1, DM_SVM_MAX_DETECTORS]; C < 8, C % 8 != 0 or
+ * C > DM_SVM_MAX_FEATURES (the hard negatives' score pass stages w in LDS as fp64: 8 C bytes, 64 KB at the limit; the fit stages
+ * x_i as fp32, 4 C bytes); R < 1; ld < 2 or ld >= 2^24; cost or eps not > 0; a small workspace; rows_f16
+ * or work not 16-byte aligned. */
+#define DM_SVM_MAX_DETECTORS 128
+#define DM_SVM_MAX_FEATURES 8192
+#define DM_SVM_CONVERGED 0
+#define DM_SVM_MAX_ITER 1
+#define DM_SVM_NAN 2
+#define DM_SVM_BAD_LIST 3
+#define DM_SVM_E_NULL 1
+#define DM_SVM_E_K 2
+#define DM_SVM_E_C 3
+#define DM_SVM_E_ROWS 4
+#define DM_SVM_E_LD 5
+#define DM_SVM_E_N_LARGE 6
+#define DM_SVM_E_COST 7
+#define DM_SVM_E_WORK 8
+#define DM_SVM_E_ALIGN 9
+#define DM_SVM_E_HIP 10
+size_t dm_svm_workspace_bytes(int K, int n_max);
+int dm_svm_fit(void* stream, const void* rows_f16, int R, int C, const int32_t* sample_i32, int ld, const int32_t* n_i32,
+               const int32_t* n_pos_i32, int K, double cost, double eps, int max_iter, void* work, size_t work_bytes, double* w_f64,
+               double* b_f64, int32_t* n_iter_i32, int32_t* status_i32, double* alpha_f64_or_null);
+int dm_svm_hard_negatives(void* stream, const void* rows_f16, int R, int C, const int32_t* sample_i32, int ld, const int32_t* n_i32,
+                          const int32_t* first_i32, const int32_t* max_samples_i32, int K, const double* w_f64, const double* b_f64,
+                          void* work, size_t work_bytes, double* score_f64, int32_t* hard_i32, int32_t* count_i32);
+
 /* Profiling support for bench.py: when enabled, every launch of the dominant (implicit-GEMM)
  * kernel is bracketed by hipEvents on the launch stream.  dm_prof_read synchronises and returns
  * the accumulated kernel milliseconds, launch count and algorithmic FLOPs since the last reset. */
