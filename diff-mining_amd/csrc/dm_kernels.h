@@ -52,7 +52,7 @@ struct LaunchTimer {
     std::vector<hipEvent_t> pairs;      // start, stop, start, stop, ...
     hipError_t err = hipSuccess;
 };
-extern thread_local LaunchTimer* g_launch_timer;          // engine.hip
+extern thread_local LaunchTimer* g_launch_timer;          // engine_forward.hip
 template <typename F, typename... Args>
 inline void launch_timed(F kernel, const dim3& grid, const dim3& block, size_t lds, hipStream_t s, Args... args) {
     LaunchTimer* t = g_launch_timer;
@@ -66,13 +66,9 @@ inline void launch_timed(F kernel, const dim3& grid, const dim3& block, size_t l
     t->pairs.push_back(ev[0]); t->pairs.push_back(ev[1]);
 }
 
-// Runtime switches (A/B measurements; every default is the measured best).  Initialised from the environment variable of
-// the same name in upper case with a DM_ prefix (DM_IGEMM_PERSIST=0 ...), changeable through dm_set_option().
-enum Option { OPT_IGEMM_BIG = 0, OPT_IGEMM_SPLITK, OPT_LN_FOLD, OPT_ATTN_PIPE, OPT_IGEMM_TAIL, OPT_ATTN_CROSS, OPT_LN_STATS_G, OPT_IGEMM_EXP, OPT_LN_INKERNEL, OPT_GRAPH, OPT_GN_FOLD, OPT_SC_FOLD, OPT_FF_FOLD, OPT_TAP_REUSE, OPT_UP_FOLD, OPT_Q_ONCE, OPT_GN_EPI, OPT_CONV_OUT_ROWS, OPT_GN_SKIP, OPT_COUNT };
-int option(Option o);                       // engine.hip
-unsigned options_epoch();                   // engine.hip: changes with every set_option() that changed a value
-int set_option(const char* name, int value);   // 0 on success
-int get_option(const char* name, int* value);  // 0 on success
+#define DM_OPTIONS_IN_NAMESPACE_DM
+#include "options.h"
+#undef DM_OPTIONS_IN_NAMESPACE_DM
 
 // ---- K1/K2/K3: implicit-GEMM on MFMA (conv3x3 s1/s2/upsampled, 1x1 conv, linear) -------------
 enum IGemmMode { IG_DENSE = 0, IG_CONV3 = 1, IG_CONV3_S2 = 2, IG_CONV3_UP = 3, IG_CONV3_S2P0 = 4, IG_CONV2_UP4 = 5 };

@@ -167,7 +167,7 @@ constexpr int EPI_PARTIAL = 2;
 // translation unit of its own (igemm_pers_sc.hip).
 // UP4 (r04): Upsample2D (nearest 2x) + its 3x3 convolution as FOUR 2x2 convolutions on the low-resolution source, one per output
 // parity class (py, px): output pixel (2 y + py, 2 x + px) sees source rows y - 1 + py + {0, 1} and columns x - 1 + px + {0, 1}, and
-// the taps of the 3x3 kernel that land on one source pixel are pre-summed (engine.hip fold_upconv_weights): 4 instead of 9 k taps.
+// the taps of the 3x3 kernel that land on one source pixel are pre-summed (engine_pack.hip fold_upconv_weights): 4 instead of 9 k taps.
 // mode IG_CONV2_UP4, H x W = OH x OW = the SOURCE grid, M = N H W rows PER PHASE; the tile stream walks phase-major
 // (4 x tiles-per-phase tiles), weights Wp [4][Cout][4 Cin], the epilogue scatters a row to its pixel of the [N][2H][2W] output.
 // Template variant in a translation unit of its own (igemm_pers_up.hip).

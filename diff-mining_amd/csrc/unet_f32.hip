@@ -2,7 +2,7 @@
 //
 // `SDFeaturizer.__init__` (diffmining/typicality/dift.py:197-199) builds `OneStepSDPipeline.from_pretrained(sd_id, unet=unet,
 // safety_checker=None)` with NO torch_dtype and calls the U-Net with NO autocast (dift.py:191): every tensor and every product
-// of that path is fp32.  The fp16 engine (engine.hip) reproduces the autocast arithmetic of the typicality path
+// of that path is fp32.  The fp16 engine (engine*.hip) reproduces the autocast arithmetic of the typicality path
 // (compute.py:98-101); this file is the second arithmetic the reference uses, behind its own C-ABI handle (include/dm_engine.h,
 // dm_f32_*): fp32 weights, fp32 NHWC activations, v_mfma_f32_16x16x4_f32 GEMMs (f32_gemm.hip) and attention (f32_ops.hip).
 // It runs the whole U-Net (dm_f32_unet_forward) or the early exit after up_blocks[i] (dm_f32_dift), so it is also the
@@ -13,9 +13,10 @@
 #include "f32_kernels.h"
 #include "arena.h"
 #include "weights.h"
+#include "sd15.h"
+#include "host_rt.h"
+#include "options.h"
 #include "../../include/dm_engine.h"
-
-int dm_get_option_up_fold();      // engine.hip: the process-wide switch "up_fold" (dm_set_option)
 
 #include <cmath>
 #include <cstdio>
@@ -27,15 +28,10 @@ int dm_get_option_up_fold();      // engine.hip: the process-wide switch "up_fol
 #include <hip/hip_fp16.h>
 
 using namespace dm32;
+using namespace sd15;
 
 namespace {
 
-constexpr int NB = 4;
-const int BOC[NB] = {320, 640, 1280, 1280};
-constexpr int LAYERS = 2, CTX_DIM = 768, CTX_LEN = 77, HEADS = 8, GROUPS = 32, TEMB = 1280;
-constexpr float GN_EPS = 1e-5f, ATTN_GN_EPS = 1e-6f, LN_EPS = 1e-5f;
-const bool DOWN_ATTN[NB] = {true, true, true, false};
-const bool UP_ATTN[NB] = {false, true, true, true};
 constexpr size_t NONE = (size_t)-1;
 
 thread_local std::string g_create_error32;
@@ -50,9 +46,6 @@ struct DownB { Res res[2]; Tfm tf[2]; bool attn = false; Conv down; bool has_dow
 struct UpB { Res res[3]; Tfm tf[3]; bool attn = false; Conv up; bool has_up = false; Conv up4; bool has_up4 = false; };   // up4: the up-sampler folded onto the source grid (mode 5)
 
 // SDv1.5 AutoencoderKL encoder (block_out_channels 128/256/512/512, two resnets per block, no time embedding)
-constexpr int VNB = 4;
-const int VBOC[VNB] = {128, 256, 512, 512};
-constexpr float VAE_EPS = 1e-6f;
 struct Vae32 {
     Conv conv_in;                  // transposed [27][128] for the direct kernel
     Res down[VNB][2]; Conv ds[VNB - 1];
@@ -63,7 +56,6 @@ struct Vae32 {
 };
 
 // CLIP ViT-L/14 text tower (`pipe.text_encoder` of the featuriser's fp32 pipeline: dift.py:197-199, 222-226)
-constexpr int CL_LAYERS = 12, CL_H = 768, CL_F = 3072, CL_HEADS = 12, CL_T = 77, CL_VOCAB = 49408;
 struct ClipLayer32 { Norm ln1, ln2; Conv qkv, o, fc1, fc2; };
 struct Clip32 { size_t tok = NONE, pos = NONE; ClipLayer32 layer[CL_LAYERS]; Norm final_ln; };
 
@@ -110,12 +102,6 @@ struct dm_f32_net {
 };
 
 namespace {
-
-#define F_FAIL(e, ...) do { char _b[512]; snprintf(_b, sizeof(_b), __VA_ARGS__); (e)->err = _b; return 1; } while (0)
-#define F_HIP(e, call) do { hipError_t _r = (call); if (_r != hipSuccess) { \
-    char _b[512]; snprintf(_b, sizeof(_b), "%s failed: %s (%s:%d)", #call, hipGetErrorString(_r), __FILE__, __LINE__); \
-    (e)->err = _b; return 1; } } while (0)
-#define F_TRY(x) do { int _rc = (x); if (_rc) return _rc; } while (0)
 
 // ---- packing ---------------------------------------------------------------------------------------------------------------
 struct Packer32 {           // one finalize: reads the staged tensors of `set`, owns the host image of its slab
@@ -182,7 +168,7 @@ int pack_dense(Packer32& P, const std::string& name, int cout, int cin, bool con
 }
 int pack_norm(Packer32& P, const std::string& name, int c, Norm* o) {
     o->c = c;
-    F_TRY(pack_vec(P, name + ".weight", c, &o->g));
+    DM_TRY(pack_vec(P, name + ".weight", c, &o->g));
     return pack_vec(P, name + ".bias", c, &o->b);
 }
 int pack_stack(Packer32& P, const std::vector<std::string>& names, int rows_each, int cin, Conv* o) {
@@ -198,7 +184,7 @@ int pack_stack(Packer32& P, const std::vector<std::string>& names, int rows_each
 }
 // q | k | v projections stacked [3C][C] with their biases [3C]
 int pack_qkv(Packer32& P, const std::vector<std::string>& names, int c, Conv* o) {
-    F_TRY(pack_stack(P, names, c, c, o));
+    DM_TRY(pack_stack(P, names, c, c, o));
     std::vector<float> qb;
     for (const std::string& n : names) {
         HostT* b = P.get(n + ".bias", {c});
@@ -228,12 +214,12 @@ int pack_geglu(Packer32& P, const std::string& name, int c, Conv* o) {
     return 0;
 }
 int pack_vae_res(Packer32& P, const std::string& name, int cin, int cout, Res* r) {
-    F_TRY(pack_norm(P, name + ".norm1", cin, &r->n1));
-    F_TRY(pack_conv3(P, name + ".conv1", cout, cin, &r->c1));
-    F_TRY(pack_norm(P, name + ".norm2", cout, &r->n2));
-    F_TRY(pack_conv3(P, name + ".conv2", cout, cout, &r->c2));
+    DM_TRY(pack_norm(P, name + ".norm1", cin, &r->n1));
+    DM_TRY(pack_conv3(P, name + ".conv1", cout, cin, &r->c1));
+    DM_TRY(pack_norm(P, name + ".norm2", cout, &r->n2));
+    DM_TRY(pack_conv3(P, name + ".conv2", cout, cout, &r->c2));
     r->has_sc = cin != cout;
-    if (r->has_sc) F_TRY(pack_dense(P, name + ".conv_shortcut", cout, cin, true, true, &r->sc));
+    if (r->has_sc) DM_TRY(pack_dense(P, name + ".conv_shortcut", cout, cin, true, true, &r->sc));
     return 0;
 }
 // the U-Net's ResnetBlock2D = the VAE's + a time-embedding projection, whose rows go to P.tw / P.tb and not to the blob
@@ -247,31 +233,31 @@ int pack_res(Packer32& P, const std::string& name, int cin, int cout, Res* r) {
     return pack_vae_res(P, name, cin, cout, r);
 }
 int pack_clip_layer(Packer32& P, const std::string& b, ClipLayer32* L) {       // CLIPEncoderLayer, text and image tower alike
-    F_TRY(pack_norm(P, b + ".layer_norm1", CL_H, &L->ln1));
-    F_TRY(pack_qkv(P, {b + ".self_attn.q_proj", b + ".self_attn.k_proj", b + ".self_attn.v_proj"}, CL_H, &L->qkv));
-    F_TRY(pack_dense(P, b + ".self_attn.out_proj", CL_H, CL_H, false, true, &L->o));
-    F_TRY(pack_norm(P, b + ".layer_norm2", CL_H, &L->ln2));
-    F_TRY(pack_dense(P, b + ".mlp.fc1", CL_F, CL_H, false, true, &L->fc1));
+    DM_TRY(pack_norm(P, b + ".layer_norm1", CL_H, &L->ln1));
+    DM_TRY(pack_qkv(P, {b + ".self_attn.q_proj", b + ".self_attn.k_proj", b + ".self_attn.v_proj"}, CL_H, &L->qkv));
+    DM_TRY(pack_dense(P, b + ".self_attn.out_proj", CL_H, CL_H, false, true, &L->o));
+    DM_TRY(pack_norm(P, b + ".layer_norm2", CL_H, &L->ln2));
+    DM_TRY(pack_dense(P, b + ".mlp.fc1", CL_F, CL_H, false, true, &L->fc1));
     return pack_dense(P, b + ".mlp.fc2", CL_H, CL_F, false, true, &L->fc2);
 }
 int pack_tfm(Packer32& P, const std::string& name, int c, Tfm* t) {
     dm_f32_net* e = P.e;
     t->c = c; t->layer = e->n_tf++;
     e->tfs.push_back(t);
-    F_TRY(pack_norm(P, name + ".norm", c, &t->gn));
-    F_TRY(pack_dense(P, name + ".proj_in", c, c, true, true, &t->proj_in));
+    DM_TRY(pack_norm(P, name + ".norm", c, &t->gn));
+    DM_TRY(pack_dense(P, name + ".proj_in", c, c, true, true, &t->proj_in));
     const std::string b = name + ".transformer_blocks.0";
-    F_TRY(pack_norm(P, b + ".norm1", c, &t->ln1));
-    F_TRY(pack_stack(P, {b + ".attn1.to_q", b + ".attn1.to_k", b + ".attn1.to_v"}, c, c, &t->qkv));
-    F_TRY(pack_dense(P, b + ".attn1.to_out.0", c, c, false, true, &t->o1));
-    F_TRY(pack_norm(P, b + ".norm2", c, &t->ln2));
-    F_TRY(pack_dense(P, b + ".attn2.to_q", c, c, false, false, &t->q2));
-    F_TRY(pack_stack(P, {b + ".attn2.to_k", b + ".attn2.to_v"}, c, CTX_DIM, &t->kv2));
-    F_TRY(pack_dense(P, b + ".attn2.to_out.0", c, c, false, true, &t->o2));
-    F_TRY(pack_norm(P, b + ".norm3", c, &t->ln3));
-    F_TRY(pack_geglu(P, b + ".ff.net.0.proj", c, &t->ff1));
-    F_TRY(pack_dense(P, b + ".ff.net.2", c, 4 * c, false, true, &t->ff2));
-    F_TRY(pack_dense(P, name + ".proj_out", c, c, true, true, &t->proj_out));
+    DM_TRY(pack_norm(P, b + ".norm1", c, &t->ln1));
+    DM_TRY(pack_stack(P, {b + ".attn1.to_q", b + ".attn1.to_k", b + ".attn1.to_v"}, c, c, &t->qkv));
+    DM_TRY(pack_dense(P, b + ".attn1.to_out.0", c, c, false, true, &t->o1));
+    DM_TRY(pack_norm(P, b + ".norm2", c, &t->ln2));
+    DM_TRY(pack_dense(P, b + ".attn2.to_q", c, c, false, false, &t->q2));
+    DM_TRY(pack_stack(P, {b + ".attn2.to_k", b + ".attn2.to_v"}, c, CTX_DIM, &t->kv2));
+    DM_TRY(pack_dense(P, b + ".attn2.to_out.0", c, c, false, true, &t->o2));
+    DM_TRY(pack_norm(P, b + ".norm3", c, &t->ln3));
+    DM_TRY(pack_geglu(P, b + ".ff.net.0.proj", c, &t->ff1));
+    DM_TRY(pack_dense(P, b + ".ff.net.2", c, 4 * c, false, true, &t->ff2));
+    DM_TRY(pack_dense(P, name + ".proj_out", c, c, true, true, &t->proj_out));
     return 0;
 }
 
@@ -286,7 +272,7 @@ struct Fwd32 {
         t->N = N; t->H = H; t->W = W; t->C = C;
         const size_t bytes = (size_t)N * H * W * C * sizeof(float);
         t->off = e->arena.alloc(bytes);
-        if (t->off == NONE) F_FAIL(e, "fp32 workspace arena exhausted (%zu bytes requested)", bytes);
+        if (t->off == NONE) DM_FAIL(e, "fp32 workspace arena exhausted (%zu bytes requested)", bytes);
         t->p = reinterpret_cast<float*>(e->arena_base + t->off);
         return 0;
     }
@@ -296,19 +282,19 @@ struct Fwd32 {
         Ev ev; ev.flops = flops; ev.kind = kind; ev.M = M; ev.N = N; ev.K = K; ev.mode = mode;
         for (hipEvent_t* h : {&ev.a, &ev.b}) {
             if (!e->ev_pool.empty()) { *h = e->ev_pool.back(); e->ev_pool.pop_back(); }
-            else F_HIP(e, hipEventCreate(h));
+            else DM_HIP(e, hipEventCreate(h));
         }
-        F_HIP(e, hipEventRecord(ev.a, s));
+        DM_HIP(e, hipEventRecord(ev.a, s));
         e->evs.push_back(ev);
         return 0;
     }
-    int prof_end() { if (e->prof && !dry) F_HIP(e, hipEventRecord(e->evs.back().b, s)); return 0; }
+    int prof_end() { if (e->prof && !dry) DM_HIP(e, hipEventRecord(e->evs.back().b, s)); return 0; }
 
     int gemm(const Conv& cv, int mode, const T32& x, const T32* x2, int OH, int OW, const float* temb, int temb_ld, const T32* res, T32* y, int epi = 0) {
         const int cin = x.C + (x2 ? x2->C : 0);
-        if (cin != cv.cin) F_FAIL(e, "gemm32: channel mismatch %d vs %d", cin, cv.cin);
+        if (cin != cv.cin) DM_FAIL(e, "gemm32: channel mismatch %d vs %d", cin, cv.cin);
         const int cy = epi == 1 ? cv.cout / 2 : cv.cout;
-        F_TRY(alloc(y, x.N, OH, OW, cy));
+        DM_TRY(alloc(y, x.N, OH, OW, cy));
         if (dry) return 0;
         GemmParams p;
         p.epi = epi;
@@ -316,52 +302,52 @@ struct Fwd32 {
         p.Cout = cv.cout; p.Cin = cin; p.C1 = x.C; p.mode = mode; p.ldy = cy; p.ldres = res ? res->C : 0; p.temb_ld = temb_ld;
         if (mode == 0) { p.M = (int)x.rows(); p.H = 1; p.W = p.M; p.OH = 1; p.OW = p.M; }
         else { p.M = x.N * OH * OW; p.H = x.H; p.W = x.W; p.OH = OH; p.OW = OW; }
-        F_TRY(prof_begin(0, 2.0 * (double)p.M * cv.cout * (double)((mode == 0 ? 1 : 9) * cin), p.M, cv.cout, (mode == 0 ? 1 : 9) * cin, mode));
-        F_HIP(e, launch_gemm(p, s));
+        DM_TRY(prof_begin(0, 2.0 * (double)p.M * cv.cout * (double)((mode == 0 ? 1 : 9) * cin), p.M, cv.cout, (mode == 0 ? 1 : 9) * cin, mode));
+        DM_HIP(e, launch_gemm(p, s));
         return prof_end();
     }
     int upconv4(const Conv& cv, const T32& x, T32* y) {      // FLOPs booked = executed (4 taps)
-        if (x.C != cv.cin) F_FAIL(e, "upconv4 (fp32): channel mismatch %d vs %d", x.C, cv.cin);
-        F_TRY(alloc(y, x.N, 2 * x.H, 2 * x.W, cv.cout));
+        if (x.C != cv.cin) DM_FAIL(e, "upconv4 (fp32): channel mismatch %d vs %d", x.C, cv.cin);
+        DM_TRY(alloc(y, x.N, 2 * x.H, 2 * x.W, cv.cout));
         if (dry) return 0;
         GemmParams p;
         p.X = x.p; p.Wp = P(cv.w); p.bias = P(cv.b); p.Y = y->p;
         p.Cout = cv.cout; p.Cin = x.C; p.C1 = x.C; p.mode = 5; p.ldy = cv.cout;
         p.M = x.N * x.H * x.W; p.H = x.H; p.W = x.W; p.OH = x.H; p.OW = x.W;
-        F_TRY(prof_begin(0, 2.0 * 4.0 * (double)p.M * cv.cout * 4.0 * (double)x.C, 4 * p.M, cv.cout, 4 * x.C, 5));
-        F_HIP(e, launch_gemm(p, s));
+        DM_TRY(prof_begin(0, 2.0 * 4.0 * (double)p.M * cv.cout * 4.0 * (double)x.C, 4 * p.M, cv.cout, 4 * x.C, 5));
+        DM_HIP(e, launch_gemm(p, s));
         return prof_end();
     }
     int dense(const Conv& cv, const T32& x, const T32* x2, const T32* res, T32* y) { return gemm(cv, 0, x, x2, x.H, x.W, nullptr, 0, res, y); }
     int groupnorm(const Norm& nw, const T32& x, const T32* x2, float eps, bool silu, T32* y) {
         const int C = x.C + (x2 ? x2->C : 0);
-        if (C != nw.c) F_FAIL(e, "groupnorm32: channel mismatch %d vs %d", C, nw.c);
+        if (C != nw.c) DM_FAIL(e, "groupnorm32: channel mismatch %d vs %d", C, nw.c);
         T32 st;
-        F_TRY(alloc(&st, 1, 1, x.N * GROUPS, 2));
-        F_TRY(alloc(y, x.N, x.H, x.W, C));
+        DM_TRY(alloc(&st, 1, 1, x.N * GROUPS, 2));
+        DM_TRY(alloc(y, x.N, x.H, x.W, C));
         if (!dry) {
-            F_HIP(e, launch_gn_stats(x.p, x2 ? x2->p : nullptr, x.N, x.H * x.W, C, x.C, GROUPS, eps, st.p, s));
-            F_HIP(e, launch_gn_apply(x.p, x2 ? x2->p : nullptr, x.N, x.H * x.W, C, x.C, GROUPS, P(nw.g), P(nw.b), st.p, silu ? 1 : 0, y->p, s));
+            DM_HIP(e, launch_gn_stats(x.p, x2 ? x2->p : nullptr, x.N, x.H * x.W, C, x.C, GROUPS, eps, st.p, s));
+            DM_HIP(e, launch_gn_apply(x.p, x2 ? x2->p : nullptr, x.N, x.H * x.W, C, x.C, GROUPS, P(nw.g), P(nw.b), st.p, silu ? 1 : 0, y->p, s));
         }
         free(st);
         return 0;
     }
     int layernorm(const Norm& nw, const T32& x, T32* y) {
-        F_TRY(alloc(y, x.N, x.H, x.W, x.C));
-        if (!dry) F_HIP(e, launch_layernorm(x.p, (int)x.rows(), x.C, P(nw.g), P(nw.b), LN_EPS, y->p, s));
+        DM_TRY(alloc(y, x.N, x.H, x.W, x.C));
+        if (!dry) DM_HIP(e, launch_layernorm(x.p, (int)x.rows(), x.C, P(nw.g), P(nw.b), LN_EPS, y->p, s));
         return 0;
     }
     int resnet(const Res& r, const T32& x, const T32* x2, const float* tproj, T32* out) {      // ResnetBlock2D
         T32 n1, h1, n2, sc;
-        F_TRY(groupnorm(r.n1, x, x2, res_eps, true, &n1));
-        F_TRY(gemm(r.c1, 1, n1, nullptr, x.H, x.W, tproj ? tproj + r.temb_off : nullptr, e->tproj_total, nullptr, &h1));
+        DM_TRY(groupnorm(r.n1, x, x2, res_eps, true, &n1));
+        DM_TRY(gemm(r.c1, 1, n1, nullptr, x.H, x.W, tproj ? tproj + r.temb_off : nullptr, e->tproj_total, nullptr, &h1));
         free(n1);
-        F_TRY(groupnorm(r.n2, h1, nullptr, res_eps, true, &n2));
+        DM_TRY(groupnorm(r.n2, h1, nullptr, res_eps, true, &n2));
         free(h1);
         const T32* resid = &x;
-        if (r.has_sc) { F_TRY(dense(r.sc, x, x2, nullptr, &sc)); resid = &sc; }
-        else if (x2) F_FAIL(e, "resnet32: concat input without shortcut conv");
-        F_TRY(gemm(r.c2, 1, n2, nullptr, x.H, x.W, nullptr, 0, resid, out));
+        if (r.has_sc) { DM_TRY(dense(r.sc, x, x2, nullptr, &sc)); resid = &sc; }
+        else if (x2) DM_FAIL(e, "resnet32: concat input without shortcut conv");
+        DM_TRY(gemm(r.c2, 1, n2, nullptr, x.H, x.W, nullptr, 0, resid, out));
         free(n2);
         if (r.has_sc) free(sc);
         return 0;
@@ -373,41 +359,41 @@ struct Fwd32 {
         a.bsq = bsq; a.bsk = bskv; a.bsv = bskv; a.bso = (long long)Tq * C;
         a.kv_slot = slots; a.n_slots = e->n_prompts; a.B = B; a.heads = heads; a.Tq = Tq; a.Tk = Tk; a.D = C / heads;
         a.scale = 1.0f / sqrtf((float)a.D);
-        F_TRY(prof_begin(1, 4.0 * B * heads * (double)Tq * Tk * a.D, B * Tq, Tk, a.D, Tq == Tk ? 100 : 101));
-        F_HIP(e, launch_attention(a, s));
+        DM_TRY(prof_begin(1, 4.0 * B * heads * (double)Tq * Tk * a.D, B * Tq, Tk, a.D, Tq == Tk ? 100 : 101));
+        DM_HIP(e, launch_attention(a, s));
         return prof_end();
     }
     int transformer(const Tfm& t, const T32& x, const int32_t* slots, T32* out) {       // Transformer2DModel + BasicTransformerBlock
         const int C = t.c, T = x.H * x.W, B = x.N;
         T32 n, t0, ln, qkv, a, t1, q, t2, ff, t3;
-        F_TRY(groupnorm(t.gn, x, nullptr, ATTN_GN_EPS, false, &n));
-        F_TRY(dense(t.proj_in, n, nullptr, nullptr, &t0));
+        DM_TRY(groupnorm(t.gn, x, nullptr, ATTN_GN_EPS, false, &n));
+        DM_TRY(dense(t.proj_in, n, nullptr, nullptr, &t0));
         free(n);
-        F_TRY(layernorm(t.ln1, t0, &ln));
-        F_TRY(dense(t.qkv, ln, nullptr, nullptr, &qkv));
+        DM_TRY(layernorm(t.ln1, t0, &ln));
+        DM_TRY(dense(t.qkv, ln, nullptr, nullptr, &qkv));
         free(ln);
-        F_TRY(alloc(&a, B, x.H, x.W, C));
-        if (!dry) F_TRY(attention(qkv.p, 3 * C, (long long)T * 3 * C, qkv.p + C, qkv.p + 2 * C, 3 * C, (long long)T * 3 * C, nullptr, B, T, T, C, a.p));
+        DM_TRY(alloc(&a, B, x.H, x.W, C));
+        if (!dry) DM_TRY(attention(qkv.p, 3 * C, (long long)T * 3 * C, qkv.p + C, qkv.p + 2 * C, 3 * C, (long long)T * 3 * C, nullptr, B, T, T, C, a.p));
         free(qkv);
-        F_TRY(dense(t.o1, a, nullptr, &t0, &t1));
+        DM_TRY(dense(t.o1, a, nullptr, &t0, &t1));
         free(a); free(t0);
-        F_TRY(layernorm(t.ln2, t1, &ln));
-        F_TRY(dense(t.q2, ln, nullptr, nullptr, &q));
+        DM_TRY(layernorm(t.ln2, t1, &ln));
+        DM_TRY(dense(t.q2, ln, nullptr, nullptr, &q));
         free(ln);
-        F_TRY(alloc(&a, B, x.H, x.W, C));
+        DM_TRY(alloc(&a, B, x.H, x.W, C));
         if (!dry) {
             const float* kv = e->kv_cache[t.layer];
-            F_TRY(attention(q.p, C, (long long)T * C, kv, kv + C, 2 * C, (long long)CTX_LEN * 2 * C, slots, B, T, CTX_LEN, C, a.p));
+            DM_TRY(attention(q.p, C, (long long)T * C, kv, kv + C, 2 * C, (long long)CTX_LEN * 2 * C, slots, B, T, CTX_LEN, C, a.p));
         }
         free(q);
-        F_TRY(dense(t.o2, a, nullptr, &t1, &t2));
+        DM_TRY(dense(t.o2, a, nullptr, &t1, &t2));
         free(a); free(t1);
-        F_TRY(layernorm(t.ln3, t2, &ln));
-        F_TRY(gemm(t.ff1, 0, ln, nullptr, x.H, x.W, nullptr, 0, nullptr, &ff, 1));        // GEGLU in the epilogue: [tokens][4C]
+        DM_TRY(layernorm(t.ln3, t2, &ln));
+        DM_TRY(gemm(t.ff1, 0, ln, nullptr, x.H, x.W, nullptr, 0, nullptr, &ff, 1));        // GEGLU in the epilogue: [tokens][4C]
         free(ln);
-        F_TRY(dense(t.ff2, ff, nullptr, &t2, &t3));
+        DM_TRY(dense(t.ff2, ff, nullptr, &t2, &t3));
         free(ff); free(t2);
-        F_TRY(dense(t.proj_out, t3, nullptr, &x, out));
+        DM_TRY(dense(t.proj_out, t3, nullptr, &x, out));
         free(t3);
         return 0;
     }
@@ -416,19 +402,19 @@ struct Fwd32 {
     int clip_layer(const ClipLayer32& L, int n, int T, bool causal, T32* x) {
         const int M = n * T;
         T32 h, qkv, a, x1, f, x2;
-        F_TRY(layernorm(L.ln1, *x, &h));
-        F_TRY(dense(L.qkv, h, nullptr, nullptr, &qkv));
+        DM_TRY(layernorm(L.ln1, *x, &h));
+        DM_TRY(dense(L.qkv, h, nullptr, nullptr, &qkv));
         free(h);
-        F_TRY(alloc(&a, 1, 1, M, CL_H));
-        if (!dry) F_HIP(e, launch_clip_attention(qkv.p, n, T, CL_HEADS, causal, a.p, s));
+        DM_TRY(alloc(&a, 1, 1, M, CL_H));
+        if (!dry) DM_HIP(e, launch_clip_attention(qkv.p, n, T, CL_HEADS, causal, a.p, s));
         free(qkv);
-        F_TRY(dense(L.o, a, nullptr, x, &x1));
+        DM_TRY(dense(L.o, a, nullptr, x, &x1));
         free(a); free(*x);
-        F_TRY(layernorm(L.ln2, x1, &h));
-        F_TRY(dense(L.fc1, h, nullptr, nullptr, &f));
+        DM_TRY(layernorm(L.ln2, x1, &h));
+        DM_TRY(dense(L.fc1, h, nullptr, nullptr, &f));
         free(h);
-        if (!dry) F_HIP(e, launch_quick_gelu(f.p, (long long)M * CL_F, s));
-        F_TRY(dense(L.fc2, f, nullptr, &x1, &x2));
+        if (!dry) DM_HIP(e, launch_quick_gelu(f.p, (long long)M * CL_F, s));
+        DM_TRY(dense(L.fc2, f, nullptr, &x1, &x2));
         free(f); free(x1);
         *x = x2;
         return 0;
@@ -444,24 +430,24 @@ int run_forward32(dm_f32_net* e, const Args32& A, hipStream_t s, bool dry) {
     Fwd32 F{e, s, dry, e->w_unet.slab};
     const int B = A.B;
     T32 te0, e1, e1s, emb, embs, tproj;
-    F_TRY(F.alloc(&te0, 1, 1, B, BOC[0]));
-    if (!dry) F_HIP(e, launch_timestep_embed(A.t, B, BOC[0], te0.p, s));
-    F_TRY(F.dense(e->time1, te0, nullptr, nullptr, &e1));
+    DM_TRY(F.alloc(&te0, 1, 1, B, BOC[0]));
+    if (!dry) DM_HIP(e, launch_timestep_embed(A.t, B, BOC[0], te0.p, s));
+    DM_TRY(F.dense(e->time1, te0, nullptr, nullptr, &e1));
     F.free(te0);
-    F_TRY(F.alloc(&e1s, 1, 1, B, TEMB));
-    if (!dry) F_HIP(e, launch_silu(e1.p, e1s.p, (long long)B * TEMB, s));
+    DM_TRY(F.alloc(&e1s, 1, 1, B, TEMB));
+    if (!dry) DM_HIP(e, launch_silu(e1.p, e1s.p, (long long)B * TEMB, s));
     F.free(e1);
-    F_TRY(F.dense(e->time2, e1s, nullptr, nullptr, &emb));
+    DM_TRY(F.dense(e->time2, e1s, nullptr, nullptr, &emb));
     F.free(e1s);
-    F_TRY(F.alloc(&embs, 1, 1, B, TEMB));
-    if (!dry) F_HIP(e, launch_silu(emb.p, embs.p, (long long)B * TEMB, s));
+    DM_TRY(F.alloc(&embs, 1, 1, B, TEMB));
+    if (!dry) DM_HIP(e, launch_silu(emb.p, embs.p, (long long)B * TEMB, s));
     F.free(emb);
-    F_TRY(F.dense(e->tproj_all, embs, nullptr, nullptr, &tproj));
+    DM_TRY(F.dense(e->tproj_all, embs, nullptr, nullptr, &tproj));
     F.free(embs);
 
     T32 h;
-    F_TRY(F.alloc(&h, B, A.H, A.W, BOC[0]));
-    if (!dry) F_HIP(e, launch_conv_in(A.x, F.P(e->conv_in.w), F.P(e->conv_in.b), B, 4, A.H, A.W, BOC[0], h.p, s));
+    DM_TRY(F.alloc(&h, B, A.H, A.W, BOC[0]));
+    if (!dry) DM_HIP(e, launch_conv_in(A.x, F.P(e->conv_in.w), F.P(e->conv_in.b), B, 4, A.H, A.W, BOC[0], h.p, s));
     std::vector<T32> skips;
     skips.push_back(h);
     T32 cur = h;                     // aliases the newest skip (not freed here)
@@ -469,23 +455,23 @@ int run_forward32(dm_f32_net* e, const Args32& A, hipStream_t s, bool dry) {
         const DownB& d = e->down[i];
         for (int j = 0; j < LAYERS; ++j) {
             T32 r;
-            F_TRY(F.resnet(d.res[j], cur, nullptr, tproj.p, &r));
-            if (d.attn) { T32 a; F_TRY(F.transformer(d.tf[j], r, A.slots, &a)); F.free(r); r = a; }
+            DM_TRY(F.resnet(d.res[j], cur, nullptr, tproj.p, &r));
+            if (d.attn) { T32 a; DM_TRY(F.transformer(d.tf[j], r, A.slots, &a)); F.free(r); r = a; }
             skips.push_back(r);
             cur = r;
         }
         if (d.has_down) {
             T32 dn;
-            F_TRY(F.gemm(d.down, 2, cur, nullptr, (cur.H + 1) / 2, (cur.W + 1) / 2, nullptr, 0, nullptr, &dn));
+            DM_TRY(F.gemm(d.down, 2, cur, nullptr, (cur.H + 1) / 2, (cur.W + 1) / 2, nullptr, 0, nullptr, &dn));
             skips.push_back(dn);
             cur = dn;
         }
     }
     T32 m0, m1, m2;
-    F_TRY(F.resnet(e->mid_res[0], cur, nullptr, tproj.p, &m0));
-    F_TRY(F.transformer(e->mid_tf, m0, A.slots, &m1));
+    DM_TRY(F.resnet(e->mid_res[0], cur, nullptr, tproj.p, &m0));
+    DM_TRY(F.transformer(e->mid_tf, m0, A.slots, &m1));
     F.free(m0);
-    F_TRY(F.resnet(e->mid_res[1], m1, nullptr, tproj.p, &m2));
+    DM_TRY(F.resnet(e->mid_res[1], m1, nullptr, tproj.p, &m2));
     F.free(m1);
     cur = m2;                        // owned from here on
     const bool fwd_up_size = (A.H % 8 != 0) || (A.W % 8 != 0);          // dift.py:54-56
@@ -495,9 +481,9 @@ int run_forward32(dm_f32_net* e, const Args32& A, hipStream_t s, bool dry) {
         for (int j = 0; j < LAYERS + 1; ++j) {
             T32 skip = skips.back(); skips.pop_back();
             T32 r;
-            F_TRY(F.resnet(u.res[j], cur, &skip, tproj.p, &r));
+            DM_TRY(F.resnet(u.res[j], cur, &skip, tproj.p, &r));
             F.free(cur); F.free(skip);
-            if (u.attn) { T32 a; F_TRY(F.transformer(u.tf[j], r, A.slots, &a)); F.free(r); r = a; }
+            if (u.attn) { T32 a; DM_TRY(F.transformer(u.tf[j], r, A.slots, &a)); F.free(r); r = a; }
             cur = r;
         }
         if (u.has_up) {
@@ -505,20 +491,20 @@ int run_forward32(dm_f32_net* e, const Args32& A, hipStream_t s, bool dry) {
             if (fwd_up_size && !skips.empty()) { OH = skips.back().H; OW = skips.back().W; }
             T32 upc;
             // exact 2x: four 2x2 convolutions on the source grid (4/9 of the MACs; option up_fold, as the fp16 engine)
-            if (dm_get_option_up_fold() && u.has_up4 && OH == 2 * cur.H && OW == 2 * cur.W) F_TRY(F.upconv4(u.up4, cur, &upc));
-            else F_TRY(F.gemm(u.up, 3, cur, nullptr, OH, OW, nullptr, 0, nullptr, &upc));
+            if (dm::option(dm::OPT_UP_FOLD) && u.has_up4 && OH == 2 * cur.H && OW == 2 * cur.W) DM_TRY(F.upconv4(u.up4, cur, &upc));
+            else DM_TRY(F.gemm(u.up, 3, cur, nullptr, OH, OW, nullptr, 0, nullptr, &upc));
             F.free(cur);
             cur = upc;
         }
         if (A.up_ft_index == i && !dry) {
-            if (A.feat) F_HIP(e, launch_nhwc_to_nchw(cur.p, cur.N, cur.H * cur.W, cur.C, A.feat, s));
-            if (A.feat_mean) F_HIP(e, launch_ensemble_mean(cur.p, cur.N / A.ensemble, A.ensemble, cur.H * cur.W, cur.C, A.feat_mean, s));
+            if (A.feat) DM_HIP(e, launch_nhwc_to_nchw(cur.p, cur.N, cur.H * cur.W, cur.C, A.feat, s));
+            if (A.feat_mean) DM_HIP(e, launch_ensemble_mean(cur.p, cur.N / A.ensemble, A.ensemble, cur.H * cur.W, cur.C, A.feat_mean, s));
         }
     }
     if (A.up_ft_index < 0) {
         T32 nrm;
-        F_TRY(F.groupnorm(e->norm_out, cur, nullptr, GN_EPS, true, &nrm));
-        if (!dry) F_HIP(e, launch_conv_out(nrm.p, F.P(e->conv_out.w), F.P(e->conv_out.b), B, A.H, A.W, BOC[0], 4, A.out, s));
+        DM_TRY(F.groupnorm(e->norm_out, cur, nullptr, GN_EPS, true, &nrm));
+        if (!dry) DM_HIP(e, launch_conv_out(nrm.p, F.P(e->conv_out.w), F.P(e->conv_out.b), B, A.H, A.W, BOC[0], 4, A.out, s));
         F.free(nrm);
     }
     F.free(cur);
@@ -537,46 +523,46 @@ int run_vae32(dm_f32_net* e, const VaeArgs32& A, hipStream_t s, bool dry) {
     F.res_eps = VAE_EPS;
     const Vae32& v = e->vae;
     T32 cur;
-    F_TRY(F.alloc(&cur, A.B, A.H, A.W, VBOC[0]));
-    if (!dry) F_HIP(e, launch_conv_in(A.image, F.P(v.conv_in.w), F.P(v.conv_in.b), A.B, 3, A.H, A.W, VBOC[0], cur.p, s));
+    DM_TRY(F.alloc(&cur, A.B, A.H, A.W, VBOC[0]));
+    if (!dry) DM_HIP(e, launch_conv_in(A.image, F.P(v.conv_in.w), F.P(v.conv_in.b), A.B, 3, A.H, A.W, VBOC[0], cur.p, s));
     for (int i = 0; i < VNB; ++i) {
         for (int j = 0; j < 2; ++j) {
             T32 r;
-            F_TRY(F.resnet(v.down[i][j], cur, nullptr, nullptr, &r));
+            DM_TRY(F.resnet(v.down[i][j], cur, nullptr, nullptr, &r));
             F.free(cur);
             cur = r;
         }
         if (i != VNB - 1) {      // Downsample2D(padding=0): F.pad(x, (0,1,0,1)) + conv3x3 stride 2
             T32 dn;
-            F_TRY(F.gemm(v.ds[i], 4, cur, nullptr, cur.H / 2, cur.W / 2, nullptr, 0, nullptr, &dn));
+            DM_TRY(F.gemm(v.ds[i], 4, cur, nullptr, cur.H / 2, cur.W / 2, nullptr, 0, nullptr, &dn));
             F.free(cur);
             cur = dn;
         }
     }
     {
         T32 m0, n, qkv, a, m1, m2;
-        F_TRY(F.resnet(v.mid[0], cur, nullptr, nullptr, &m0));
+        DM_TRY(F.resnet(v.mid[0], cur, nullptr, nullptr, &m0));
         F.free(cur);
         const int C = VBOC[VNB - 1], T = m0.H * m0.W;
-        F_TRY(F.groupnorm(v.attn_gn, m0, nullptr, VAE_EPS, false, &n));
-        F_TRY(F.dense(v.qkv, n, nullptr, nullptr, &qkv));
+        DM_TRY(F.groupnorm(v.attn_gn, m0, nullptr, VAE_EPS, false, &n));
+        DM_TRY(F.dense(v.qkv, n, nullptr, nullptr, &qkv));
         F.free(n);
-        F_TRY(F.alloc(&a, m0.N, m0.H, m0.W, C));
-        if (!dry) F_TRY(F.attention(qkv.p, 3 * C, (long long)T * 3 * C, qkv.p + C, qkv.p + 2 * C, 3 * C, (long long)T * 3 * C, nullptr,
+        DM_TRY(F.alloc(&a, m0.N, m0.H, m0.W, C));
+        if (!dry) DM_TRY(F.attention(qkv.p, 3 * C, (long long)T * 3 * C, qkv.p + C, qkv.p + 2 * C, 3 * C, (long long)T * 3 * C, nullptr,
                                     m0.N, T, T, C, a.p, 1));
         F.free(qkv);
-        F_TRY(F.dense(v.o, a, nullptr, &m0, &m1));
+        DM_TRY(F.dense(v.o, a, nullptr, &m0, &m1));
         F.free(a); F.free(m0);
-        F_TRY(F.resnet(v.mid[1], m1, nullptr, nullptr, &m2));
+        DM_TRY(F.resnet(v.mid[1], m1, nullptr, nullptr, &m2));
         F.free(m1);
         cur = m2;
     }
     T32 nrm, co;
-    F_TRY(F.groupnorm(v.norm_out, cur, nullptr, VAE_EPS, true, &nrm));
+    DM_TRY(F.groupnorm(v.norm_out, cur, nullptr, VAE_EPS, true, &nrm));
     F.free(cur);
-    F_TRY(F.gemm(v.conv_out, 1, nrm, nullptr, nrm.H, nrm.W, nullptr, 0, nullptr, &co));
+    DM_TRY(F.gemm(v.conv_out, 1, nrm, nullptr, nrm.H, nrm.W, nullptr, 0, nullptr, &co));
     F.free(nrm);
-    if (!dry) F_HIP(e, launch_posterior(co.p, F.P(v.qw), F.P(v.qb), A.noise, A.B, A.draws, co.H * co.W, A.scaling, A.latent, A.moments, s));
+    if (!dry) DM_HIP(e, launch_posterior(co.p, F.P(v.qw), F.P(v.qb), A.noise, A.B, A.draws, co.H * co.W, A.scaling, A.latent, A.moments, s));
     F.free(co);
     return 0;
 }
@@ -588,13 +574,13 @@ int run_clip32(dm_f32_net* e, const int32_t* ids, int n, float* out, hipStream_t
     const Clip32& c = e->clip;
     const int M = n * CL_T;
     T32 x;
-    F_TRY(F.alloc(&x, 1, 1, M, CL_H));
-    if (!dry) F_HIP(e, launch_clip_embed(ids, F.P(c.tok), F.P(c.pos), M, CL_T, CL_H, CL_VOCAB, x.p, s));
-    for (int l = 0; l < CL_LAYERS; ++l) F_TRY(F.clip_layer(c.layer[l], n, CL_T, true, &x));
+    DM_TRY(F.alloc(&x, 1, 1, M, CL_H));
+    if (!dry) DM_HIP(e, launch_clip_embed(ids, F.P(c.tok), F.P(c.pos), M, CL_T, CL_H, CL_VOCAB, x.p, s));
+    for (int l = 0; l < CL_LAYERS; ++l) DM_TRY(F.clip_layer(c.layer[l], n, CL_T, true, &x));
     T32 y;
-    F_TRY(F.layernorm(c.final_ln, x, &y));
+    DM_TRY(F.layernorm(c.final_ln, x, &y));
     F.free(x);
-    if (!dry) F_HIP(e, hipMemcpyAsync(out, y.p, (size_t)M * CL_H * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (!dry) DM_HIP(e, hipMemcpyAsync(out, y.p, (size_t)M * CL_H * sizeof(float), hipMemcpyDeviceToDevice, s));
     F.free(y);
     return 0;
 }
@@ -615,33 +601,33 @@ int run_clipvis32(dm_f32_net* e, const ClipVisArgs& A, hipStream_t s, bool dry) 
     const ClipVis32& c = e->clipv;
     const int n = A.n, M = n * CV_T;
     T32 rows, pe, x;
-    F_TRY(F.alloc(&rows, 1, 1, n * CV_NPATCH, CV_KP));
+    DM_TRY(F.alloc(&rows, 1, 1, n * CV_NPATCH, CV_KP));
     if (!dry) {
-        if (A.pix) F_HIP(e, launch_clip_patchify(A.pix, n, rows.p, s));
-        else F_HIP(e, launch_clip_preprocess(A.images, A.desc, A.tables, n, 1, rows.p, s));
+        if (A.pix) DM_HIP(e, launch_clip_patchify(A.pix, n, rows.p, s));
+        else DM_HIP(e, launch_clip_preprocess(A.images, A.desc, A.tables, n, 1, rows.p, s));
     }
-    F_TRY(F.dense(c.patch, rows, nullptr, nullptr, &pe));          // the stride-32 convolution, no bias
+    DM_TRY(F.dense(c.patch, rows, nullptr, nullptr, &pe));          // the stride-32 convolution, no bias
     F.free(rows);
-    F_TRY(F.alloc(&x, 1, 1, M, CL_H));
-    if (!dry) F_HIP(e, launch_clip_tokens(pe.p, F.P(c.cls), F.P(c.pos), n, CL_H, x.p, s));
+    DM_TRY(F.alloc(&x, 1, 1, M, CL_H));
+    if (!dry) DM_HIP(e, launch_clip_tokens(pe.p, F.P(c.cls), F.P(c.pos), n, CL_H, x.p, s));
     F.free(pe);
     T32 x0;
-    F_TRY(F.layernorm(c.pre_ln, x, &x0));
+    DM_TRY(F.layernorm(c.pre_ln, x, &x0));
     F.free(x);
     x = x0;
-    for (int l = 0; l < CL_LAYERS; ++l) F_TRY(F.clip_layer(c.layer[l], n, CV_T, false, &x));
-    if (A.hidden && !dry) F_HIP(e, hipMemcpyAsync(A.hidden, x.p, (size_t)M * CL_H * sizeof(float), hipMemcpyDeviceToDevice, s));
+    for (int l = 0; l < CL_LAYERS; ++l) DM_TRY(F.clip_layer(c.layer[l], n, CV_T, false, &x));
+    if (A.hidden && !dry) DM_HIP(e, hipMemcpyAsync(A.hidden, x.p, (size_t)M * CL_H * sizeof(float), hipMemcpyDeviceToDevice, s));
     if (A.embeds) {
         T32 cls, pooled, emb;
-        F_TRY(F.alloc(&cls, 1, 1, n, CL_H));
-        if (!dry) F_HIP(e, launch_clip_cls(x.p, n, CL_H, cls.p, s));
-        F_TRY(F.layernorm(c.post_ln, cls, &pooled));
+        DM_TRY(F.alloc(&cls, 1, 1, n, CL_H));
+        if (!dry) DM_HIP(e, launch_clip_cls(x.p, n, CL_H, cls.p, s));
+        DM_TRY(F.layernorm(c.post_ln, cls, &pooled));
         F.free(cls);
-        F_TRY(F.dense(c.proj, pooled, nullptr, nullptr, &emb));
+        DM_TRY(F.dense(c.proj, pooled, nullptr, nullptr, &emb));
         F.free(pooled);
         if (!dry) {
-            if (A.normalize) F_HIP(e, launch_clip_l2norm(emb.p, n, CV_PROJ, A.embeds, s));
-            else F_HIP(e, hipMemcpyAsync(A.embeds, emb.p, (size_t)n * CV_PROJ * sizeof(float), hipMemcpyDeviceToDevice, s));
+            if (A.normalize) DM_HIP(e, launch_clip_l2norm(emb.p, n, CV_PROJ, A.embeds, s));
+            else DM_HIP(e, hipMemcpyAsync(A.embeds, emb.p, (size_t)n * CV_PROJ * sizeof(float), hipMemcpyDeviceToDevice, s));
         }
         F.free(emb);
     }
@@ -656,13 +642,13 @@ int ensure_arena_for32(dm_f32_net* e, hipStream_t s, const std::vector<long long
     if (it != e->arena_need.end()) need = it->second;
     else {
         e->arena.reset((size_t)1 << 46, true);
-        F_TRY(run_dry());
+        DM_TRY(run_dry());
         need = e->arena.peak + (1 << 20);
         e->arena_need[key] = need;
     }
     if (need > e->arena_cap) {
-        if (e->arena_base) { F_HIP(e, hipStreamSynchronize(s)); F_HIP(e, hipFree(e->arena_base)); e->arena_base = nullptr; e->arena_cap = 0; }
-        F_HIP(e, hipMalloc((void**)&e->arena_base, need));
+        if (e->arena_base) { DM_HIP(e, hipStreamSynchronize(s)); DM_HIP(e, hipFree(e->arena_base)); e->arena_base = nullptr; e->arena_cap = 0; }
+        DM_HIP(e, hipMalloc((void**)&e->arena_base, need));
         e->arena_cap = need;
     }
     e->arena.reset(e->arena_cap, false);
@@ -683,9 +669,9 @@ int ensure_arena32(dm_f32_net* e, const Args32& A, hipStream_t s) {
 // runs of at most CV_CHUNK images: the fc1 output is 614 KB per image, so the workspace is bounded whatever the call's size;
 // every row's arithmetic is independent of the rows around it, so the split does not change a bit
 int run_clipvis_chunked32(dm_f32_net* e, ClipVisArgs A, void* stream, const char* what) {
-    if (!e->w_clipv.ready) F_FAIL(e, "%s: CLIP vision weights not loaded (dm_f32_load_clip_vision_weight / dm_f32_finalize_clip_vision)", what);
-    if (A.n <= 0) F_FAIL(e, "%s: bad image count %d", what, A.n);
-    F_HIP(e, hipSetDevice(e->device));
+    if (!e->w_clipv.ready) DM_FAIL(e, "%s: CLIP vision weights not loaded (dm_f32_load_clip_vision_weight / dm_f32_finalize_clip_vision)", what);
+    if (A.n <= 0) DM_FAIL(e, "%s: bad image count %d", what, A.n);
+    DM_HIP(e, hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;
     const ClipVisArgs full = A;
     for (int n0 = 0; n0 < full.n; n0 += CV_CHUNK) {
@@ -695,25 +681,25 @@ int run_clipvis_chunked32(dm_f32_net* e, ClipVisArgs A, void* stream, const char
         if (full.desc) C.desc = full.desc + n0;
         if (full.embeds) C.embeds = full.embeds + (size_t)n0 * CV_PROJ;
         if (full.hidden) C.hidden = full.hidden + (size_t)n0 * CV_T * CL_H;
-        F_TRY(ensure_arena_for32(e, s, {3, C.n, C.pix ? 1 : 0, C.hidden ? 1 : 0, C.embeds ? 1 : 0}, [&]() { return run_clipvis32(e, C, s, true); }));
-        F_TRY(run_clipvis32(e, C, s, false));
+        DM_TRY(ensure_arena_for32(e, s, {3, C.n, C.pix ? 1 : 0, C.hidden ? 1 : 0, C.embeds ? 1 : 0}, [&]() { return run_clipvis32(e, C, s, true); }));
+        DM_TRY(run_clipvis32(e, C, s, false));
     }
     return 0;
 }
 
 int run_chunked32(dm_f32_net* e, Args32 A, void* stream) {
-    if (!e->finalized) F_FAIL(e, "fp32 net not finalized");
-    if (e->n_prompts <= 0) F_FAIL(e, "dm_f32_set_prompts must be called first");
-    if (A.B <= 0 || A.H < 1 || A.W < 1) F_FAIL(e, "bad batch / latent size");
-    F_HIP(e, hipSetDevice(e->device));
+    if (!e->finalized) DM_FAIL(e, "fp32 net not finalized");
+    if (e->n_prompts <= 0) DM_FAIL(e, "dm_f32_set_prompts must be called first");
+    if (A.B <= 0 || A.H < 1 || A.W < 1) DM_FAIL(e, "bad batch / latent size");
+    DM_HIP(e, hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;
     int chunk = chunk32(A.H, A.W);
     if (A.feat_mean) {                       // an ensemble never straddles two runs
-        if (A.ensemble <= 0 || A.B % A.ensemble != 0) F_FAIL(e, "batch %d is not a multiple of ensemble %d", A.B, A.ensemble);
+        if (A.ensemble <= 0 || A.B % A.ensemble != 0) DM_FAIL(e, "batch %d is not a multiple of ensemble %d", A.B, A.ensemble);
         chunk = chunk >= A.ensemble ? chunk / A.ensemble * A.ensemble : A.ensemble;
     }
     int c_out = 0, oh = 0, ow = 0;
-    if (A.up_ft_index >= 0 && dm_dift_shape(A.H, A.W, A.up_ft_index, &c_out, &oh, &ow)) F_FAIL(e, "bad up_ft_index %d", A.up_ft_index);
+    if (A.up_ft_index >= 0 && dm_dift_shape(A.H, A.W, A.up_ft_index, &c_out, &oh, &ow)) DM_FAIL(e, "bad up_ft_index %d", A.up_ft_index);
     const Args32 full = A;
     for (int b0 = 0; b0 < full.B; b0 += chunk) {
         Args32 C = full;
@@ -724,8 +710,8 @@ int run_chunked32(dm_f32_net* e, Args32 A, void* stream) {
         if (full.out) C.out = full.out + (size_t)b0 * 4 * full.H * full.W;
         if (full.feat) C.feat = full.feat + (size_t)b0 * c_out * oh * ow;
         if (full.feat_mean) C.feat_mean = full.feat_mean + (size_t)(b0 / full.ensemble) * c_out * oh * ow;
-        F_TRY(ensure_arena32(e, C, s));
-        F_TRY(run_forward32(e, C, s, false));
+        DM_TRY(ensure_arena32(e, C, s));
+        DM_TRY(run_forward32(e, C, s, false));
     }
     return 0;
 }
@@ -762,14 +748,14 @@ const char* dm_f32_last_error(dm_f32_net* e) { return e ? e->err.c_str() : g_cre
 
 int dm_f32_load_weight(dm_f32_net* e, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim) {
     if (!e || !name || !host_ptr || !shape) return 1;
-    if (e->finalized) F_FAIL(e, "load_weight after finalize");
+    if (e->finalized) DM_FAIL(e, "load_weight after finalize");
     return dm::stage_tensor(e->w_unet.host, name, host_ptr, dtype, shape, ndim, e->err);
 }
 
 int dm_f32_finalize(dm_f32_net* e) {
     if (!e) return 1;
     if (e->finalized) return 0;
-    F_HIP(e, hipSetDevice(e->device));
+    DM_HIP(e, hipSetDevice(e->device));
     Packer32 P{e, e->w_unet};
     e->n_tf = 0; e->tfs.clear();
     {   // conv_in runs as a direct kernel on the NCHW sample: weights transposed to [(ci, dy, dx)][cout]
@@ -780,26 +766,26 @@ int dm_f32_finalize(dm_f32_net* e) {
             for (int k = 0; k < 36; ++k) wt[(size_t)k * BOC[0] + co] = w->data[(size_t)co * 36 + k];
         e->conv_in.w = P.put(wt.data(), wt.size());
         e->conv_in.cin = 4; e->conv_in.cout = BOC[0]; e->conv_in.k = 3;
-        F_TRY(pack_vec(P, "conv_in.bias", BOC[0], &e->conv_in.b));
+        DM_TRY(pack_vec(P, "conv_in.bias", BOC[0], &e->conv_in.b));
     }
-    F_TRY(pack_dense(P, "time_embedding.linear_1", TEMB, BOC[0], false, true, &e->time1));
-    F_TRY(pack_dense(P, "time_embedding.linear_2", TEMB, TEMB, false, true, &e->time2));
+    DM_TRY(pack_dense(P, "time_embedding.linear_1", TEMB, BOC[0], false, true, &e->time1));
+    DM_TRY(pack_dense(P, "time_embedding.linear_2", TEMB, TEMB, false, true, &e->time2));
     int cin = BOC[0];
     for (int i = 0; i < NB; ++i) {
         DownB& d = e->down[i];
         d.attn = DOWN_ATTN[i];
         for (int j = 0; j < LAYERS; ++j) {
             const std::string b = "down_blocks." + std::to_string(i);
-            F_TRY(pack_res(P, b + ".resnets." + std::to_string(j), cin, BOC[i], &d.res[j]));
-            if (d.attn) F_TRY(pack_tfm(P, b + ".attentions." + std::to_string(j), BOC[i], &d.tf[j]));
+            DM_TRY(pack_res(P, b + ".resnets." + std::to_string(j), cin, BOC[i], &d.res[j]));
+            if (d.attn) DM_TRY(pack_tfm(P, b + ".attentions." + std::to_string(j), BOC[i], &d.tf[j]));
             cin = BOC[i];
         }
         d.has_down = i != NB - 1;
-        if (d.has_down) F_TRY(pack_conv3(P, "down_blocks." + std::to_string(i) + ".downsamplers.0.conv", BOC[i], BOC[i], &d.down));
+        if (d.has_down) DM_TRY(pack_conv3(P, "down_blocks." + std::to_string(i) + ".downsamplers.0.conv", BOC[i], BOC[i], &d.down));
     }
-    F_TRY(pack_res(P, "mid_block.resnets.0", BOC[NB - 1], BOC[NB - 1], &e->mid_res[0]));
-    F_TRY(pack_tfm(P, "mid_block.attentions.0", BOC[NB - 1], &e->mid_tf));
-    F_TRY(pack_res(P, "mid_block.resnets.1", BOC[NB - 1], BOC[NB - 1], &e->mid_res[1]));
+    DM_TRY(pack_res(P, "mid_block.resnets.0", BOC[NB - 1], BOC[NB - 1], &e->mid_res[0]));
+    DM_TRY(pack_tfm(P, "mid_block.attentions.0", BOC[NB - 1], &e->mid_tf));
+    DM_TRY(pack_res(P, "mid_block.resnets.1", BOC[NB - 1], BOC[NB - 1], &e->mid_res[1]));
     // up blocks: reversed channel list; resnet j of block i takes cat([hidden, skip]) (UNet2DConditionModel.__init__)
     int prev = BOC[NB - 1];
     for (int i = 0; i < NB; ++i) {
@@ -811,30 +797,30 @@ int dm_f32_finalize(dm_f32_net* e) {
             const int skip_c = (j == LAYERS) ? in_c : out_c;
             const int res_in = (j == 0) ? prev : out_c;
             const std::string b = "up_blocks." + std::to_string(i);
-            F_TRY(pack_res(P, b + ".resnets." + std::to_string(j), res_in + skip_c, out_c, &u.res[j]));
-            if (u.attn) F_TRY(pack_tfm(P, b + ".attentions." + std::to_string(j), out_c, &u.tf[j]));
+            DM_TRY(pack_res(P, b + ".resnets." + std::to_string(j), res_in + skip_c, out_c, &u.res[j]));
+            if (u.attn) DM_TRY(pack_tfm(P, b + ".attentions." + std::to_string(j), out_c, &u.tf[j]));
         }
         u.has_up = i != NB - 1;
         if (u.has_up) {
-            F_TRY(pack_conv3(P, "up_blocks." + std::to_string(i) + ".upsamplers.0.conv", out_c, out_c, &u.up));
-            F_TRY(pack_upconv4(P, "up_blocks." + std::to_string(i) + ".upsamplers.0.conv", out_c, out_c, u.up, &u.up4));
+            DM_TRY(pack_conv3(P, "up_blocks." + std::to_string(i) + ".upsamplers.0.conv", out_c, out_c, &u.up));
+            DM_TRY(pack_upconv4(P, "up_blocks." + std::to_string(i) + ".upsamplers.0.conv", out_c, out_c, u.up, &u.up4));
             u.has_up4 = true;
         }
         prev = out_c;
     }
-    F_TRY(pack_norm(P, "conv_norm_out", BOC[0], &e->norm_out));
-    F_TRY(pack_conv3(P, "conv_out", 4, BOC[0], &e->conv_out));
+    DM_TRY(pack_norm(P, "conv_norm_out", BOC[0], &e->norm_out));
+    DM_TRY(pack_conv3(P, "conv_out", 4, BOC[0], &e->conv_out));
     e->tproj_total = (int)P.tb.size();
     e->tproj_all.w = P.put(P.tw.data(), P.tw.size());
     e->tproj_all.b = P.put(P.tb.data(), P.tb.size());
     e->tproj_all.cin = TEMB; e->tproj_all.cout = e->tproj_total; e->tproj_all.k = 1;
-    F_TRY(P.finish("U-Net", 0));
+    DM_TRY(P.finish("U-Net", 0));
     {   // scheduler coefficients as the reference forms them (acp.to(fp32)[t] ** 0.5, (1 - acp[t]) ** 0.5)
         std::vector<float> acp(1000), tab(2000);
-        if (dm_scheduler_alphas_cumprod(1000, 0.00085f, 0.012f, acp.data())) F_FAIL(e, "scheduler table");
+        if (dm_scheduler_alphas_cumprod(1000, 0.00085f, 0.012f, acp.data())) DM_FAIL(e, "scheduler table");
         for (int i = 0; i < 1000; ++i) { tab[i] = sqrtf(acp[i]); tab[1000 + i] = sqrtf(1.0f - acp[i]); }
-        F_HIP(e, hipMalloc((void**)&e->sched_tab, tab.size() * sizeof(float)));
-        F_HIP(e, hipMemcpy(e->sched_tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
+        DM_HIP(e, hipMalloc((void**)&e->sched_tab, tab.size() * sizeof(float)));
+        DM_HIP(e, hipMemcpy(e->sched_tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
     }
     e->finalized = true;
     return 0;
@@ -843,16 +829,16 @@ int dm_f32_finalize(dm_f32_net* e) {
 /* ctx_dev [n_prompts][77][768] fp32: cross-attention K/V of the 16 transformer blocks for every prompt */
 int dm_f32_set_prompts(dm_f32_net* e, const void* ctx_dev, int n_prompts, void* stream) {
     if (!e || !ctx_dev || n_prompts <= 0) return 1;
-    if (!e->finalized) F_FAIL(e, "set_prompts before finalize");
-    F_HIP(e, hipSetDevice(e->device));
+    if (!e->finalized) DM_FAIL(e, "set_prompts before finalize");
+    DM_HIP(e, hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;
     if (n_prompts > e->kv_capacity) {
-        F_HIP(e, hipStreamSynchronize(s));
-        for (float* p : e->kv_cache) if (p) F_HIP(e, hipFree(p));
+        DM_HIP(e, hipStreamSynchronize(s));
+        for (float* p : e->kv_cache) if (p) DM_HIP(e, hipFree(p));
         int cap = e->kv_capacity > 0 ? e->kv_capacity : 4;
         while (cap < n_prompts) cap *= 2;
         e->kv_cache.assign(e->n_tf, nullptr);
-        for (int l = 0; l < e->n_tf; ++l) F_HIP(e, hipMalloc((void**)&e->kv_cache[l], (size_t)cap * CTX_LEN * 2 * e->tfs[l]->c * sizeof(float)));
+        for (int l = 0; l < e->n_tf; ++l) DM_HIP(e, hipMalloc((void**)&e->kv_cache[l], (size_t)cap * CTX_LEN * 2 * e->tfs[l]->c * sizeof(float)));
         e->kv_capacity = cap;
     }
     e->n_prompts = n_prompts;
@@ -862,7 +848,7 @@ int dm_f32_set_prompts(dm_f32_net* e, const void* ctx_dev, int n_prompts, void* 
         GemmParams p;
         p.X = (const float*)ctx_dev; p.Wp = e->w_unet.slab + kv.w; p.Y = e->kv_cache[l];
         p.M = M; p.Cout = kv.cout; p.Cin = CTX_DIM; p.C1 = CTX_DIM; p.H = 1; p.W = M; p.OH = 1; p.OW = M; p.mode = 0; p.ldy = kv.cout;
-        F_HIP(e, launch_gemm(p, s));
+        DM_HIP(e, launch_gemm(p, s));
     }
     return 0;
 }
@@ -880,30 +866,30 @@ int dm_f32_unet_forward(dm_f32_net* e, const void* sample_dev, const int64_t* t_
 int dm_f32_score(dm_f32_net* e, const void* x_dev, const int32_t* x_index_dev, const void* eps_dev, const int64_t* t_dev,
                  const int32_t* slot_dev, int batch, int n_x, int h, int w, void* loss_out_dev, void* stream) {
     if (!e || !x_dev || !eps_dev || !t_dev || !slot_dev || !loss_out_dev || batch <= 0 || n_x <= 0) return 1;
-    if (!e->finalized) F_FAIL(e, "fp32 net not finalized");
-    if (!x_index_dev && n_x != batch) F_FAIL(e, "x has %d rows for a batch of %d and no x_index", n_x, batch);
-    F_HIP(e, hipSetDevice(e->device));
+    if (!e->finalized) DM_FAIL(e, "fp32 net not finalized");
+    if (!x_index_dev && n_x != batch) DM_FAIL(e, "x has %d rows for a batch of %d and no x_index", n_x, batch);
+    DM_HIP(e, hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;
     const long long per = 4LL * h * w;
     const size_t need = (size_t)2 * batch * per;
     if (need > e->score_tmp_floats) {
-        if (e->score_tmp) { F_HIP(e, hipStreamSynchronize(s)); F_HIP(e, hipFree(e->score_tmp)); e->score_tmp = nullptr; e->score_tmp_floats = 0; }
-        F_HIP(e, hipMalloc((void**)&e->score_tmp, need * sizeof(float)));
+        if (e->score_tmp) { DM_HIP(e, hipStreamSynchronize(s)); DM_HIP(e, hipFree(e->score_tmp)); e->score_tmp = nullptr; e->score_tmp_floats = 0; }
+        DM_HIP(e, hipMalloc((void**)&e->score_tmp, need * sizeof(float)));
         e->score_tmp_floats = need;
     }
     float* noisy = e->score_tmp;
     float* pred = e->score_tmp + (size_t)batch * per;
-    F_HIP(e, launch_add_noise((const float*)x_dev, x_index_dev, (const float*)eps_dev, t_dev, e->sched_tab, e->sched_tab + 1000, batch, per, noisy, s));
+    DM_HIP(e, launch_add_noise((const float*)x_dev, x_index_dev, (const float*)eps_dev, t_dev, e->sched_tab, e->sched_tab + 1000, batch, per, noisy, s));
     Args32 A{noisy, t_dev, slot_dev, batch, h, w, -1, pred, nullptr, nullptr, 1};
-    F_TRY(run_chunked32(e, A, stream));
-    F_HIP(e, launch_sqerr(pred, (const float*)eps_dev, (long long)batch * per, (float*)loss_out_dev, s));
+    DM_TRY(run_chunked32(e, A, stream));
+    DM_HIP(e, launch_sqerr(pred, (const float*)eps_dev, (long long)batch * per, (float*)loss_out_dev, s));
     return 0;
 }
 
 int dm_f32_dift(dm_f32_net* e, const void* noisy_dev, const int64_t* t_dev, const int32_t* slot_dev, int batch, int h, int w,
                 int up_ft_index, void* feat_out_dev, void* mean_out_dev, int ensemble, void* stream) {
     if (!e || !noisy_dev || !t_dev || !slot_dev || (!feat_out_dev && !mean_out_dev)) return 1;
-    if (up_ft_index < 0 || up_ft_index >= NB) F_FAIL(e, "up_ft_index %d out of range", up_ft_index);
+    if (up_ft_index < 0 || up_ft_index >= NB) DM_FAIL(e, "up_ft_index %d out of range", up_ft_index);
     Args32 A{(const float*)noisy_dev, t_dev, slot_dev, batch, h, w, up_ft_index, nullptr, (float*)feat_out_dev, (float*)mean_out_dev,
              ensemble > 0 ? ensemble : 1};
     return run_chunked32(e, A, stream);
@@ -911,7 +897,7 @@ int dm_f32_dift(dm_f32_net* e, const void* noisy_dev, const int64_t* t_dev, cons
 
 int dm_f32_load_vae_weight(dm_f32_net* e, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim) {
     if (!e || !name || !host_ptr || !shape) return 1;
-    if (e->w_vae.ready) F_FAIL(e, "load_vae_weight after finalize_vae");
+    if (e->w_vae.ready) DM_FAIL(e, "load_vae_weight after finalize_vae");
     std::string nm(name);
     if (nm.rfind("vae.", 0) == 0) nm = nm.substr(4);
     if (nm.rfind("decoder.", 0) == 0 || nm.rfind("post_quant_conv.", 0) == 0) return 0;     // not on the path
@@ -925,7 +911,7 @@ int dm_f32_load_vae_weight(dm_f32_net* e, const char* name, const void* host_ptr
 int dm_f32_finalize_vae(dm_f32_net* e) {
     if (!e) return 1;
     if (e->w_vae.ready) return 0;
-    F_HIP(e, hipSetDevice(e->device));
+    DM_HIP(e, hipSetDevice(e->device));
     Packer32 P{e, e->w_vae};
     Vae32& v = e->vae;
     {
@@ -936,27 +922,27 @@ int dm_f32_finalize_vae(dm_f32_net* e) {
             for (int k = 0; k < 27; ++k) wt[(size_t)k * VBOC[0] + co] = w->data[(size_t)co * 27 + k];
         v.conv_in.w = P.put(wt.data(), wt.size());
         v.conv_in.cin = 3; v.conv_in.cout = VBOC[0]; v.conv_in.k = 3;
-        F_TRY(pack_vec(P, "encoder.conv_in.bias", VBOC[0], &v.conv_in.b));
+        DM_TRY(pack_vec(P, "encoder.conv_in.bias", VBOC[0], &v.conv_in.b));
     }
     int cin = VBOC[0];
     for (int i = 0; i < VNB; ++i) {
         const int cout = VBOC[i];
         const std::string bn = "encoder.down_blocks." + std::to_string(i);
-        for (int j = 0; j < 2; ++j) F_TRY(pack_vae_res(P, bn + ".resnets." + std::to_string(j), j == 0 ? cin : cout, cout, &v.down[i][j]));
-        if (i != VNB - 1) F_TRY(pack_conv3(P, bn + ".downsamplers.0.conv", cout, cout, &v.ds[i]));
+        for (int j = 0; j < 2; ++j) DM_TRY(pack_vae_res(P, bn + ".resnets." + std::to_string(j), j == 0 ? cin : cout, cout, &v.down[i][j]));
+        if (i != VNB - 1) DM_TRY(pack_conv3(P, bn + ".downsamplers.0.conv", cout, cout, &v.ds[i]));
         cin = cout;
     }
     const int C = VBOC[VNB - 1];
-    F_TRY(pack_vae_res(P, "encoder.mid_block.resnets.0", C, C, &v.mid[0]));
+    DM_TRY(pack_vae_res(P, "encoder.mid_block.resnets.0", C, C, &v.mid[0]));
     {
         const std::string a = "encoder.mid_block.attentions.0";
-        F_TRY(pack_norm(P, a + ".group_norm", C, &v.attn_gn));
-        F_TRY(pack_qkv(P, {a + ".to_q", a + ".to_k", a + ".to_v"}, C, &v.qkv));
-        F_TRY(pack_dense(P, a + ".to_out.0", C, C, false, true, &v.o));
+        DM_TRY(pack_norm(P, a + ".group_norm", C, &v.attn_gn));
+        DM_TRY(pack_qkv(P, {a + ".to_q", a + ".to_k", a + ".to_v"}, C, &v.qkv));
+        DM_TRY(pack_dense(P, a + ".to_out.0", C, C, false, true, &v.o));
     }
-    F_TRY(pack_vae_res(P, "encoder.mid_block.resnets.1", C, C, &v.mid[1]));
-    F_TRY(pack_norm(P, "encoder.conv_norm_out", C, &v.norm_out));
-    F_TRY(pack_conv3(P, "encoder.conv_out", 8, C, &v.conv_out));
+    DM_TRY(pack_vae_res(P, "encoder.mid_block.resnets.1", C, C, &v.mid[1]));
+    DM_TRY(pack_norm(P, "encoder.conv_norm_out", C, &v.norm_out));
+    DM_TRY(pack_conv3(P, "encoder.conv_out", 8, C, &v.conv_out));
     {
         HostT* qw = P.get("quant_conv.weight", {8, 8, 1, 1});
         HostT* qb = P.get("quant_conv.bias", {8});
@@ -973,9 +959,9 @@ int dm_f32_finalize_vae(dm_f32_net* e) {
 int dm_f32_vae_encode(dm_f32_net* e, const void* image_dev, const void* noise_dev, int batch, int draws_per_image, int H, int W,
                       float scaling_factor, void* latent_dev, void* moments_dev, void* stream) {
     if (!e || !image_dev || (!latent_dev && !moments_dev)) return 1;
-    if (!e->w_vae.ready) F_FAIL(e, "no VAE weights (dm_f32_load_vae_weight / dm_f32_finalize_vae)");
-    if (batch <= 0 || H < 8 || W < 8 || draws_per_image < 1) F_FAIL(e, "bad batch / image size");
-    F_HIP(e, hipSetDevice(e->device));
+    if (!e->w_vae.ready) DM_FAIL(e, "no VAE weights (dm_f32_load_vae_weight / dm_f32_finalize_vae)");
+    if (batch <= 0 || H < 8 || W < 8 || draws_per_image < 1) DM_FAIL(e, "bad batch / image size");
+    DM_HIP(e, hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;
     const int h = H / 8, w = W / 8;
     const long long area = (long long)H * W;
@@ -988,15 +974,15 @@ int dm_f32_vae_encode(dm_f32_net* e, const void* image_dev, const void* noise_de
         A.noise = noise_dev ? (const float*)noise_dev + (size_t)b0 * draws_per_image * 4 * h * w : nullptr;
         A.latent = latent_dev ? (float*)latent_dev + (size_t)b0 * draws_per_image * 4 * h * w : nullptr;
         A.moments = moments_dev ? (float*)moments_dev + (size_t)b0 * 8 * h * w : nullptr;
-        F_TRY(ensure_arena_for32(e, s, {1, A.B, A.H, A.W, 0}, [&]() { return run_vae32(e, A, s, true); }));
-        F_TRY(run_vae32(e, A, s, false));
+        DM_TRY(ensure_arena_for32(e, s, {1, A.B, A.H, A.W, 0}, [&]() { return run_vae32(e, A, s, true); }));
+        DM_TRY(run_vae32(e, A, s, false));
     }
     return 0;
 }
 
 int dm_f32_load_clip_weight(dm_f32_net* e, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim) {
     if (!e || !name || !host_ptr || !shape) return 1;
-    if (e->w_clip.ready) F_FAIL(e, "load_clip_weight after finalize_clip");
+    if (e->w_clip.ready) DM_FAIL(e, "load_clip_weight after finalize_clip");
     std::string nm(name);
     for (const char* pre : {"text_encoder.", "text_model."}) if (nm.rfind(pre, 0) == 0) nm = nm.substr(strlen(pre));
     if (nm.size() >= 12 && nm.compare(nm.size() - 12, 12, "position_ids") == 0) return 0;          // index buffer
@@ -1006,7 +992,7 @@ int dm_f32_load_clip_weight(dm_f32_net* e, const char* name, const void* host_pt
 int dm_f32_finalize_clip(dm_f32_net* e) {
     if (!e) return 1;
     if (e->w_clip.ready) return 0;
-    F_HIP(e, hipSetDevice(e->device));
+    DM_HIP(e, hipSetDevice(e->device));
     Packer32 P{e, e->w_clip};
     Clip32& c = e->clip;
     {
@@ -1016,8 +1002,8 @@ int dm_f32_finalize_clip(dm_f32_net* e) {
         c.tok = P.put(tok->data.data(), tok->data.size());
         c.pos = P.put(pos->data.data(), pos->data.size());
     }
-    for (int l = 0; l < CL_LAYERS; ++l) F_TRY(pack_clip_layer(P, "encoder.layers." + std::to_string(l), &c.layer[l]));
-    F_TRY(pack_norm(P, "final_layer_norm", CL_H, &c.final_ln));
+    for (int l = 0; l < CL_LAYERS; ++l) DM_TRY(pack_clip_layer(P, "encoder.layers." + std::to_string(l), &c.layer[l]));
+    DM_TRY(pack_norm(P, "final_layer_norm", CL_H, &c.final_ln));
     return P.finish("CLIP text", 196);
 }
 
@@ -1025,25 +1011,25 @@ int dm_f32_finalize_clip(dm_f32_net* e) {
  * input_ids_dev [n_prompts, 77] int32 (tokenizer output, padding="max_length"); out_f32_dev [n_prompts, 77, 768] fp32 */
 int dm_f32_clip_encode(dm_f32_net* e, const int32_t* input_ids_dev, int n_prompts, int seq_len, void* out_f32_dev, void* stream) {
     if (!e) return 1;
-    if (!e->w_clip.ready) F_FAIL(e, "dm_f32_clip_encode: CLIP text weights not loaded (dm_f32_load_clip_weight / dm_f32_finalize_clip)");
-    if (!input_ids_dev || !out_f32_dev || n_prompts <= 0) F_FAIL(e, "dm_f32_clip_encode: bad argument");
-    if (seq_len != CL_T) F_FAIL(e, "dm_f32_clip_encode: seq_len must be %d (padding=\"max_length\")", CL_T);
-    F_HIP(e, hipSetDevice(e->device));
+    if (!e->w_clip.ready) DM_FAIL(e, "dm_f32_clip_encode: CLIP text weights not loaded (dm_f32_load_clip_weight / dm_f32_finalize_clip)");
+    if (!input_ids_dev || !out_f32_dev || n_prompts <= 0) DM_FAIL(e, "dm_f32_clip_encode: bad argument");
+    if (seq_len != CL_T) DM_FAIL(e, "dm_f32_clip_encode: seq_len must be %d (padding=\"max_length\")", CL_T);
+    DM_HIP(e, hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;
     const int chunk = 128;                                   // prompts per pass (workspace ~ 0.5 GB)
     for (int n0 = 0; n0 < n_prompts; n0 += chunk) {
         const int n = (n_prompts - n0 < chunk) ? (n_prompts - n0) : chunk;
         const int32_t* ids = input_ids_dev + (size_t)n0 * CL_T;
         float* o = (float*)out_f32_dev + (size_t)n0 * CL_T * CL_H;
-        F_TRY(ensure_arena_for32(e, s, {2, n, 0, 0, 0}, [&]() { return run_clip32(e, ids, n, o, s, true); }));
-        F_TRY(run_clip32(e, ids, n, o, s, false));
+        DM_TRY(ensure_arena_for32(e, s, {2, n, 0, 0, 0}, [&]() { return run_clip32(e, ids, n, o, s, true); }));
+        DM_TRY(run_clip32(e, ids, n, o, s, false));
     }
     return 0;
 }
 
 int dm_f32_load_clip_vision_weight(dm_f32_net* e, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim) {
     if (!e || !name || !host_ptr || !shape) return 1;
-    if (e->w_clipv.ready) F_FAIL(e, "load_clip_vision_weight after finalize_clip_vision");
+    if (e->w_clipv.ready) DM_FAIL(e, "load_clip_vision_weight after finalize_clip_vision");
     std::string nm(name);
     // a full CLIPModel state dict: the text half and the logit scale are not on this path; position_ids is an index buffer
     if (nm.rfind("text_model.", 0) == 0 || nm == "text_projection.weight" || nm == "logit_scale") return 0;
@@ -1055,7 +1041,7 @@ int dm_f32_load_clip_vision_weight(dm_f32_net* e, const char* name, const void* 
 int dm_f32_finalize_clip_vision(dm_f32_net* e) {
     if (!e) return 1;
     if (e->w_clipv.ready) return 0;
-    F_HIP(e, hipSetDevice(e->device));
+    DM_HIP(e, hipSetDevice(e->device));
     Packer32 P{e, e->w_clipv};
     ClipVis32& c = e->clipv;
     {
@@ -1068,21 +1054,21 @@ int dm_f32_finalize_clip_vision(dm_f32_net* e) {
         c.patch.w = P.put(pw->data.data(), pw->data.size());
         c.patch.cin = CV_KP; c.patch.cout = CL_H; c.patch.k = 1; c.patch.b = NONE;
     }
-    F_TRY(pack_norm(P, "pre_layrnorm", CL_H, &c.pre_ln));
-    for (int l = 0; l < CL_LAYERS; ++l) F_TRY(pack_clip_layer(P, "encoder.layers." + std::to_string(l), &c.layer[l]));
-    F_TRY(pack_norm(P, "post_layernorm", CL_H, &c.post_ln));
-    F_TRY(pack_dense(P, "visual_projection", CV_PROJ, CL_H, false, false, &c.proj));
+    DM_TRY(pack_norm(P, "pre_layrnorm", CL_H, &c.pre_ln));
+    for (int l = 0; l < CL_LAYERS; ++l) DM_TRY(pack_clip_layer(P, "encoder.layers." + std::to_string(l), &c.layer[l]));
+    DM_TRY(pack_norm(P, "post_layernorm", CL_H, &c.post_ln));
+    DM_TRY(pack_dense(P, "visual_projection", CV_PROJ, CL_H, false, false, &c.proj));
     return P.finish("CLIP vision", CV_TENSORS);
 }
 
 int dm_f32_clip_preprocess(dm_f32_net* e, const void* images_u8_dev, const dm_clip_pre_desc* descs_dev, const int32_t* tables_dev,
                            int n_patches, void* out_pixel_values_dev, void* stream) {
     if (!e) return 1;
-    if (!images_u8_dev || !descs_dev || !tables_dev || !out_pixel_values_dev || n_patches <= 0) F_FAIL(e, "dm_f32_clip_preprocess: bad argument");
-    F_HIP(e, hipSetDevice(e->device));
+    if (!images_u8_dev || !descs_dev || !tables_dev || !out_pixel_values_dev || n_patches <= 0) DM_FAIL(e, "dm_f32_clip_preprocess: bad argument");
+    DM_HIP(e, hipSetDevice(e->device));
     for (int n0 = 0; n0 < n_patches; n0 += 65535) {
         const int n = (n_patches - n0 < 65535) ? n_patches - n0 : 65535;
-        F_HIP(e, launch_clip_preprocess((const uint8_t*)images_u8_dev, descs_dev + n0, tables_dev, n, 0,
+        DM_HIP(e, launch_clip_preprocess((const uint8_t*)images_u8_dev, descs_dev + n0, tables_dev, n, 0,
                                         (float*)out_pixel_values_dev + (size_t)n0 * CV_KP * CV_NPATCH, (hipStream_t)stream));
     }
     return 0;
@@ -1090,7 +1076,7 @@ int dm_f32_clip_preprocess(dm_f32_net* e, const void* images_u8_dev, const dm_cl
 
 int dm_f32_clip_image_features(dm_f32_net* e, const void* pixel_values_dev, int n, int normalize, void* out_f32_dev, void* stream) {
     if (!e) return 1;
-    if (!pixel_values_dev || !out_f32_dev) F_FAIL(e, "dm_f32_clip_image_features: bad argument");
+    if (!pixel_values_dev || !out_f32_dev) DM_FAIL(e, "dm_f32_clip_image_features: bad argument");
     ClipVisArgs A;
     A.pix = (const float*)pixel_values_dev; A.n = n; A.normalize = normalize != 0; A.embeds = (float*)out_f32_dev;
     return run_clipvis_chunked32(e, A, stream, "dm_f32_clip_image_features");
@@ -1098,7 +1084,7 @@ int dm_f32_clip_image_features(dm_f32_net* e, const void* pixel_values_dev, int 
 
 int dm_f32_clip_vision_hidden(dm_f32_net* e, const void* pixel_values_dev, int n, void* out_f32_dev, void* stream) {
     if (!e) return 1;
-    if (!pixel_values_dev || !out_f32_dev) F_FAIL(e, "dm_f32_clip_vision_hidden: bad argument");
+    if (!pixel_values_dev || !out_f32_dev) DM_FAIL(e, "dm_f32_clip_vision_hidden: bad argument");
     ClipVisArgs A;
     A.pix = (const float*)pixel_values_dev; A.n = n; A.hidden = (float*)out_f32_dev;
     return run_clipvis_chunked32(e, A, stream, "dm_f32_clip_vision_hidden");
@@ -1107,7 +1093,7 @@ int dm_f32_clip_vision_hidden(dm_f32_net* e, const void* pixel_values_dev, int n
 int dm_f32_clip_patch_features(dm_f32_net* e, const void* images_u8_dev, const dm_clip_pre_desc* descs_dev, const int32_t* tables_dev,
                                int n_patches, int normalize, void* out_f32_dev, void* stream) {
     if (!e) return 1;
-    if (!images_u8_dev || !descs_dev || !tables_dev || !out_f32_dev) F_FAIL(e, "dm_f32_clip_patch_features: bad argument");
+    if (!images_u8_dev || !descs_dev || !tables_dev || !out_f32_dev) DM_FAIL(e, "dm_f32_clip_patch_features: bad argument");
     ClipVisArgs A;
     A.images = (const uint8_t*)images_u8_dev; A.desc = descs_dev; A.tables = tables_dev;
     A.n = n_patches; A.normalize = normalize != 0; A.embeds = (float*)out_f32_dev;
@@ -1123,13 +1109,13 @@ int dm_f32_prof_enable(dm_f32_net* e, int on) {
 int dm_f32_prof_read(dm_f32_net* e, double* gemm_ms, double* gemm_flops, int64_t* gemm_launches, double* attn_ms, double* attn_flops,
                      int64_t* attn_launches) {
     if (!e) return 1;
-    F_HIP(e, hipSetDevice(e->device));
+    DM_HIP(e, hipSetDevice(e->device));
     FILE* dump = nullptr;          // DM_PROF_DUMP=<file>: one line per timed launch (kind M N K mode flops ms) for tools/prof_shapes.py
     if (const char* dp = getenv("DM_PROF_DUMP")) dump = fopen(dp, "a");
     for (auto& ev : e->evs) {
-        F_HIP(e, hipEventSynchronize(ev.b));
+        DM_HIP(e, hipEventSynchronize(ev.b));
         float ms = 0.f;
-        F_HIP(e, hipEventElapsedTime(&ms, ev.a, ev.b));
+        DM_HIP(e, hipEventElapsedTime(&ms, ev.a, ev.b));
         if (dump) fprintf(dump, "%d %d %d %d %d %.0f %.6f\n", ev.kind, ev.M, ev.N, ev.K, ev.mode, ev.flops, ms);
         e->prof_ms[ev.kind] += ms; e->prof_flops[ev.kind] += ev.flops; e->prof_n[ev.kind] += 1;
         e->ev_pool.push_back(ev.a); e->ev_pool.push_back(ev.b);

@@ -28,7 +28,7 @@ def pack_conv3(w):       # [Cout,Cin,3,3] -> [Cout, 9*Cin], k = (tap, cin)
     return w.permute(0, 2, 3, 1).reshape(w.shape[0], -1).contiguous()
 
 
-def pack_geglu(w, b):    # [8C, C] -> quad-interleaved rows (see engine.hip pack_geglu)
+def pack_geglu(w, b):    # [8C, C] -> quad-interleaved rows (see engine_pack.hip pack_geglu)
     c8 = w.shape[0]
     c4 = c8 // 2
     rho = torch.arange(c8)
