@@ -23,26 +23,16 @@
 //     padded, all-ones row of V^T.  Steady state per score: exp2 + max + convert (D = 40: +11 %).
 // Measured alternatives (r01): register staging + transposing ds_write_b16 0.55x, 128-key staged
 // tiles 0.95x, 64 queries/wave (occupancy 1) 0.8x, forcing 4 waves/SIMD (spills) 0.45x.
-#include "dm_kernels.h"
+#include "attention_common.h"
 #include <cstdlib>
 
 namespace dm {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
 namespace {
 
-constexpr int KT = 64;                // keys per tile
 constexpr int NT = 256;               // threads per block
-constexpr float RESCALE_THR = 8.0f;   // log2 units
 
 __device__ __attribute__((aligned(256))) unsigned char g_attn_zero[256];
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 template <int D, int QF>
 __global__ __launch_bounds__(NT, (D > 80 ? 1 : 2))
@@ -75,8 +65,7 @@ void attn_kernel(AttnParams p) {
     const int h = blockIdx.y;
     const int b = blockIdx.z;
     const int q0 = blockIdx.x * (64 * QF) + wid * (16 * QF);
-    int kvb = p.kv_slot ? p.kv_slot[b] : (p.slot_div > 0 ? b / p.slot_div : b);
-    if (p.n_slots > 0) kvb = kvb < 0 ? 0 : (kvb < p.n_slots ? kvb : p.n_slots - 1);      // memory safety: never beyond the registered prompts
+    const int kvb = kv_batch(p, b);
 
     const f16* Qb = p.Q + (size_t)(p.q_mod > 0 ? b % p.q_mod : b) * p.bsq + h * D;
     const f16* Kb = p.K + (size_t)kvb * p.bsk + h * D;
@@ -348,23 +337,6 @@ hipError_t launch_t(const AttnParams& p, hipStream_t s) {
 }
 
 }  // namespace
-
-hipError_t launch_attention_pipe(const AttnParams& p, hipStream_t s);    // attention_pipe.hip
-bool attention_pipe_supports(const AttnParams& p);
-hipError_t launch_attention_pipe80(const AttnParams& p, hipStream_t s);  // attention_pipe80.hip
-bool attention_pipe80_supports(const AttnParams& p);
-hipError_t launch_attention_cross(const AttnParams& p, hipStream_t s);   // attention_cross.hip
-bool attention_cross_supports(const AttnParams& p);
-hipError_t launch_attention_d160(const AttnParams& p, hipStream_t s);    // attention_d160.hip (r06: head_dim 160, eight waves per block)
-bool attention_d160_supports(const AttnParams& p);
-hipError_t launch_attention_d160_cross(const AttnParams& p, hipStream_t s);   // the 77-key cross-attention at head_dim 160 (one pass)
-bool attention_d160_cross_supports(const AttnParams& p);
-hipError_t launch_attention_qk32(const AttnParams& p, hipStream_t s);    // attention_qk32.hip (r06: scores on 32x32x16 MFMAs)
-bool attention_qk32_supports(const AttnParams& p);
-hipError_t launch_attention_qk64(const AttnParams& p, hipStream_t s);    // attention_qk64.hip (two 32-query sets per wave, bit-identical to qk32)
-bool attention_qk64_supports(const AttnParams& p);
-hipError_t launch_attention_pp(const AttnParams& p, int variant, hipStream_t s);   // attention_pp.hip
-bool attention_pp_supports(const AttnParams& p);
 
 static AttnRoute generic_route(int D) {
     switch (D) {

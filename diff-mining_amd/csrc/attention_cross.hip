@@ -17,19 +17,9 @@
 //     ds_read_b64_tr_b16, softmax denominator in a ones row of V^T (head_dim 40: a constant 16-byte chunk behind each
 //     96-byte LDS row; head_dim 80: a register-constant row block, bare 160-byte rows — both strides keep the
 //     transpose reads free of bank conflicts).
-#include "dm_kernels.h"
-
-#include <type_traits>
-#include <utility>
+#include "attention_common.h"
 
 namespace dm {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -59,15 +49,6 @@ struct XGeo {
     static_assert(16 * 3 + 64 * (KS - 1) + 16 <= RS + PAD && 32 * (EFV - 1) + 8 * 3 + 8 <= RS + PAD, "fragment overrun must stay inside the pad");
 };
 
-template <int OFF>
-__device__ __forceinline__ void tr_read(u32x2& out, unsigned base) {
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(out) : "v"(base), "n"(OFF) : "memory");
-}
-template <class F, int... I>
-__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) { static_for_impl(f, std::make_integer_sequence<int, N>{}); }
-
 template <int D>
 __global__ __launch_bounds__(NT, (D > 40 ? 2 : 3))
 void attn_cross_kernel(AttnParams p, int nsplit) {
@@ -88,8 +69,7 @@ void attn_cross_kernel(AttnParams p, int nsplit) {
     const int unit = (t / p.heads) * 8 + x;                  // (sample, slice)
     if (unit >= p.B * nsplit) return;
     const int b = unit / nsplit, part = unit - b * nsplit;
-    int kvb = p.kv_slot ? p.kv_slot[b] : (p.slot_div > 0 ? b / p.slot_div : b);
-    if (p.n_slots > 0) kvb = kvb < 0 ? 0 : (kvb < p.n_slots ? kvb : p.n_slots - 1);      // memory safety: never beyond the registered prompts
+    const int kvb = kv_batch(p, b);
     const int nqb = (p.Tq + 64 * QF - 1) / (64 * QF);
     const int qb0 = (int)((long long)part * nqb / nsplit), qb1 = (int)((long long)(part + 1) * nqb / nsplit);
 

@@ -14,37 +14,22 @@
 //   * arithmetic of the generic kernel's head_dim-160 path, order included: raw q.k in fp32, P = exp2(fma(s, scale log2 e, -m)), the
 //     denominator as fp32 adds of the unrounded P, lazy rescale at 2^8 — so the two kernels agree to the last bit of the softmax and
 //     differ only by the order of the PV k slots (none: the same permuted order) => bit-identical (asserted by the test).
-#include "dm_kernels.h"
+#include "attention_common.h"
 
 namespace dm {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
 constexpr int D = 160;
-constexpr int KT = 64;                // keys per tile
 constexpr int NW = 8;                 // waves per block
 constexpr int QW = 32;                // queries per wave (two 16-query fragments)
 constexpr int QF = 2;
 constexpr int KS = 5, EF = 10;        // k steps of QK^T, 16-row blocks of O^T
-constexpr float RESCALE_THR = 8.0f;   // log2 units
 constexpr int RS = 2 * D;             // 320-byte LDS rows
 constexpr int TILE = KT * RS;         // 20480
 constexpr int KOFF = 0, VOFF = TILE;
 constexpr int STAGE = 2 * TILE;       // 40960
 constexpr int NPIECE = 2 * TILE / 1024 / NW;      // 5 LDS-DMA pieces per wave and tile
-
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-template <int OFF>
-__device__ __forceinline__ void tr_read(u32x2& out, unsigned base) {
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(out) : "v"(base), "n"(OFF) : "memory");
-}
 
 // the twenty transpose reads of a 32-key half SS: blocks e = 2 E2 (base `ve`) and 2 E2 + 1 (base `vo`), 4-key groups 2 SS, 2 SS + 1
 template <int SS, int E2>
@@ -82,8 +67,7 @@ void attn_d160_kernel(AttnParams p, int nunits) {
     auto set_kv = [&](int unit) __attribute__((always_inline)) {
         const int bh = unit / nqb;
         const int h = bh % p.heads, b = bh / p.heads;
-        int kvb = p.kv_slot ? p.kv_slot[b] : (p.slot_div > 0 ? b / p.slot_div : b);
-        if (p.n_slots > 0) kvb = kvb < 0 ? 0 : (kvb < p.n_slots ? kvb : p.n_slots - 1);
+        const int kvb = kv_batch(p, b);
         const f16* Kb = p.K + (size_t)kvb * p.bsk + h * D;
         const f16* Vb = p.V + (size_t)kvb * p.bsv + h * D;
 #pragma unroll
@@ -298,8 +282,7 @@ void attn_d160_cross_kernel(AttnParams p) {
     const int h = bh % p.heads;
     const int b = bh / p.heads;
     const int q0 = qblk * (NW * QW) + wid * QW;
-    int kvb = p.kv_slot ? p.kv_slot[b] : (p.slot_div > 0 ? b / p.slot_div : b);
-    if (p.n_slots > 0) kvb = kvb < 0 ? 0 : (kvb < p.n_slots ? kvb : p.n_slots - 1);
+    const int kvb = kv_batch(p, b);
 
     const f16* Qb = p.Q + (size_t)(p.q_mod > 0 ? b % p.q_mod : b) * p.bsq + h * D;
     const f16* Kb = p.K + (size_t)kvb * p.bsk + h * D;

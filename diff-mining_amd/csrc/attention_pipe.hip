@@ -18,34 +18,17 @@
 //     iteration ahead of V tiles (two K + two V buffers, one barrier per iteration);
 //   * the per-row maximum is only reduced across lanes when a rescale actually happens (one ballot per
 //     iteration decides), and a rescale fixes the already computed S(t+1) up in place.
-#include "dm_kernels.h"
+#include "attention_common.h"
 
 namespace dm {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
 constexpr int D = 40;
-constexpr int KT = 64;                // keys per tile
 constexpr int NT = 256;               // threads per block
 constexpr int QF = 2;                 // 16-query fragments per wave
-constexpr float RESCALE_THR = 8.0f;   // log2 units
-constexpr int RS = 96;                // LDS row stride: 5 real chunks + 1 constant chunk
-constexpr int TILE = KT * RS;         // 6144
-constexpr int KOFF = 0, VOFF = TILE + 32;        // 32 zero bytes behind each tile (K reads overrun a row by 32 B)
-constexpr int STAGE = 2 * (TILE + 32);           // 12352
-constexpr int NSTG = 3;               // K/V ring depth: K is fetched three, V two tiles ahead of their use
-constexpr int KS = 2, EF = 3;
-
-__device__ __attribute__((aligned(16))) const unsigned short g_kconst[8] = {0x3C00, 0x3C00, 0, 0, 0, 0, 0, 0};
-__device__ __attribute__((aligned(16))) const unsigned short g_vconst[8] = {0x3C00, 0, 0, 0, 0, 0, 0, 0};
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
+constexpr int RS = Geo40::RS, TILE = Geo40::TILE, KOFF = Geo40::KOFF, VOFF = Geo40::VOFF, STAGE = Geo40::STAGE;   // 96, 6144, 0, 6176, 12352
+constexpr int KS = Geo40::KS, EF = Geo40::EF;   // 2, 3
 
 #ifdef DM_ATTN_TIMING
 __device__ long long g_attnp_dbg[16];
@@ -54,18 +37,6 @@ __device__ unsigned long long g_attnp_span[2] = {~0ull, 0ull};
 #else
 #define TICK(i) do {} while (0)
 #endif
-
-#define PIN(x) asm volatile("" : "+v"(x))
-
-// max through inline asm: __builtin_fmaxf (llvm.maxnum) first canonicalises operands that come out of MFMAs
-// or asm (v_max x, x), 2-3 extra VALU per row block and tile; scores are never NaN here
-__device__ __forceinline__ float vmax2(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ float vmax3(float a, float b, float c) { float r; asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
-
-template <int OFF>
-__device__ __forceinline__ void tr_read(u32x2& out, unsigned base) {
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(out) : "v"(base), "n"(OFF) : "memory");
-}
 
 #ifndef DM_ATTN_OCC
 #define DM_ATTN_OCC 3
@@ -84,23 +55,14 @@ void attn_pipe_kernel(AttnParams p) {
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l15 = lane & 15;
     const int lg = lane >> 4;
-    // XCD-aware block order: one XCD walks consecutive (sample, head) pairs, so all query blocks of a
-    // pair (which stream the same K/V) share that XCD's L2.
     const int nqb = (p.Tq + 64 * QF - 1) / (64 * QF);
-    int v;
-    {
-        const int nblk = gridDim.x, bid = blockIdx.x;
-        const int q = nblk >> 3, r = nblk & 7;
-        const int xcd = bid & 7, loc = bid >> 3;
-        v = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-    }
+    const int v = xcd_block_order();
     const int qblk = v % nqb;
     const int bh = v / nqb;
     const int h = bh % p.heads;
     const int b = bh / p.heads;
     const int q0 = qblk * (64 * QF) + wid * (16 * QF);
-    int kvb = p.kv_slot ? p.kv_slot[b] : (p.slot_div > 0 ? b / p.slot_div : b);
-    if (p.n_slots > 0) kvb = kvb < 0 ? 0 : (kvb < p.n_slots ? kvb : p.n_slots - 1);      // memory safety: never beyond the registered prompts
+    const int kvb = kv_batch(p, b);
 
     const f16* Qb = p.Q + (size_t)b * p.bsq + h * D;
     const f16* Kb = p.K + (size_t)kvb * p.bsk + h * D;

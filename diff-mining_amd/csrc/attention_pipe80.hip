@@ -20,57 +20,14 @@
 // tokens (577 -> 790 TFLOP/s), 1.32 -> 0.92 ms at 20 x 8 x 4096.  Phase timers (tools/attn_timing.py 80 1024): an iteration
 // is ~2500 cycles per wave (phase A 1500, phase B 600), and the first wait of a block (K(0) + Q from a busy memory
 // system) ~9700 cycles = a fifth of a 16-tile block's life, hidden only by the one other block resident on the CU.
-#include "dm_kernels.h"
-
-#include <type_traits>
-#include <utility>
+#include "attention_common.h"
 
 namespace dm {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
 namespace {
 
-constexpr int KT = 64;                // keys per tile
 constexpr int NT = 256;               // threads per block
 constexpr int QF = 2;                 // 16-query fragments per wave
-constexpr float RESCALE_THR = 8.0f;   // log2 units
-constexpr int NSTG = 3;               // K/V ring depth: K is fetched three, V two tiles ahead of their use
-
-// CC = 1: rows carry a constant 16-byte chunk behind the data ({1,1,0..} for K: the k columns that take -m_hi / -m_lo from
-// Q'; {1,0..} for V: the ones row of V^T), as attention_pipe.hip does.  CC = 0: bare rows; the running max enters as the
-// initial value of the score accumulators and the ones row block of V^T is a register constant (D % 16 == 0).
-template <int D, int CC>
-struct Geo {
-    static constexpr int CH = D / 8;                       // real 16-byte chunks per row
-    static constexpr int RS = (CH + CC) * 16;              // LDS row stride (bytes)
-    static constexpr int KS = (D + 8 * CC + 31) / 32;      // k steps of S^T = K Q^T
-    static constexpr int EF = (D + 1 + 15) / 16;           // 16-row blocks of O^T
-    static constexpr int EFV = CC ? EF : D / 16;           // ... of which read from LDS
-    static constexpr int S_M = D / 32, LG_M = (D % 32) / 8;   // where k = D, D + 1 live in the Q' fragments
-    static constexpr int E_L = D / 16, LG_L = (D % 16) / 4;   // where row D of O^T lives in the accumulators
-    static constexpr int TILE = KT * RS;
-    static constexpr int PAD = 32;                         // zero bytes behind each tile (fragment reads overrun a row)
-    static constexpr int KOFF = 0, VOFF = TILE + PAD;
-    static constexpr int STAGE = 2 * (TILE + PAD);
-    static constexpr int NP = KT * (CH + CC) / 64;         // 1 KiB LDS-DMA pieces per operand tile
-    static constexpr int NPW = (2 * NP + 3) / 4;           // piece slots per wave
-    static constexpr int SCRATCH = NSTG * STAGE;           // 1 KiB target of the dummy slots
-    static constexpr int LDS = NSTG * STAGE + 1024;
-    static_assert(D % 8 == 0 && (KT * (CH + CC)) % 64 == 0 && (CC || D % 16 == 0), "tile must be whole pieces");
-    static_assert(16 * 3 + 64 * (KS - 1) + 16 <= RS + PAD && 32 * (EFV - 1) + 8 * 3 + 8 <= RS + PAD, "fragment overrun must stay inside the pad");
-};
-
-__device__ __attribute__((aligned(16))) const unsigned short g_kconst80[8] = {0x3C00, 0x3C00, 0, 0, 0, 0, 0, 0};
-__device__ __attribute__((aligned(16))) const unsigned short g_vconst80[8] = {0x3C00, 0, 0, 0, 0, 0, 0, 0};
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-#define PIN(x) asm volatile("" : "+v"(x))
 
 #ifdef DM_ATTN_TIMING
 __device__ long long g_attnp80_dbg[16];
@@ -79,20 +36,6 @@ __device__ unsigned long long g_attnp80_span[2] = {~0ull, 0ull};
 #else
 #define TICK(i) do {} while (0)
 #endif
-
-__device__ __forceinline__ float vmax2(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ float vmax3(float a, float b, float c) { float r; asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
-
-template <int OFF>
-__device__ __forceinline__ void tr_read(u32x2& out, unsigned base) {
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(out) : "v"(base), "n"(OFF) : "memory");
-}
-
-// compile-time loop: f(std::integral_constant<int, i>) for i in [0, N)
-template <class F, int... I>
-__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) { static_for_impl(f, std::make_integer_sequence<int, N>{}); }
 
 template <int D, int CC>
 __global__ __launch_bounds__(NT, 2)
@@ -111,23 +54,14 @@ void attn_pipe80_kernel(AttnParams p) {
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l15 = lane & 15;
     const int lg = lane >> 4;
-    // XCD-aware block order: one XCD walks consecutive (sample, head) pairs, so all query blocks of a
-    // pair (which stream the same K/V) share that XCD's L2.
     const int nqb = (p.Tq + 64 * QF - 1) / (64 * QF);
-    int v;
-    {
-        const int nblk = gridDim.x, bid = blockIdx.x;
-        const int q = nblk >> 3, r = nblk & 7;
-        const int xcd = bid & 7, loc = bid >> 3;
-        v = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-    }
+    const int v = xcd_block_order();
     const int qblk = v % nqb;
     const int bh = v / nqb;
     const int h = bh % p.heads;
     const int b = bh / p.heads;
     const int q0 = qblk * (64 * QF) + wid * (16 * QF);
-    int kvb = p.kv_slot ? p.kv_slot[b] : (p.slot_div > 0 ? b / p.slot_div : b);
-    if (p.n_slots > 0) kvb = kvb < 0 ? 0 : (kvb < p.n_slots ? kvb : p.n_slots - 1);      // memory safety: never beyond the registered prompts
+    const int kvb = kv_batch(p, b);
 
     const f16* Qb = p.Q + (size_t)b * p.bsq + h * D;
     const f16* Kb = p.K + (size_t)kvb * p.bsk + h * D;
@@ -153,7 +87,7 @@ void attn_pipe80_kernel(AttnParams p) {
         const int key = idx / (G::CH + CC), ch = idx - key * (G::CH + CC);
         const int ld = isv ? p.ldv : p.ldk;
         if (j < 2 * G::NP && ch < G::CH) { gsrc[i] = (isv ? Vb : Kb) + (size_t)key * ld + ch * 8; ginc[i] = KT * ld; }
-        else { gsrc[i] = reinterpret_cast<const f16*>(isv ? g_vconst80 : g_kconst80); ginc[i] = 0; }
+        else { gsrc[i] = reinterpret_cast<const f16*>(isv ? g_vconst : g_kconst); ginc[i] = 0; }
     }
     auto piece_is_v = [&](int i) __attribute__((always_inline)) { return wid + 4 * i >= G::NP; };   // dummies count as V
     auto piece = [&](int i, int kst, int vst) __attribute__((always_inline)) {

@@ -25,43 +25,18 @@
 //   K(u+1), V(u) are read in I_{2u-1} (A) and I_{2u} (B);  their pieces were issued in the V(u-2) phases and are waited for
 //   (counted vmcnt) at the end of the V(u-1) phases, i.e. before barriers 2u-2 (A) and 2u-1 (B);  K(u+3) / V(u+2) overwrite the
 //   buffers of K(u) / V(u-1), last read by B in I_{2u-2}, and are issued no earlier than I_{2u-1}.
-#include "dm_kernels.h"
+#include "attention_common.h"
 
 namespace dm {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
 constexpr int D = 40;
-constexpr int KT = 64;                // keys per tile
 constexpr int QF = 2;                 // 16-query fragments per wave
-constexpr float RESCALE_THR = 8.0f;   // log2 units
-constexpr int RS = 96;                // LDS row stride: 5 real chunks + 1 constant chunk
-constexpr int TILE = KT * RS;         // 6144
-constexpr int KOFF = 0, VOFF = TILE + 32;        // 32 zero bytes behind each tile (K reads overrun a row by 32 B)
-constexpr int STAGE = 2 * (TILE + 32);           // 12352
-constexpr int KS = 2, EF = 3;
+constexpr int RS = Geo40::RS, TILE = Geo40::TILE, KOFF = Geo40::KOFF, VOFF = Geo40::VOFF, STAGE = Geo40::STAGE;   // 96, 6144, 0, 6176, 12352
+constexpr int KS = Geo40::KS, EF = Geo40::EF;   // 2, 3
 
-__device__ __attribute__((aligned(16))) const unsigned short g_kconst_pp[8] = {0x3C00, 0x3C00, 0, 0, 0, 0, 0, 0};
-__device__ __attribute__((aligned(16))) const unsigned short g_vconst_pp[8] = {0x3C00, 0, 0, 0, 0, 0, 0, 0};
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-#define PIN(x) asm volatile("" : "+v"(x))
 #define PHASE_BARRIER() do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_barrier" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
-
-__device__ __forceinline__ float vmax2(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ float vmax3(float a, float b, float c) { float r; asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
-
-template <int OFF>
-__device__ __forceinline__ void tr_read(u32x2& out, unsigned base) {
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(out) : "v"(base), "n"(OFF) : "memory");
-}
 
 // PRIO: 0 = no priorities; 1 = s_setprio 1 for the duration of every M phase; 2 = static s_setprio k for set k (the younger sets)
 __device__ long long g_attnpp_dbg[3 * 8];
@@ -87,22 +62,14 @@ void attn_pp_kernel(AttnParams p) {
     const bool setB = set == 1;   (void)setB;
     const int l15 = lane & 15;
     const int lg = lane >> 4;
-    // XCD-aware block order: one XCD walks consecutive (sample, head) pairs, so all query blocks of a pair share that XCD's L2
     const int nqb = (p.Tq + QBLK - 1) / QBLK;
-    int v;
-    {
-        const int nblk = gridDim.x, bid = blockIdx.x;
-        const int q = nblk >> 3, r = nblk & 7;
-        const int xcd = bid & 7, loc = bid >> 3;
-        v = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-    }
+    const int v = xcd_block_order();
     const int qblk = v % nqb;
     const int bh = v / nqb;
     const int h = bh % p.heads;
     const int b = bh / p.heads;
     const int q0 = qblk * QBLK + wid * (16 * QF);
-    int kvb = p.kv_slot ? p.kv_slot[b] : (p.slot_div > 0 ? b / p.slot_div : b);
-    if (p.n_slots > 0) kvb = kvb < 0 ? 0 : (kvb < p.n_slots ? kvb : p.n_slots - 1);
+    const int kvb = kv_batch(p, b);
 
     const f16* Qb = p.Q + (size_t)b * p.bsq + h * D;
     const f16* Kb = p.K + (size_t)kvb * p.bsk + h * D;
@@ -145,7 +112,7 @@ void attn_pp_kernel(AttnParams p) {
         const int key = idx / 6, ch = idx - key * 6;
         const int ld = isv ? p.ldv : p.ldk;
         if (ch < 5) { gsrc[i] = (isv ? Vb : Kb) + (size_t)key * ld + ch * 8; ginc[i] = KT * ld; }
-        else { gsrc[i] = reinterpret_cast<const f16*>(isv ? g_vconst_pp : g_kconst_pp); ginc[i] = 0; }
+        else { gsrc[i] = reinterpret_cast<const f16*>(isv ? g_vconst : g_kconst); ginc[i] = 0; }
     }
     bool abl_loop = false;
     // piece i of this wave: a K piece (-> K stage kst) or a V piece (-> V stage vst)

@@ -24,49 +24,18 @@
 // K/V ring with counted vmcnt, one barrier per tile, the lazy rescale (threshold 2^8) with one ballot per tile, scores
 // ping-ponged between two register tiles, exp2 / pack of tile t under the score MFMAs of tile t+1.  NOT bit-identical to
 // attention_pipe.hip: a score is now one 48-long fp32 chain instead of a 64-long one in another order.
-#include "dm_kernels.h"
+#include "attention_common.h"
 
 namespace dm {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
 constexpr int D = 40;
-constexpr int KT = 64;                // keys per tile
 constexpr int NT = 256;               // threads per block
 constexpr int QW = 32;                // queries per wave
-constexpr float RESCALE_THR = 8.0f;   // log2 units
-constexpr int RS = 96;                // LDS row stride: 5 real chunks + 1 constant chunk
-constexpr int TILE = KT * RS;         // 6144
-constexpr int KOFF = 0, VOFF = TILE + 32;
-constexpr int STAGE = 2 * (TILE + 32);           // 12352 (attention_pipe.hip's stage: the launcher shares its LDS size)
-constexpr int NSTG = 3;               // K/V ring depth: K is fetched three, V two tiles ahead of their use
-constexpr int EF = 3;                 // 16-row blocks of O^T (40 rows + the ones row)
-
-__device__ __attribute__((aligned(16))) const unsigned short g_kconst32[8] = {0x3C00, 0x3C00, 0, 0, 0, 0, 0, 0};
-__device__ __attribute__((aligned(16))) const unsigned short g_vconst32[8] = {0x3C00, 0, 0, 0, 0, 0, 0, 0};
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-#define PIN(x) asm volatile("" : "+v"(x))
-
-__device__ __forceinline__ float vmax2(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ float vmax3(float a, float b, float c) { float r; asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
-__device__ __forceinline__ void swap16(unsigned& a, unsigned& b) {      // a.row1 <-> b.row0, a.row3 <-> b.row2 (rows of 16 lanes)
-    const auto r = __builtin_amdgcn_permlane16_swap(a, b, false, false);
-    a = r[0]; b = r[1];
-}
-
-template <int OFF>
-__device__ __forceinline__ void tr_read(u32x2& out, unsigned base) {
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(out) : "v"(base), "n"(OFF) : "memory");
-}
+constexpr int RS = Geo40::RS, TILE = Geo40::TILE, KOFF = Geo40::KOFF, VOFF = Geo40::VOFF, STAGE = Geo40::STAGE;   // 96, 6144, 0, 6176, 12352
+constexpr int EF = Geo40::EF;         // 16-row blocks of O^T (40 rows + the ones row)
+static_assert(NSTG * STAGE == 3 * Geo40::STAGE, "the launcher asks for attn_pipe_kernel's LDS size: its stage, its ring depth");
 
 __global__ __launch_bounds__(NT, 3)
 void attn_qk32_kernel(AttnParams p) {
@@ -79,22 +48,14 @@ void attn_qk32_kernel(AttnParams p) {
     const int lg = lane >> 4;
     const int l31 = lane & 31;
     const int hh5 = lane >> 5;            // which 8 of the 16 k values of a 32x32x16 operand / which 4-key half of a C row group
-    // XCD-aware block order: one XCD walks consecutive (sample, head) pairs, so all query blocks of a pair share that XCD's L2
     const int nqb = (p.Tq + 4 * QW - 1) / (4 * QW);
-    int v;
-    {
-        const int nblk = gridDim.x, bid = blockIdx.x;
-        const int q = nblk >> 3, r = nblk & 7;
-        const int xcd = bid & 7, loc = bid >> 3;
-        v = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-    }
+    const int v = xcd_block_order();
     const int qblk = v % nqb;
     const int bh = v / nqb;
     const int h = bh % p.heads;
     const int b = bh / p.heads;
     const int q0 = qblk * (4 * QW) + wid * QW;
-    int kvb = p.kv_slot ? p.kv_slot[b] : (p.slot_div > 0 ? b / p.slot_div : b);
-    if (p.n_slots > 0) kvb = kvb < 0 ? 0 : (kvb < p.n_slots ? kvb : p.n_slots - 1);
+    const int kvb = kv_batch(p, b);
 
     const f16* Qb = p.Q + (size_t)b * p.bsq + h * D;
     const f16* Kb = p.K + (size_t)kvb * p.bsk + h * D;
@@ -135,7 +96,7 @@ void attn_qk32_kernel(AttnParams p) {
         const int ch = isv ? pch : (pch ^ ((row >> 3) & 1));
         const int ld = isv ? p.ldv : p.ldk;
         if (ch < 5) { gsrc[i] = (isv ? Vb : Kb) + (size_t)key * ld + ch * 8; ginc[i] = KT * ld; }
-        else { gsrc[i] = reinterpret_cast<const f16*>(isv ? g_vconst32 : g_kconst32); ginc[i] = 0; }
+        else { gsrc[i] = reinterpret_cast<const f16*>(isv ? g_vconst : g_kconst); ginc[i] = 0; }
     }
     auto piece_is_v = [&](int i) __attribute__((always_inline)) { return wid + 4 * i >= 6; };
     auto piece = [&](int i, int kst, int vst) __attribute__((always_inline)) {

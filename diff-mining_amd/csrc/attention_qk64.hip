@@ -19,42 +19,21 @@
 //   P5  PV(t) MFMAs of set 1                                  || set 1's lane-partial max
 // The lane-partial max runs as four independent v_max3 chains (key block x half), two steps per asm statement: fmax is exact and
 // order-free, and the chains no longer stall the issue on s_nops.
-#include "dm_kernels.h"
+#include "attention_common.h"
 
 namespace dm {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
 constexpr int D = 40;
-constexpr int KT = 64;                // keys per tile
 constexpr int NT = 256;               // threads per block
 constexpr int QS = 32;                // queries per set
 constexpr int NS = 2;                 // sets per wave
 constexpr int QW = NS * QS;           // queries per wave
-constexpr float RESCALE_THR = 8.0f;   // log2 units
-constexpr int RS = 96;                // LDS row stride: 5 real chunks + 1 constant chunk
-constexpr int TILE = KT * RS;         // 6144
-constexpr int KOFF = 0, VOFF = TILE + 32;
-constexpr int STAGE = 2 * (TILE + 32);           // 12352
-constexpr int NSTG = 3;               // K/V ring depth: K is fetched three, V two tiles ahead of their use
-constexpr int EF = 3;                 // 16-row blocks of O^T (40 rows + the ones row)
+constexpr int RS = Geo40::RS, TILE = Geo40::TILE, KOFF = Geo40::KOFF, VOFF = Geo40::VOFF, STAGE = Geo40::STAGE;   // 96, 6144, 0, 6176, 12352
+constexpr int EF = Geo40::EF;         // 16-row blocks of O^T (40 rows + the ones row)
+static_assert(NSTG * STAGE == 3 * Geo40::STAGE, "the launcher asks for attn_pipe_kernel's LDS size: its stage, its ring depth");
 
-__device__ __attribute__((aligned(16))) const unsigned short g_kconst64[8] = {0x3C00, 0x3C00, 0, 0, 0, 0, 0, 0};
-__device__ __attribute__((aligned(16))) const unsigned short g_vconst64[8] = {0x3C00, 0, 0, 0, 0, 0, 0, 0};
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-#define PIN(x) asm volatile("" : "+v"(x))
-
-__device__ __forceinline__ float vmax2(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ float vmax3(float a, float b, float c) { float r; asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
 // two independent chain steps in one asm statement: the hazard recognizer cannot see into an asm block and pads every boundary
 // between two of them with an s_nop, which independent v_max ops do not need
 __device__ __forceinline__ void vmax2x2(float& x, float& y, float a0, float a1, float b0, float b1) {
@@ -62,15 +41,6 @@ __device__ __forceinline__ void vmax2x2(float& x, float& y, float a0, float a1, 
 }
 __device__ __forceinline__ void vmax3x2(float& x, float& y, float a0, float a1, float b0, float b1) {
     asm("v_max3_f32 %0, %0, %2, %3\n\tv_max3_f32 %1, %1, %4, %5" : "+v"(x), "+v"(y) : "v"(a0), "v"(a1), "v"(b0), "v"(b1));
-}
-__device__ __forceinline__ void swap16(unsigned& a, unsigned& b) {      // a.row1 <-> b.row0, a.row3 <-> b.row2 (rows of 16 lanes)
-    const auto r = __builtin_amdgcn_permlane16_swap(a, b, false, false);
-    a = r[0]; b = r[1];
-}
-
-template <int OFF>
-__device__ __forceinline__ void tr_read(u32x2& out, unsigned base) {
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(out) : "v"(base), "n"(OFF) : "memory");
 }
 
 __global__ __launch_bounds__(NT, 2)
@@ -84,22 +54,14 @@ void attn_qk64_kernel(AttnParams p) {
     const int lg = lane >> 4;
     const int l31 = lane & 31;
     const int hh5 = lane >> 5;
-    // XCD-aware block order: one XCD walks consecutive (sample, head) pairs, so all query blocks of a pair share that XCD's L2
     const int nqb = (p.Tq + 4 * QW - 1) / (4 * QW);
-    int v;
-    {
-        const int nblk = gridDim.x, bid = blockIdx.x;
-        const int q = nblk >> 3, r = nblk & 7;
-        const int xcd = bid & 7, loc = bid >> 3;
-        v = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-    }
+    const int v = xcd_block_order();
     const int qblk = v % nqb;
     const int bh = v / nqb;
     const int h = bh % p.heads;
     const int b = bh / p.heads;
     const int q0 = qblk * (4 * QW) + wid * QW;       // set j: queries q0 + 32 j + l31
-    int kvb = p.kv_slot ? p.kv_slot[b] : (p.slot_div > 0 ? b / p.slot_div : b);
-    if (p.n_slots > 0) kvb = kvb < 0 ? 0 : (kvb < p.n_slots ? kvb : p.n_slots - 1);
+    const int kvb = kv_batch(p, b);
 
     const f16* Qb = p.Q + (size_t)b * p.bsq + h * D;
     const f16* Kb = p.K + (size_t)kvb * p.bsk + h * D;
@@ -138,7 +100,7 @@ void attn_qk64_kernel(AttnParams p) {
         const int ch = isv ? pch : (pch ^ ((row >> 3) & 1));
         const int ld = isv ? p.ldv : p.ldk;
         if (ch < 5) { gsrc[i] = (isv ? Vb : Kb) + (size_t)key * ld + ch * 8; ginc[i] = KT * ld; }
-        else { gsrc[i] = reinterpret_cast<const f16*>(isv ? g_vconst64 : g_kconst64); ginc[i] = 0; }
+        else { gsrc[i] = reinterpret_cast<const f16*>(isv ? g_vconst : g_kconst); ginc[i] = 0; }
     }
     auto piece_is_v = [&](int i) __attribute__((always_inline)) { return wid + 4 * i >= 6; };
     auto piece = [&](int i, int kst, int vst) __attribute__((always_inline)) {

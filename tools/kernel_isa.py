@@ -1,0 +1,72 @@
+#!/usr/bin/env python3
+"""One line per gfx950 kernel of the given translation units (default: all of build.SOURCES): its code-object metadata,
+its instruction count and the sha256 of its instruction stream.  Host only, no GPU.
+
+    python tools/kernel_isa.py [--dump DIR] [file.hip ...]
+
+Run it on two trees and `diff` the tables: a refactor that must not change device code shows equal lines.  The stream is
+what `hipcc -S --cuda-device-only` (build.FLAGS) prints between a kernel's label and its .Lfunc_end, without comments and
+assembler directives.  Two things are normalised before hashing, because renaming a constant changes them and nothing
+else: data-symbol names in @rel32 operands (replaced by the symbol's position in order of first use) and __hip_cuid_*.
+--dump DIR also writes each normalised stream to DIR/<file>.<kernel>.s, so that two trees can be compared line by line.
+"""
+import argparse
+import hashlib
+import importlib
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+build = importlib.import_module("diff-mining_amd.build")
+
+FIELDS = ["vgpr_count", "agpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size",
+          "group_segment_fixed_size", "kernarg_segment_size", "max_flat_workgroup_size"]
+
+
+def kernels(asm):
+    """[(name, {field: value}, [normalised instruction-stream lines])] of one device assembly text."""
+    meta = asm[asm.index("amdhsa.kernels:"):] if "amdhsa.kernels:" in asm else ""
+    out = []
+    for entry in re.split(r"^  - (?=\.)", meta, flags=re.M)[1:]:
+        f = dict(re.findall(r"^(?:    )?\.(\w+):\s+(\S+)$", entry, flags=re.M))
+        body = re.search(r"^%s:.*?\n(.*?)^\.Lfunc_end\d+:" % re.escape(f["name"]), asm, flags=re.M | re.S).group(1)
+        syms, lines = {}, []
+        for ln in body.splitlines():
+            ln = ln.split(";")[0].strip()
+            if not ln or (ln.startswith(".") and not ln.endswith(":")):      # comments, directives (.amdhsa_*, .p2align, ...)
+                continue
+            ln = re.sub(r"[\w.$]+(?=@rel32)", lambda m: "sym%d" % syms.setdefault(m.group(0), len(syms)), ln)
+            lines.append(re.sub(r"__hip_cuid_\w+", "__hip_cuid", ln))
+        out.append((f["name"], f, lines))
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--dump", metavar="DIR", help="write each normalised instruction stream to DIR")
+    ap.add_argument("files", nargs="*", default=build.SOURCES)
+    a = ap.parse_args()
+    if a.dump:
+        os.makedirs(a.dump, exist_ok=True)
+    with tempfile.TemporaryDirectory() as tmp:
+        for src in a.files:
+            s = os.path.join(tmp, "tu.s")
+            r = subprocess.run([build._hipcc()] + build.FLAGS + ["-S", "--cuda-device-only", "-o", s,
+                                                                 os.path.join(build.CSRC, os.path.basename(src))], capture_output=True, text=True)
+            if r.returncode != 0:
+                sys.exit("%s: hipcc failed\n%s%s" % (src, r.stdout, r.stderr))
+            for name, f, lines in kernels(open(s).read()):
+                text = "\n".join(lines) + "\n"
+                ninstr = sum(not ln.endswith(":") for ln in lines)
+                print(os.path.basename(src), name, " ".join("%s=%s" % (k, f.get(k, "?")) for k in FIELDS),
+                      "instrs=%d" % ninstr, "sha256=" + hashlib.sha256(text.encode()).hexdigest())
+                if a.dump:
+                    with open(os.path.join(a.dump, "%s.%s.s" % (os.path.basename(src), name)), "w") as o:
+                        o.write(text)
+
+
+if __name__ == "__main__":
+    main()
