@@ -4,7 +4,16 @@
 
 namespace dm {
 
-hipError_t launch_igemm_pers(const IGemmParams& p, hipStream_t s) { return launch_igemm_pers_t<false>(p, s); }
+hipError_t launch_igemm_pers(const IGemmParams& p, hipStream_t s) {
+    static std::atomic<uint64_t> attr_seen{0};
+    set_lds_once(attr_seen, PERS_LDS, {igemm_pers_kernel<EPI_PLAIN, false, PX_NONE>, igemm_pers_kernel<EPI_GEGLU, false, PX_NONE>,
+                                       igemm_pers_kernel<EPI_PLAIN, false, PX_TEMB>, igemm_pers_kernel<EPI_PLAIN, false, PX_RES>});
+    pers_kernel_t k = igemm_pers_kernel<EPI_PLAIN, false, PX_NONE>;
+    if (p.epi == EPI_GEGLU) k = igemm_pers_kernel<EPI_GEGLU, false, PX_NONE>;
+    else if (p.temb) k = igemm_pers_kernel<EPI_PLAIN, false, PX_TEMB>;
+    else if (p.res) k = igemm_pers_kernel<EPI_PLAIN, false, PX_RES>;
+    return launch_pers(k, PERS_LDS, pers_tiles(p), p, s);
+}
 
 #ifdef DM_IGEMM_TIMING
 extern "C" int dm_debug_pers_timing(long long* out) {

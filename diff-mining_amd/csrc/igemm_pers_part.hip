@@ -7,6 +7,11 @@
 
 namespace dm {
 
-hipError_t launch_igemm_pers_partial(const IGemmParams& p, hipStream_t s) { return launch_igemm_pers_partial_t(p, s); }
+// units = tiles * ksplit, fp32 partials (see EPI_PARTIAL); the caller runs the reduction afterwards
+hipError_t launch_igemm_pers_partial(const IGemmParams& p, hipStream_t s) {
+    static std::atomic<uint64_t> attr_seen{0};
+    set_lds_once(attr_seen, PERS_LDS, {igemm_pers_kernel<EPI_PARTIAL, false, PX_NONE>});
+    return launch_pers(igemm_pers_kernel<EPI_PARTIAL, false, PX_NONE>, PERS_LDS, pers_tiles(p) * p.ksplit, p, s);
+}
 
 }  // namespace dm

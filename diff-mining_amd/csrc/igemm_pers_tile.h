@@ -21,48 +21,21 @@
 // GEGLU, folded LayerNorm) is identical to igemm_big_tile.h / igemm_tile.h: results are bit-identical, so a
 // sample's output does not depend on which tile geometry its batch size selects.
 #pragma once
-#include "dm_kernels.h"
+#include "igemm_common.h"
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <type_traits>
 
 namespace dm {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef _Float16 half2_ __attribute__((ext_vector_type(2)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef _Float16 ln_half2 __attribute__((ext_vector_type(2)));
-typedef unsigned uintx2 __attribute__((ext_vector_type(2)));
-typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
-
 namespace {
 
-constexpr int BK = 64;
 #ifndef DM_TILE_SWZ
 #define DM_TILE_SWZ 8
 #endif
 constexpr int TILE_SWZ_G = DM_TILE_SWZ;       // pixel tiles per group of the wide layers' tile order (0 = channel-minor everywhere)
-
-// erf-GELU  x * Phi(x) = max(x, 0) - |x| * T(|x|),  T(a) = 0.5 * (1 - erf(a / sqrt 2)) by Abramowitz-Stegun 7.1.26
-// (|erf error| < 1.5e-7; measured over all 63 488 finite fp16 inputs: max |error| 3.3e-7, i.e. far below the fp16
-// rounding of the result): 1 rcp + 1 exp2 + 12 plain VALU instead of libm erff (~40 instructions), which dominated the
-// GEGLU epilogue (40 calls per lane per 256 x 320 tile).  The tail T is formed directly (no 1 - 1 cancellation for
-// negative x), the 0.5 lives in the coefficients and 1 / sqrt 2 in the constants, and the max / |x| form needs no
-// compare-and-select (r02: -2..3 % on the GEGLU launches against the x * (x < 0 ? T : 1 - T) form; a fused-multiply-add
-// form and an inline-asm max measured the same).
-__device__ __forceinline__ float gelu_erf(float x) {
-    const float ax = __builtin_fabsf(x);
-    const float t = __builtin_amdgcn_rcpf(__builtin_fmaf(0.3275911f * 0.70710678118654752440f, ax, 1.0f));
-    float poly = __builtin_fmaf(t, 0.5f * 1.061405429f, 0.5f * -1.453152027f);
-    poly = __builtin_fmaf(t, poly, 0.5f * 1.421413741f);
-    poly = __builtin_fmaf(t, poly, 0.5f * -0.284496736f);
-    poly = __builtin_fmaf(t, poly, 0.5f * 0.254829592f);
-    poly *= t;
-    const float e = __builtin_amdgcn_exp2f((x * x) * -0.72134752044448170368f);        // exp(-x^2 / 2)
-    return __builtin_fmaxf(x, 0.f) - ax * (poly * e);
-}
 
 __device__ __attribute__((aligned(256))) unsigned char g_zero_page_pers[1024];
 __device__ __attribute__((aligned(256))) unsigned char g_store_sink[8 * 64 * 16];      // one 16-byte slot per (wave, lane)
@@ -103,17 +76,6 @@ static inline hipError_t zero_page_addr(const void** out) {
     *out = z;
     return hipSuccess;
 }
-// IGemmParams::zero_page of this translation unit's zero page; the launchers call zero_page_addr() first and fail with its error
-static inline IGemmParams with_zero_page(const IGemmParams& p) {
-    IGemmParams q = p;
-    (void)zero_page_addr(&q.zero_page);
-    return q;
-}
-#define DM_REQUIRE_ZERO_PAGE() do { const void* _z; const hipError_t _r = zero_page_addr(&_z); if (_r != hipSuccess) return _r; } while (0)
-
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
 // Lane id straight from the hardware.  `asm volatile` on purpose: the k loop runs at 256 registers, and any per-lane
 // constant derived once at kernel entry is either kept live across it or spilled — and a spill reload waits on
 // vmcnt, i.e. behind the LDS-DMA in flight and the previous tile's stores.  Re-deriving the handful of lane
@@ -154,6 +116,221 @@ enum { PX_NONE = 0, PX_TEMB = 1, PX_RES = 2 };
 // igemm_splitk.hip then applies the fused epilogue's arithmetic.
 constexpr int EPI_PARTIAL = 2;
 
+// ---- what igemm_pers_kernel and the tap-reuse kernel (igemm_pers_tr.hip) share ---------------------------------------------
+constexpr int PERS_TP = 256, PERS_TC = 320;            // the block tile; 8 waves as 4 (pixels) x 2 (channels), wave tile 64 px x 2 x 80 ch
+constexpr int TICKET_WORD = 1020;                      // spare word of a vector slot's bias KiB: the block's next-tile ticket
+
+// stores per wave per tile (every wave issues all of them: rows beyond M go to the sink page); GNB: + 10 GroupNorm block-sum stores
+constexpr int pers_nstore(int EPI, bool GNB) { return EPI == EPI_PARTIAL ? 40 : EPI == EPI_GEGLU ? 16 : GNB ? 34 : 24; }
+
+// the wait at a tile's top (N = the previous tile's stores, which may still be in flight) and between k steps (N = 0)
+template <int N>
+__device__ __forceinline__ void wait_vmcnt_barrier() { asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" :: "n"(N) : "memory"); }
+
+// the ticket's word in vector slot `slot` (W: how the kernel reaches a volatile LDS word; AUXB: bytes of a slot)
+template <typename W, int AUXB>
+__device__ __forceinline__ W ticket_word(char* aux0, int slot) { return (W)(aux0 + slot * AUXB + TICKET_WORD); }
+
+// swizzled 16-byte chunk (in elements) of LDS-DMA lane ln.  (Where a kernel also needs the lane's row ln >> 3 it spells the two
+// together: through this function those streams change — register allocation only, but the gate is equal streams.)
+__device__ __forceinline__ int lds_chunk(int ln) { return ((ln & 7) ^ (ln >> 3)) * 8; }
+
+// a block is done: the last one resets the counters, so a launch finds and leaves them at zero
+__device__ __forceinline__ void tiles_finish(int* const& ctr) {
+    if (threadIdx.x == 0) {
+        if (atomicAdd(&ctr[CTR_DONE], 1) == (int)gridDim.x - 1) {
+#pragma unroll
+            for (int x = 0; x < 8; ++x) ctr[x * 32] = 0;
+            ctr[CTR_DONE] = 0;
+            __threadfence();
+        }
+    }
+}
+
+// bias (wave 0) and time-embedding row (wave 1) of the tile at (lp0, lc0) -> the vector slot `ax` by LDS-DMA (lanes past the
+// vector read the zero page); false for the other waves
+template <int EXTRA>
+__device__ __forceinline__ bool load_aux_bias_temb(const IGemmParams& p, char* ax, const int& wid, int lane, const char* zp, int lc0, int lp0, const int& OHW) {
+    if (wid == 0) {
+        const char* s = (p.bias && lane < PERS_TC / 8) ? reinterpret_cast<const char*>(p.bias + lc0) + lane * 16 : zp;
+        __builtin_amdgcn_global_load_lds((gptr_t)s, (lptr_t)(ax + AUX_BIAS), 16, 0, 0);
+        return true;
+    }
+    if (wid == 1) {
+        if (EXTRA == PX_TEMB) {
+            const int n = lp0 / OHW;
+            const char* s = (lane < PERS_TC / 8) ? reinterpret_cast<const char*>(p.temb + (size_t)n * p.temb_ld + lc0) + lane * 16 : zp;
+            __builtin_amdgcn_global_load_lds((gptr_t)s, (lptr_t)(ax + AUX_TEMB), 16, 0, 0);
+        }
+        return true;
+    }
+    return false;
+}
+
+// ---- epilogue: straight from the accumulators ---------------------------------------------------------------
+// GNB: also write the GroupNorm block sums of the output (IGemmParams::gn_blocks); AUXB: bytes of a vector slot; ph: UP4 parity class.
+// The kernel's per-wave values come by reference, as a lambda would capture them (by value the residual variants compile differently).
+template <int EPI, bool LN, int EXTRA, bool WS, bool UP4, bool GNB, int AUXB>
+__device__ __forceinline__ void pers_epilogue(const IGemmParams& p, floatx4 (&acc)[2][5][4], char* const& aux0, const int& wid, const int& wc,
+                                              const int& wp, int p0, int c0out, int slot, int ph) {
+    constexpr int CH = 2;
+    const char* ax = aux0 + slot * AUXB;
+    constexpr int OCH = (EPI == EPI_GEGLU) ? 40 : 80;          // output channels of one (wave, h) sub-tile
+    constexpr bool RES = (EXTRA == PX_RES);
+    const int c0o = (EPI == EPI_GEGLU) ? c0out / 2 : c0out;
+    // the lane id is re-read from the hardware inside every epilogue: anything derived from the kernel-wide `lane`
+    // is hoisted out of the tile loop by the compiler and then lives (or spills) across the k loop, which runs
+    // at 256 registers; a spill reload here would also sit behind the LDS-DMA just issued (vmcnt is in-order)
+    const int eln = hw_lane();
+    const int e15 = eln & 15, eg = eln >> 4;
+    f16* const sink = reinterpret_cast<f16*>(g_store_sink) + (wid * 64 + eln) * 8;
+    // residual of unit u = (h, j) in the layout of the stores: 16 channels of block eg (two half8) + block 4's quarter
+    // Residual variant, two phases: (A) every unit is converted / transposed into packed registers while ALL residual
+    // loads are issued (unit u+1's right after unit u's conversion freed its 20 accumulator registers), (B) add + store.
+    // Every load is older than every store (vmcnt retires in order: a load queued behind stores would wait for them),
+    // and the wait for the first residual — which also sits behind the LDS-DMA of the next tile's first k step —
+    // overlaps the conversion work instead of preceding it.
+    constexpr int NU = 4 * CH;
+    half8 rlo[RES ? NU : 1], rhi[RES ? NU : 1], plo[RES ? NU : 1], phi[RES ? NU : 1];
+    half4 r4[RES ? NU : 1], p4[RES ? NU : 1];
+    f16* ypu[RES ? NU : 1];
+    auto load_res = [&](int u) __attribute__((always_inline)) {
+        const int h = u >> 2, j = u & 3;
+        int m = p0 + wp * 64 + 16 * j + e15;
+        m = m < p.M ? m : p.M - 1;
+        const f16* rp = p.res + (size_t)m * p.ldres + c0o + wc * (OCH * CH) + h * OCH;
+        rlo[RES ? u : 0] = *reinterpret_cast<const half8*>(rp + 16 * eg);
+        rhi[RES ? u : 0] = *reinterpret_cast<const half8*>(rp + 16 * eg + 8);
+        r4[RES ? u : 0] = *reinterpret_cast<const half4*>(rp + 64 + 4 * eg);
+    };
+    if (RES) load_res(0);
+#pragma unroll
+    for (int h = 0; h < CH; ++h) {
+        // GroupNorm block sums of the (wave, h) sub-tile's 64 rows x 80 channels (time-embedding launches = conv1, norm2's input):
+        // ten channel pairs per lane, accumulated over the four row blocks j, then the fixed 16-lane tree (dm_kernels.h)
+        float gs[GNB ? 10 : 1], gq[GNB ? 10 : 1];
+        if constexpr (GNB) {
+#pragma unroll
+            for (int k = 0; k < 10; ++k) { gs[k] = 0.f; gq[k] = 0.f; }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int u = h * 4 + j;
+            const int pr = wp * 64 + 16 * j + e15;
+            const int m = p0 + pr;
+            // folded LayerNorm: y = rstd (acc - mean s) + t, evaluated as fma(rstd, acc, fma(-rstd mean, s, t)) — two fused
+            // operations per value instead of mul / sub / mul / add (r03: 4 of ~37 VALU instructions per GEGLU quad), and one
+            // rounding less; the 128-row tile (igemm_tile.h) uses the same form
+            float nrm = 0.f, rs = 1.f;
+            if (LN && !WS) {
+                const float2 st = *reinterpret_cast<const float2*>(ax + AUX_STATS + pr * 8);
+                rs = st.y; nrm = -(st.y * st.x);
+            }
+            constexpr int NWD = (EPI == EPI_GEGLU) ? 1 : 2;
+            unsigned R[4][NWD], R4[NWD];
+#pragma unroll
+            for (int i = 0; i < 5; ++i) {
+                const int ct = wc * 80 * CH + h * 80 + 16 * i + 4 * eg;          // tile-local GEMM channel
+                float v[4];
+                if (LN) {
+                    const floatx4 t4 = *reinterpret_cast<const floatx4*>(ax + AUX_LNT + ct * 4);
+                    const floatx4 s4 = *reinterpret_cast<const floatx4*>(ax + AUX_LNS + ct * 4);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) v[r] = __builtin_fmaf(rs, acc[h][i][j][r], __builtin_fmaf(nrm, s4[r], t4[r]));
+                } else {
+                    const half4 bv = *reinterpret_cast<const half4*>(ax + AUX_BIAS + ct * 2);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) v[r] = acc[h][i][j][r] + (float)bv[r];
+                }
+                unsigned w0, w1 = 0;
+                if (EPI == EPI_GEGLU) {
+                    const f16 h0 = (f16)v[0], h1 = (f16)v[1], g0 = (f16)v[2], g1 = (f16)v[3];
+                    const f16 q0 = (f16)gelu_erf((float)g0), q1 = (f16)gelu_erf((float)g1);
+                    const half2_ o = half2_{(f16)((float)h0 * (float)q0), (f16)((float)h1 * (float)q1)};
+                    w0 = __builtin_bit_cast(unsigned, o);
+                } else {
+                    half4 o = half4{(f16)v[0], (f16)v[1], (f16)v[2], (f16)v[3]};
+                    if ((EXTRA == PX_TEMB)) {
+                        const half4 tv = *reinterpret_cast<const half4*>(ax + AUX_TEMB + ct * 2);
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) o[r] = (f16)((float)o[r] + (float)tv[r]);
+                    }
+                    const uintx2 uu = __builtin_bit_cast(uintx2, o);
+                    w0 = uu[0]; w1 = uu[1];
+                }
+                if (i < 4) { R[i][0] = w0; if (NWD == 2) R[i][NWD - 1] = w1; }
+                else { R4[0] = w0; if (NWD == 2) R4[NWD - 1] = w1; }
+            }
+            transpose4<NWD>(R);            // lane group eg now holds quarters 0..3 of channel block eg
+            size_t orow = (size_t)m;
+            if constexpr (UP4) {                               // source-grid row -> its pixel of parity class ph in the [N][2H][2W] output
+                const int OHW = p.OH * p.OW;
+                const int n = m / OHW, rem = m - n * OHW;
+                const int oh = rem / p.OW, ow = rem - oh * p.OW;
+                orow = ((size_t)n * (2 * p.OH) + (2 * oh + (ph >> 1))) * (size_t)(2 * p.OW) + (2 * ow + (ph & 1));
+            }
+            f16* yp = (m < p.M) ? p.Y + orow * p.ldy + c0o + wc * (OCH * CH) + h * OCH : nullptr;
+            if (EPI == EPI_GEGLU) {
+                const uintx4 o8 = uintx4{R[0][0], R[1][0], R[2][0], R[3][0]};           // 8 output channels of block eg
+                *reinterpret_cast<uintx4*>(yp ? yp + 8 * eg : sink) = o8;
+                *reinterpret_cast<unsigned*>(yp ? yp + 32 + 2 * eg : sink) = R4[0];
+            } else {
+                half8 lo = __builtin_bit_cast(half8, uintx4{R[0][0], R[0][NWD - 1], R[1][0], R[1][NWD - 1]});
+                half8 hi = __builtin_bit_cast(half8, uintx4{R[2][0], R[2][NWD - 1], R[3][0], R[3][NWD - 1]});
+                half4 o4 = __builtin_bit_cast(half4, uintx2{R4[0], R4[NWD - 1]});
+                if (RES) {
+                    plo[RES ? u : 0] = lo; phi[RES ? u : 0] = hi; p4[RES ? u : 0] = o4; ypu[RES ? u : 0] = yp;
+                    if (u + 1 < NU) load_res(u + 1);
+                } else {
+                    *reinterpret_cast<half8*>(yp ? yp + 16 * eg : sink) = lo;
+                    *reinterpret_cast<half8*>(yp ? yp + 16 * eg + 8 : sink) = hi;
+                    *reinterpret_cast<half4*>(yp ? yp + 64 + 4 * eg : sink) = o4;
+                    if constexpr (GNB) {
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) {
+                            gn_pair_acc(gs[GNB ? 2 * i : 0], gq[GNB ? 2 * i : 0], R[i][0]);
+                            gn_pair_acc(gs[GNB ? 2 * i + 1 : 0], gq[GNB ? 2 * i + 1 : 0], R[i][NWD - 1]);
+                        }
+                        gn_pair_acc(gs[GNB ? 8 : 0], gq[GNB ? 8 : 0], R4[0]);
+                        gn_pair_acc(gs[GNB ? 9 : 0], gq[GNB ? 9 : 0], R4[NWD - 1]);
+                    }
+                }
+            }
+        }
+        if constexpr (GNB) {
+#pragma unroll
+            for (int k = 0; k < 10; ++k) { gs[k] = gn_row16_sum(gs[k]); gq[k] = gn_row16_sum(gq[k]); }
+            const int r0 = p0 + wp * 64;
+            // every lane issues the five stores (the vmcnt count at the next tile's top is per instruction): lanes other than e15 = 0,
+            // blocks beyond M and launches without a block buffer write their slot of the sink page
+            float* const fsink = reinterpret_cast<float*>(sink);
+            float* const gb = (p.gn_blocks && e15 == 0 && r0 < p.M) ? p.gn_blocks + (size_t)(r0 >> 6) * p.Cout + c0o + wc * (OCH * CH) + h * OCH : nullptr;
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                *reinterpret_cast<floatx4*>(gb ? gb + 16 * eg + 4 * i : fsink) = floatx4{gs[GNB ? 2 * i : 0], gq[GNB ? 2 * i : 0], gs[GNB ? 2 * i + 1 : 0], gq[GNB ? 2 * i + 1 : 0]};
+            *reinterpret_cast<floatx4*>(gb ? gb + 64 + 4 * eg : fsink) = floatx4{gs[GNB ? 8 : 0], gq[GNB ? 8 : 0], gs[GNB ? 9 : 0], gq[GNB ? 9 : 0]};
+        }
+    }
+    if (RES) {
+#pragma unroll
+        for (int u = 0; u < NU; ++u) {
+            half8 lo = plo[RES ? u : 0], hi = phi[RES ? u : 0];
+            half4 o4 = p4[RES ? u : 0];
+#pragma unroll
+            for (int r = 0; r < 8; ++r) {
+                lo[r] = (f16)((float)lo[r] + (float)rlo[RES ? u : 0][r]);
+                hi[r] = (f16)((float)hi[r] + (float)rhi[RES ? u : 0][r]);
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) o4[r] = (f16)((float)o4[r] + (float)r4[RES ? u : 0][r]);
+            f16* yp = ypu[RES ? u : 0];
+            *reinterpret_cast<half8*>(yp ? yp + 16 * eg : sink) = lo;
+            *reinterpret_cast<half8*>(yp ? yp + 16 * eg + 8 : sink) = hi;
+            *reinterpret_cast<half4*>(yp ? yp + 64 + 4 * eg : sink) = o4;
+        }
+    }
+}
+
 // 8 waves (2 per SIMD), wave tile 64 px x 160 ch in two 80-channel halves, <= 256 registers.  (A 16-wave form of the
 // same block tile — 64 x 80 wave tiles, <= 128 registers — was measured 1-5 % slower in r02: DESIGN.md §4b.)
 // WS (r03): per-SAMPLE weights and bias row — GroupNorm folded into a 1x1 convolution (IGemmParams::w_sample_stride): a tile
@@ -175,13 +352,13 @@ template <int EPI, bool LN, int EXTRA, bool WS = false, bool SC = false, bool UP
 __global__ __launch_bounds__(512, 2)
 void igemm_pers_kernel(IGemmParams p, int ntiles, int cset) {
     constexpr int WC = 2, CH = 2, NW = 8;
-    constexpr int TP = 256, TC = 320;
+    constexpr int TP = PERS_TP, TC = PERS_TC;
     constexpr int WBYTES = TC * 128, XBYTES = TP * 128, STAGE = WBYTES + XBYTES;
     constexpr int WI = TC / 8 / NW, XI = TP / 8 / NW;          // 5 + 4 LDS-DMA pieces (8 rows x 128 B) per wave per k step
     constexpr int NL = WI + XI;
-    // stores per wave per tile (every wave issues all of them: rows beyond M go to the sink page)
     constexpr bool PART = (EPI == EPI_PARTIAL);
-    constexpr int NSTORE = PART ? 40 : (EPI == EPI_GEGLU) ? 16 : (EXTRA == PX_TEMB) ? 34 : 24;      // time-embedding launches: + 10 GroupNorm block-sum stores
+    constexpr bool GNB = (EXTRA == PX_TEMB) && EPI == EPI_PLAIN;          // the time-embedding launches write GroupNorm block sums
+    constexpr int NSTORE = pers_nstore(EPI, GNB);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* const aux0 = smem + 2 * STAGE;
 
@@ -191,30 +368,20 @@ void igemm_pers_kernel(IGemmParams p, int ntiles, int cset) {
 
     // ---- this block's tiles: XCD x (= block % 8) owns a contiguous range; its blocks stride through it ----------
     const int tiles_c = p.Cout / TC;
-    // the first tile of a block is static (tstart + its index on the XCD); further ones come from the XCD's counter
+    // the first tile of a block is static (tstart + its index on the XCD); further ones come from the XCD's counter.  (These four
+    // lines and the accumulator zeroing below stay in each kernel: as shared functions they changed the register allocation.)
     int tile, tend, tdyn;
     const int xcd = blockIdx.x & 7;
     {
         const int nblk = gridDim.x;
         const int loc = blockIdx.x >> 3;
-        const int q = ntiles >> 3, r = ntiles & 7;
-        const int tstart = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-        tend = tstart + q + (xcd < r ? 1 : 0);
+        const int tstart = xcd_range_start(blockIdx.x, ntiles);
+        tend = tstart + (ntiles >> 3) + (xcd < (ntiles & 7) ? 1 : 0);
         tdyn = tstart + ((nblk - xcd + 7) >> 3);       // first dynamically handed-out tile of this XCD
         tile = tstart + loc;
     }
     int* const ctr = p.tile_ctr ? p.tile_ctr : &g_tile_ctr[cset][0];
-    auto finish = [&]() __attribute__((always_inline)) {
-        if (threadIdx.x == 0) {
-            if (atomicAdd(&ctr[CTR_DONE], 1) == (int)gridDim.x - 1) {
-#pragma unroll
-                for (int x = 0; x < 8; ++x) ctr[x * 32] = 0;
-                ctr[CTR_DONE] = 0;
-                __threadfence();
-            }
-        }
-    };
-    if (tile >= tend) { finish(); return; }
+    if (tile >= tend) { tiles_finish(ctr); return; }
 
     const int C1 = p.C1;
     const int C2 = p.Cin - C1;
@@ -226,7 +393,6 @@ void igemm_pers_kernel(IGemmParams p, int ntiles, int cset) {
     const int nk = ntaps * cpt / KSP + cpt_sc;                   // k steps of one unit, >= 4 (igemm_pers_ok)
     const int Ktot = ntaps * p.Cin + (SC ? p.Csc : 0);
     const int OHW = p.OH * p.OW;
-    constexpr bool temb_lds = (EXTRA == PX_TEMB);                // a tile lies inside one sample: its temb row goes through LDS
 
 
     // ---- load-side state of the tile whose operands are being fetched ---------------------------------------------
@@ -311,15 +477,14 @@ void igemm_pers_kernel(IGemmParams p, int ntiles, int cset) {
         if (p.OH == 2 * p.H && p.OW == 2 * p.W) { ih = uh >> 1; iw = uw >> 1; }      // exact 2x: floor(u * 0.5), no float math
         else {                                                                      // F.interpolate(size=...), odd latent sizes
             const float sh = (float)p.H / (float)p.OH, sw = (float)p.W / (float)p.OW;
-            ih = (int)floorf((float)uh * sh); ih = ih < p.H - 1 ? ih : p.H - 1;
-            iw = (int)floorf((float)uw * sw); iw = iw < p.W - 1 ? iw : p.W - 1;
+            ih = nearest_src(uh, sh, p.H);
+            iw = nearest_src(uw, sw, p.W);
         }
         return xnb + ih * p.W + iw;
     };
     auto set_src = [&](int tap, int cs) __attribute__((always_inline)) {
         const int dy = UP4 ? tap >> 1 : tap / 3, dx = UP4 ? tap & 1 : tap - dy * 3;
-        const int ln = hw_lane();
-        const int lrow = ln >> 3, lchunk = ((ln & 7) ^ lrow) * 8;
+        const int lchunk = lds_chunk(hw_lane());
 #pragma unroll
         for (int k = 0; k < XI; ++k) {
             const int pix = src_pixel(k, dy, dx);
@@ -359,16 +524,8 @@ void igemm_pers_kernel(IGemmParams p, int ntiles, int cset) {
         char* ax = aux0 + slot * AUX_BYTES;
         const int lane = hw_lane();
         const char* zp = reinterpret_cast<const char*>(p.zero_page) + lane * 16;
-        if (wid == 0) {
-            const char* s = (p.bias && lane < TC / 8) ? reinterpret_cast<const char*>(p.bias + lc0) + lane * 16 : zp;
-            __builtin_amdgcn_global_load_lds((gptr_t)s, (lptr_t)(ax + AUX_BIAS), 16, 0, 0);
-        } else if (wid == 1) {
-            if (temb_lds) {
-                const int n = lp0 / OHW;
-                const char* s = (lane < TC / 8) ? reinterpret_cast<const char*>(p.temb + (size_t)n * p.temb_ld + lc0) + lane * 16 : zp;
-                __builtin_amdgcn_global_load_lds((gptr_t)s, (lptr_t)(ax + AUX_TEMB), 16, 0, 0);
-            }
-        } else if (LN && wid < 8) {
+        if (load_aux_bias_temb<EXTRA>(p, ax, wid, lane, zp, lc0, lp0, OHW)) return;
+        if (LN && wid < 8) {
             // wid 2,3: ln_s halves; 4,5: ln_t halves; 6,7: row statistics halves (1 KiB = 256 floats / 128 rows each)
             const int part = (wid - 2) >> 1, half = (wid - 2) & 1;
             const char* s;
@@ -392,7 +549,7 @@ void igemm_pers_kernel(IGemmParams p, int ntiles, int cset) {
     // channels (logical chunks 4 half .. 4 half + 3 of the 64-channel slab, ascending) to (sum, sum of squares) in fp32 —
     // VALU work in the shadow of the MFMAs — and after the k loop the pair is combined into (mean, rstd) in the tile's
     // vector slot.  The order depends on the row only, never on the tile geometry or the batch (igemm_tile.h adds the same
-    // numbers in the same order).
+    // numbers in the same order: ln_stats_acc / ln_stats_finish, igemm_common.h).
     const bool ln_ink = LN && !WS && p.ln_stats == nullptr;
     float ln_s1 = 0.f, ln_s2 = 0.f;
 
@@ -407,7 +564,7 @@ void igemm_pers_kernel(IGemmParams p, int ntiles, int cset) {
         const int a_row_off = (wc * 80 * CH + l15) * 128;
         const int b_row_off = (wp * 64 + l15) * 128;
         const int koff0 = ((lg ^ (l15 & 7)) << 4), koff1 = (((4 + lg) ^ (l15 & 7)) << 4);
-        const int lchunk = ((ln & 7) ^ (ln >> 3)) * 8;
+        const int lchunk = lds_chunk(ln);
         half8 b0[4], b1[4], a[5];
 #pragma unroll
         for (int j = 0; j < 4; ++j) b0[j] = *reinterpret_cast<const half8*>(xt + b_row_off + j * 2048 + koff0);
@@ -444,13 +601,7 @@ void igemm_pers_kernel(IGemmParams p, int ntiles, int cset) {
                     if (ln_ink) {
                         const int c4 = (q - 1) * 2 + i;
                         const int row = (wid * 64 + ln) >> 1, hf = ln & 1;
-                        const half8 xv = *reinterpret_cast<const half8*>(xt + row * 128 + (((4 * hf + c4) ^ (row & 7)) << 4));
-#pragma unroll
-                        for (int k = 0; k < 8; k += 2) {          // v_dot2_f32_f16: two exact fp16 products + the fp32 accumulator per instruction
-                            const ln_half2 v2 = ln_half2{xv[k], xv[k + 1]};
-                            ln_s1 = __builtin_amdgcn_fdot2(v2, ln_half2{(_Float16)1.0f, (_Float16)1.0f}, ln_s1, false);
-                            ln_s2 = __builtin_amdgcn_fdot2(v2, v2, ln_s2, false);
-                        }
+                        ln_stats_acc(*reinterpret_cast<const half8*>(xt + row * 128 + (((4 * hf + c4) ^ (row & 7)) << 4)), ln_s1, ln_s2);
                     }
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -475,172 +626,12 @@ void igemm_pers_kernel(IGemmParams p, int ntiles, int cset) {
             }
     };
 
-    // ---- epilogue: straight from the accumulators ---------------------------------------------------------------
-    auto epilogue = [&](int p0, int c0out, int slot, int ph) __attribute__((always_inline)) {
-        const char* ax = aux0 + slot * AUX_BYTES;
-        constexpr int OCH = (EPI == EPI_GEGLU) ? 40 : 80;          // output channels of one (wave, h) sub-tile
-        constexpr bool RES = (EXTRA == PX_RES);
-        constexpr bool GNB = (EXTRA == PX_TEMB) && EPI == EPI_PLAIN;          // GroupNorm block sums (IGemmParams::gn_blocks)
-        const int c0o = (EPI == EPI_GEGLU) ? c0out / 2 : c0out;
-        // the lane id is re-read from the hardware inside every epilogue: anything derived from the kernel-wide `lane`
-        // is hoisted out of the tile loop by the compiler and then lives (or spills) across the k loop, which runs
-        // at 256 registers; a spill reload here would also sit behind the LDS-DMA just issued (vmcnt is in-order)
-        const int eln = hw_lane();
-        const int e15 = eln & 15, eg = eln >> 4;
-        f16* const sink = reinterpret_cast<f16*>(g_store_sink) + (wid * 64 + eln) * 8;
-        // residual of unit u = (h, j) in the layout of the stores: 16 channels of block eg (two half8) + block 4's quarter
-        // Residual variant, two phases: (A) every unit is converted / transposed into packed registers while ALL residual
-        // loads are issued (unit u+1's right after unit u's conversion freed its 20 accumulator registers), (B) add + store.
-        // Every load is older than every store (vmcnt retires in order: a load queued behind stores would wait for them),
-        // and the wait for the first residual — which also sits behind the LDS-DMA of the next tile's first k step —
-        // overlaps the conversion work instead of preceding it.
-        constexpr int NU = 4 * CH;
-        half8 rlo[RES ? NU : 1], rhi[RES ? NU : 1], plo[RES ? NU : 1], phi[RES ? NU : 1];
-        half4 r4[RES ? NU : 1], p4[RES ? NU : 1];
-        f16* ypu[RES ? NU : 1];
-        auto load_res = [&](int u) __attribute__((always_inline)) {
-            const int h = u >> 2, j = u & 3;
-            int m = p0 + wp * 64 + 16 * j + e15;
-            m = m < p.M ? m : p.M - 1;
-            const f16* rp = p.res + (size_t)m * p.ldres + c0o + wc * (OCH * CH) + h * OCH;
-            rlo[RES ? u : 0] = *reinterpret_cast<const half8*>(rp + 16 * eg);
-            rhi[RES ? u : 0] = *reinterpret_cast<const half8*>(rp + 16 * eg + 8);
-            r4[RES ? u : 0] = *reinterpret_cast<const half4*>(rp + 64 + 4 * eg);
-        };
-        if (RES) load_res(0);
-#pragma unroll
-        for (int h = 0; h < CH; ++h) {
-            // GroupNorm block sums of the (wave, h) sub-tile's 64 rows x 80 channels (time-embedding launches = conv1, norm2's input):
-            // ten channel pairs per lane, accumulated over the four row blocks j, then the fixed 16-lane tree (dm_kernels.h)
-            float gs[GNB ? 10 : 1], gq[GNB ? 10 : 1];
-            if constexpr (GNB) {
-#pragma unroll
-                for (int k = 0; k < 10; ++k) { gs[k] = 0.f; gq[k] = 0.f; }
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int u = h * 4 + j;
-                const int pr = wp * 64 + 16 * j + e15;
-                const int m = p0 + pr;
-                // folded LayerNorm: y = rstd (acc - mean s) + t, evaluated as fma(rstd, acc, fma(-rstd mean, s, t)) — two fused
-                // operations per value instead of mul / sub / mul / add (r03: 4 of ~37 VALU instructions per GEGLU quad), and one
-                // rounding less; the 128-row tile (igemm_tile.h) uses the same form
-                float nrm = 0.f, rs = 1.f;
-                if (LN && !WS) {
-                    const float2 st = *reinterpret_cast<const float2*>(ax + AUX_STATS + pr * 8);
-                    rs = st.y; nrm = -(st.y * st.x);
-                }
-                constexpr int NWD = (EPI == EPI_GEGLU) ? 1 : 2;
-                unsigned R[4][NWD], R4[NWD];
-#pragma unroll
-                for (int i = 0; i < 5; ++i) {
-                    const int ct = wc * 80 * CH + h * 80 + 16 * i + 4 * eg;          // tile-local GEMM channel
-                    float v[4];
-                    if (LN) {
-                        const floatx4 t4 = *reinterpret_cast<const floatx4*>(ax + AUX_LNT + ct * 4);
-                        const floatx4 s4 = *reinterpret_cast<const floatx4*>(ax + AUX_LNS + ct * 4);
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) v[r] = __builtin_fmaf(rs, acc[h][i][j][r], __builtin_fmaf(nrm, s4[r], t4[r]));
-                    } else {
-                        const half4 bv = *reinterpret_cast<const half4*>(ax + AUX_BIAS + ct * 2);
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) v[r] = acc[h][i][j][r] + (float)bv[r];
-                    }
-                    unsigned w0, w1 = 0;
-                    if (EPI == EPI_GEGLU) {
-                        const f16 h0 = (f16)v[0], h1 = (f16)v[1], g0 = (f16)v[2], g1 = (f16)v[3];
-                        const f16 q0 = (f16)gelu_erf((float)g0), q1 = (f16)gelu_erf((float)g1);
-                        const half2_ o = half2_{(f16)((float)h0 * (float)q0), (f16)((float)h1 * (float)q1)};
-                        w0 = __builtin_bit_cast(unsigned, o);
-                    } else {
-                        half4 o = half4{(f16)v[0], (f16)v[1], (f16)v[2], (f16)v[3]};
-                        if (temb_lds) {
-                            const half4 tv = *reinterpret_cast<const half4*>(ax + AUX_TEMB + ct * 2);
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) o[r] = (f16)((float)o[r] + (float)tv[r]);
-                        }
-                        const uintx2 uu = __builtin_bit_cast(uintx2, o);
-                        w0 = uu[0]; w1 = uu[1];
-                    }
-                    if (i < 4) { R[i][0] = w0; if (NWD == 2) R[i][NWD - 1] = w1; }
-                    else { R4[0] = w0; if (NWD == 2) R4[NWD - 1] = w1; }
-                }
-                transpose4<NWD>(R);            // lane group eg now holds quarters 0..3 of channel block eg
-                size_t orow = (size_t)m;
-                if constexpr (UP4) {                               // source-grid row -> its pixel of parity class ph in the [N][2H][2W] output
-                    const int n = m / OHW, rem = m - n * OHW;
-                    const int oh = rem / p.OW, ow = rem - oh * p.OW;
-                    orow = ((size_t)n * (2 * p.OH) + (2 * oh + (ph >> 1))) * (size_t)(2 * p.OW) + (2 * ow + (ph & 1));
-                }
-                f16* yp = (m < p.M) ? p.Y + orow * p.ldy + c0o + wc * (OCH * CH) + h * OCH : nullptr;
-                if (EPI == EPI_GEGLU) {
-                    const uintx4 o8 = uintx4{R[0][0], R[1][0], R[2][0], R[3][0]};           // 8 output channels of block eg
-                    *reinterpret_cast<uintx4*>(yp ? yp + 8 * eg : sink) = o8;
-                    *reinterpret_cast<unsigned*>(yp ? yp + 32 + 2 * eg : sink) = R4[0];
-                } else {
-                    half8 lo = __builtin_bit_cast(half8, uintx4{R[0][0], R[0][NWD - 1], R[1][0], R[1][NWD - 1]});
-                    half8 hi = __builtin_bit_cast(half8, uintx4{R[2][0], R[2][NWD - 1], R[3][0], R[3][NWD - 1]});
-                    half4 o4 = __builtin_bit_cast(half4, uintx2{R4[0], R4[NWD - 1]});
-                    if (RES) {
-                        plo[RES ? u : 0] = lo; phi[RES ? u : 0] = hi; p4[RES ? u : 0] = o4; ypu[RES ? u : 0] = yp;
-                        if (u + 1 < NU) load_res(u + 1);
-                    } else {
-                        *reinterpret_cast<half8*>(yp ? yp + 16 * eg : sink) = lo;
-                        *reinterpret_cast<half8*>(yp ? yp + 16 * eg + 8 : sink) = hi;
-                        *reinterpret_cast<half4*>(yp ? yp + 64 + 4 * eg : sink) = o4;
-                        if constexpr (GNB) {
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) {
-                                gn_pair_acc(gs[GNB ? 2 * i : 0], gq[GNB ? 2 * i : 0], R[i][0]);
-                                gn_pair_acc(gs[GNB ? 2 * i + 1 : 0], gq[GNB ? 2 * i + 1 : 0], R[i][NWD - 1]);
-                            }
-                            gn_pair_acc(gs[GNB ? 8 : 0], gq[GNB ? 8 : 0], R4[0]);
-                            gn_pair_acc(gs[GNB ? 9 : 0], gq[GNB ? 9 : 0], R4[NWD - 1]);
-                        }
-                    }
-                }
-            }
-            if constexpr (GNB) {
-#pragma unroll
-                for (int k = 0; k < 10; ++k) { gs[k] = gn_row16_sum(gs[k]); gq[k] = gn_row16_sum(gq[k]); }
-                const int r0 = p0 + wp * 64;
-                // every lane issues the five stores (the vmcnt count at the next tile's top is per instruction): lanes other than e15 = 0,
-                // blocks beyond M and launches without a block buffer write their slot of the sink page
-                float* const fsink = reinterpret_cast<float*>(sink);
-                float* const gb = (p.gn_blocks && e15 == 0 && r0 < p.M) ? p.gn_blocks + (size_t)(r0 >> 6) * p.Cout + c0o + wc * (OCH * CH) + h * OCH : nullptr;
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    *reinterpret_cast<floatx4*>(gb ? gb + 16 * eg + 4 * i : fsink) = floatx4{gs[GNB ? 2 * i : 0], gq[GNB ? 2 * i : 0], gs[GNB ? 2 * i + 1 : 0], gq[GNB ? 2 * i + 1 : 0]};
-                *reinterpret_cast<floatx4*>(gb ? gb + 64 + 4 * eg : fsink) = floatx4{gs[GNB ? 8 : 0], gq[GNB ? 8 : 0], gs[GNB ? 9 : 0], gq[GNB ? 9 : 0]};
-            }
-        }
-        if (RES) {
-#pragma unroll
-            for (int u = 0; u < NU; ++u) {
-                half8 lo = plo[RES ? u : 0], hi = phi[RES ? u : 0];
-                half4 o4 = p4[RES ? u : 0];
-#pragma unroll
-                for (int r = 0; r < 8; ++r) {
-                    lo[r] = (f16)((float)lo[r] + (float)rlo[RES ? u : 0][r]);
-                    hi[r] = (f16)((float)hi[r] + (float)rhi[RES ? u : 0][r]);
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) o4[r] = (f16)((float)o4[r] + (float)r4[RES ? u : 0][r]);
-                f16* yp = ypu[RES ? u : 0];
-                *reinterpret_cast<half8*>(yp ? yp + 16 * eg : sink) = lo;
-                *reinterpret_cast<half8*>(yp ? yp + 16 * eg + 8 : sink) = hi;
-                *reinterpret_cast<half4*>(yp ? yp + 64 + 4 * eg : sink) = o4;
-            }
-        }
-    };
-
     // ---- prologue: the first tile's k step 0 into stage 0, its vectors into slot 0; sources of k step 1 prepared ----
     set_tile(tile);
     load_aux(0);
     prepare();
     {
-        const int ln = hw_lane();
-        const int lchunk = ((ln & 7) ^ (ln >> 3)) * 8;
+        const int lchunk = lds_chunk(hw_lane());
 #pragma unroll
         for (int i = 0; i < NL; ++i) load_piece(0, i, lchunk);
     }
@@ -670,11 +661,8 @@ void igemm_pers_kernel(IGemmParams p, int ntiles, int cset) {
         // The tile's k step 0 (and its vectors) were requested BEFORE the previous epilogue's stores, so "at most
         // NSTORE outstanding" proves they have landed; every later k step waits for everything, which is where the
         // previous tile's stores must have drained (they had the epilogue's own run time plus one k step).
-        if (first) asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-        else if (NSTORE == 40) asm volatile("s_waitcnt vmcnt(40)\n\ts_barrier" ::: "memory");
-        else if (NSTORE == 34) asm volatile("s_waitcnt vmcnt(34)\n\ts_barrier" ::: "memory");
-        else if (NSTORE == 24) asm volatile("s_waitcnt vmcnt(24)\n\ts_barrier" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(16)\n\ts_barrier" ::: "memory");
+        if (first) wait_vmcnt_barrier<0>();
+        else wait_vmcnt_barrier<NSTORE>();
         first = false;
         PTICK(3);
         // next tile of this block: asked for now (one returning atomic by thread 0), published through LDS (a spare word
@@ -690,45 +678,28 @@ void igemm_pers_kernel(IGemmParams p, int ntiles, int cset) {
             // sources of stream step g + 1 (two ahead of the one just computed): from k step nk - 2 on they belong
             // to the next tile (without one the block re-requests its own first k steps: valid addresses, unused)
             if (kt == nk - 2) {
-                next = tdyn + *reinterpret_cast<volatile int*>(aux0 + slot * AUX_BYTES + 1020);
+                next = tdyn + *ticket_word<volatile int*, AUX_BYTES>(aux0, slot);
                 next = __builtin_amdgcn_readfirstlane(next);
                 has_next = next < tend;
                 set_tile(has_next ? next : tile);
                 if (has_next) load_aux(slot ^ 1);
             }
             prepare();
-            if (kt < nk - 1) asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+            if (kt < nk - 1) wait_vmcnt_barrier<0>();
             PTICK(1);
-            if (kt == 0 && threadIdx.x == 0) *reinterpret_cast<volatile int*>(aux0 + slot * AUX_BYTES + 1020) = ticket;
+            if (kt == 0 && threadIdx.x == 0) *ticket_word<volatile int*, AUX_BYTES>(aux0, slot) = ticket;
         }
         if (LN) {
             if (ln_ink) {
                 const int ln2 = hw_lane();
-                const float t1 = ln_s1 + __shfl_xor(ln_s1, 1), t2 = ln_s2 + __shfl_xor(ln_s2, 1);
-                const float mean = t1 / (float)p.Cin;
-                float var = t2 / (float)p.Cin - mean * mean;
-                var = var > 0.f ? var : 0.f;
-                if (mean * mean > LN_REDO_RATIO2 * var) {            // cancellation: exact second pass over this row (dm_kernels.h)
-                    int m = p0 + ((wid * 64 + ln2) >> 1);
-                    m = m < p.M ? m : p.M - 1;
-                    const int half_c = p.Cin >> 1;
-                    const f16* xr = p.X + (size_t)m * p.Cin + (ln2 & 1) * half_c;
-                    float q = 0.f;
-                    for (int c = 0; c < half_c; c += 8) {
-                        const half8 v = *reinterpret_cast<const half8*>(xr + c);
-#pragma unroll
-                        for (int k = 0; k < 8; ++k) { const float d = (float)v[k] - mean; q = __builtin_fmaf(d, d, q); }
-                    }
-                    var = (q + __shfl_xor(q, 1)) / (float)p.Cin;
-                }
-                if ((ln2 & 1) == 0)
-                    *reinterpret_cast<float2*>(aux0 + slot * AUX_BYTES + AUX_STATS + ((wid * 64 + ln2) >> 1) * 8) = float2{mean, rsqrtf(var + p.ln_eps)};
+                const float2 st = ln_stats_finish(p, ln_s1, ln_s2, p0 + ((wid * 64 + ln2) >> 1), ln2 & 1, true);
+                if ((ln2 & 1) == 0) *reinterpret_cast<float2*>(aux0 + slot * AUX_BYTES + AUX_STATS + ((wid * 64 + ln2) >> 1) * 8) = st;
                 ln_s1 = 0.f; ln_s2 = 0.f;
                 asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
             }
         }
         if constexpr (PART) epilogue_partial(p0, c0out, tile - rtile * KSP);
-        else epilogue(p0, c0out, slot, cur_ph);
+        else pers_epilogue<EPI, LN, EXTRA, WS, UP4, GNB, AUX_BYTES>(p, acc, aux0, wid, wc, wp, p0, c0out, slot, cur_ph);
         PTICK(2);
 #ifdef DM_IGEMM_TIMING
         dbg[4] += 1;
@@ -737,130 +708,38 @@ void igemm_pers_kernel(IGemmParams p, int ntiles, int cset) {
         tile = next;
         slot ^= 1;
     }
-    finish();
+    tiles_finish(ctr);
 #ifdef DM_IGEMM_TIMING
     if (blockIdx.x == 77 && threadIdx.x == 0)
         for (int i = 0; i < 5; ++i) g_pers_dbg[i] = dbg[i];
 #endif
 }
 
+// ---- host side: what every launcher of a persistent kernel does after its own argument checks ------------------------------
+constexpr size_t PERS_LDS = 2 * (size_t)(PERS_TP + PERS_TC) * 128 + 2 * AUX_BYTES;           // 160 KiB: two operand stages + two vector slots
+typedef void (*pers_kernel_t)(IGemmParams, int, int);
+
+inline int pers_tiles(const IGemmParams& p) { return ((p.M + PERS_TP - 1) / PERS_TP) * (p.Cout / PERS_TC); }
+
+// raises the dynamic-LDS limit of `kernels`, the first time on each device (hipFuncSetAttribute is per DEVICE, not per process)
+inline void set_lds_once(std::atomic<uint64_t>& seen, size_t lds, std::initializer_list<pers_kernel_t> kernels) {
+    if (first_use_on_device(seen))
+        for (pers_kernel_t k : kernels) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+}
+
+std::atomic<unsigned> g_launch_no{0};      // round robin over g_tile_ctr's sets: like them, one per translation unit
+
+// `units` tiles (or split-K units) on one block per CU, with this translation unit's zero page and its next counter set
+inline hipError_t launch_pers(pers_kernel_t kernel, size_t lds, int units, const IGemmParams& p, hipStream_t s) {
+    IGemmParams q = p;
+    const hipError_t r = zero_page_addr(&q.zero_page);
+    if (r != hipSuccess) return r;
+    const int n_cu = device_cu_count();
+    const int cset = (int)(g_launch_no.fetch_add(1) % CSETS);
+    launch_timed(kernel, dim3(units < n_cu ? units : n_cu), dim3(512), lds, s, q, units, cset);
+    return hipGetLastError();
+}
+
 }  // namespace
-
-template <bool LN>
-static hipError_t launch_igemm_pers_t(const IGemmParams& p, hipStream_t s) {
-    DM_REQUIRE_ZERO_PAGE();
-    constexpr int TP = 256, TC = 320;
-    constexpr size_t lds = 2 * (size_t)(TP + TC) * 128 + 2 * AUX_BYTES;           // 160 KiB: two operand stages + two vector slots
-    const int ntiles = ((p.M + TP - 1) / TP) * (p.Cout / TC);
-    const int n_cu = device_cu_count();
-    const int grid = ntiles < n_cu ? ntiles : n_cu;
-    static std::atomic<uint64_t> attr_seen{0};      // hipFuncSetAttribute is per DEVICE, not per process
-    if (first_use_on_device(attr_seen)) {
-        (void)hipFuncSetAttribute((const void*)igemm_pers_kernel<EPI_PLAIN, LN, PX_NONE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void*)igemm_pers_kernel<EPI_GEGLU, LN, PX_NONE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if constexpr (!LN) {
-            (void)hipFuncSetAttribute((const void*)igemm_pers_kernel<EPI_PLAIN, false, PX_TEMB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            (void)hipFuncSetAttribute((const void*)igemm_pers_kernel<EPI_PLAIN, false, PX_RES>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        }
-    }
-    static std::atomic<unsigned> launch_no{0};
-    const int cset = (int)(launch_no.fetch_add(1) % CSETS);
-    const dim3 g(grid), b(512);
-    if (p.epi == EPI_GEGLU) { launch_timed((igemm_pers_kernel<EPI_GEGLU, LN, PX_NONE>), g, b, lds, s, with_zero_page(p), ntiles, cset); return hipGetLastError(); }
-    if constexpr (!LN) {        // the folded-LayerNorm layers never carry a time embedding or a residual (igemm_pers_ok)
-        if (p.temb) { launch_timed((igemm_pers_kernel<EPI_PLAIN, false, PX_TEMB>), g, b, lds, s, with_zero_page(p), ntiles, cset); return hipGetLastError(); }
-        if (p.res) { launch_timed((igemm_pers_kernel<EPI_PLAIN, false, PX_RES>), g, b, lds, s, with_zero_page(p), ntiles, cset); return hipGetLastError(); }
-    }
-    launch_timed((igemm_pers_kernel<EPI_PLAIN, LN, PX_NONE>), g, b, lds, s, with_zero_page(p), ntiles, cset);
-    return hipGetLastError();
-}
-
-// the shortcut-in-conv2 variant; only igemm_pers_sc.hip defines DM_IGEMM_PERS_SC
-#ifdef DM_IGEMM_PERS_SC
-static hipError_t launch_igemm_pers_sc_t(const IGemmParams& p, hipStream_t s) {
-    DM_REQUIRE_ZERO_PAGE();
-    constexpr int TP = 256, TC = 320;
-    constexpr size_t lds = 2 * (size_t)(TP + TC) * 128 + 2 * AUX_BYTES;
-    if ((p.mode != IG_CONV3 && p.mode != IG_DENSE) || p.epi != EPI_PLAIN || p.ln_s || p.temb || p.X2 || !p.X3 || p.Csc <= 0 || p.Csc % BK ||
-        p.C3 % BK || (p.C3 < p.Csc && !p.X4) || p.Cout % TC != 0 || p.ksplit > 1) return hipErrorInvalidValue;
-    const int ntiles = ((p.M + TP - 1) / TP) * (p.Cout / TC);
-    const int n_cu = device_cu_count();
-    const int grid = ntiles < n_cu ? ntiles : n_cu;
-    static std::atomic<uint64_t> attr_seen{0};
-    if (first_use_on_device(attr_seen)) {
-        (void)hipFuncSetAttribute((const void*)igemm_pers_kernel<EPI_PLAIN, false, PX_NONE, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void*)igemm_pers_kernel<EPI_PLAIN, false, PX_RES, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    }
-    static std::atomic<unsigned> launch_no{0};
-    const int cset = (int)(launch_no.fetch_add(1) % CSETS);
-    if (p.res) launch_timed((igemm_pers_kernel<EPI_PLAIN, false, PX_RES, false, true>), dim3(grid), dim3(512), lds, s, with_zero_page(p), ntiles, cset);
-    else launch_timed((igemm_pers_kernel<EPI_PLAIN, false, PX_NONE, false, true>), dim3(grid), dim3(512), lds, s, with_zero_page(p), ntiles, cset);
-    return hipGetLastError();
-}
-#endif
-
-// the per-sample-weights variant (GroupNorm folded into proj_in); only igemm_pers_ws.hip defines DM_IGEMM_PERS_WS
-#ifdef DM_IGEMM_PERS_WS
-static hipError_t launch_igemm_pers_ws_t(const IGemmParams& p, hipStream_t s) {
-    DM_REQUIRE_ZERO_PAGE();
-    constexpr int TP = 256, TC = 320;
-    constexpr size_t lds = 2 * (size_t)(TP + TC) * 128 + 2 * AUX_BYTES;
-    if (p.mode != IG_DENSE || p.epi != EPI_PLAIN || !p.ln_t || p.w_sample_stride <= 0 || p.rows_per_sample <= 0 ||
-        p.rows_per_sample % TP != 0 || p.M % p.rows_per_sample != 0 || p.Cout % TC != 0 || p.res || p.temb) return hipErrorInvalidValue;
-    const int ntiles = (p.M / TP) * (p.Cout / TC);
-    const int n_cu = device_cu_count();
-    const int grid = ntiles < n_cu ? ntiles : n_cu;
-    static std::atomic<uint64_t> attr_seen{0};
-    if (first_use_on_device(attr_seen))
-        (void)hipFuncSetAttribute((const void*)igemm_pers_kernel<EPI_PLAIN, true, PX_NONE, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    static std::atomic<unsigned> launch_no{0};
-    const int cset = (int)(launch_no.fetch_add(1) % CSETS);
-    launch_timed((igemm_pers_kernel<EPI_PLAIN, true, PX_NONE, true>), dim3(grid), dim3(512), lds, s, with_zero_page(p), ntiles, cset);
-    return hipGetLastError();
-}
-#endif
-
-// Upsample2D + conv as four 2x2 convolutions on the source grid (template parameter UP4); only igemm_pers_up.hip defines DM_IGEMM_PERS_UP.
-// Always this kernel, for every batch size (no 128-row partner, no head / tail cut): a sample's bits cannot depend on its batch.
-#ifdef DM_IGEMM_PERS_UP
-static hipError_t launch_igemm_pers_up4_t(const IGemmParams& p, hipStream_t s) {
-    DM_REQUIRE_ZERO_PAGE();
-    constexpr int TP = 256, TC = 320;
-    constexpr size_t lds = 2 * (size_t)(TP + TC) * 128 + 2 * AUX_BYTES;
-    if (p.mode != IG_CONV2_UP4 || p.epi != EPI_PLAIN || p.ln_s || p.temb || p.res || p.X2 || p.X3 || p.ksplit > 1 || p.w_sample_stride ||
-        p.Cout % TC != 0 || p.Cin % BK != 0 || p.C1 != p.Cin || p.OH != p.H || p.OW != p.W || p.H < 1 || p.W < 1 || p.H > 511 || p.W > 511 ||
-        p.M < 2 || p.M != (p.M / (p.H * p.W)) * p.H * p.W || p.M / (p.H * p.W) > 8191) return hipErrorInvalidValue;
-    // 32-bit element offsets: activations (row * channels + chunk), the four weight matrices, and 4 x tiles in an int
-    if ((long long)p.M * p.Cin >= (1LL << 31) || 16LL * p.Cout * p.Cin >= (1LL << 32)) return hipErrorInvalidValue;
-    const int tpp = ((p.M + TP - 1) / TP) * (p.Cout / TC);
-    const int ntiles = 4 * tpp;
-    const int n_cu = device_cu_count();
-    const int grid = ntiles < n_cu ? ntiles : n_cu;
-    static std::atomic<uint64_t> attr_seen{0};
-    if (first_use_on_device(attr_seen))
-        (void)hipFuncSetAttribute((const void*)igemm_pers_kernel<EPI_PLAIN, false, PX_NONE, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    static std::atomic<unsigned> launch_no{0};
-    const int cset = (int)(launch_no.fetch_add(1) % CSETS);
-    launch_timed((igemm_pers_kernel<EPI_PLAIN, false, PX_NONE, false, false, true>), dim3(grid), dim3(512), lds, s, with_zero_page(p), ntiles, cset);
-    return hipGetLastError();
-}
-#endif
-
-// split-K form: units = tiles * ksplit, fp32 partials (see EPI_PARTIAL); the caller runs the reduction afterwards
-static hipError_t launch_igemm_pers_partial_t(const IGemmParams& p, hipStream_t s) {
-    DM_REQUIRE_ZERO_PAGE();
-    constexpr int TP = 256, TC = 320;
-    constexpr size_t lds = 2 * (size_t)(TP + TC) * 128 + 2 * AUX_BYTES;
-    const int units = ((p.M + TP - 1) / TP) * (p.Cout / TC) * p.ksplit;
-    const int n_cu = device_cu_count();
-    const int grid = units < n_cu ? units : n_cu;
-    static std::atomic<uint64_t> attr_seen{0};
-    if (first_use_on_device(attr_seen))
-        (void)hipFuncSetAttribute((const void*)igemm_pers_kernel<EPI_PARTIAL, false, PX_NONE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    static std::atomic<unsigned> launch_no{0};
-    const int cset = (int)(launch_no.fetch_add(1) % CSETS);
-    launch_timed((igemm_pers_kernel<EPI_PARTIAL, false, PX_NONE>), dim3(grid), dim3(512), lds, s, with_zero_page(p), units, cset);
-    return hipGetLastError();
-}
 
 }  // namespace dm

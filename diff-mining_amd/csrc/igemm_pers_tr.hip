@@ -27,10 +27,8 @@ typedef volatile __attribute__((address_space(3))) int* lds_word_t;    // a vola
 template <int EXTRA, int WIMG, bool UNROLL = false, bool UP = false>
 __global__ __launch_bounds__(512, 2)
 void igemm_pers_tr_kernel(IGemmParams p, int ntiles, int cset) {
-    constexpr int EPI = EPI_PLAIN;
-    constexpr bool LN = false, WS = false;
     constexpr int WC = 2, CH = 2, NW = 8;
-    constexpr int TP = 256, TC = 320;
+    constexpr int TP = PERS_TP, TC = PERS_TC;
     constexpr int WBYTES = TC * 128;
     constexpr int PITCH = WIMG + 2;                       // LDS rows per image row
     constexpr int IROWS = TP / WIMG;                      // image rows of a tile
@@ -43,7 +41,7 @@ void igemm_pers_tr_kernel(IGemmParams p, int ntiles, int cset) {
     // GroupNorm block sums of the output from the epilogue (IGemmParams::gn_blocks): the time-embedding launches (ResnetBlock2D.conv1)
     // of 64-pixel-wide images — the 128-, 32- and 16-pixel instantiations spill with the 20 extra accumulators (tools/kernel_spills.py)
     constexpr bool GNBK = (EXTRA == PX_TEMB) && WIMG == 64;
-    constexpr int NSTORE = GNBK ? 34 : 24;      // + 10 block-sum stores
+    constexpr int NSTORE = pers_nstore(EPI_PLAIN, GNBK);
     static_assert(XI == 5 && 2 * WBYTES + 2 * XBYTES + 2 * AUX_BYTES <= 160 * 1024, "LDS budget");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* const xs0 = smem + 2 * WBYTES;
@@ -55,29 +53,18 @@ void igemm_pers_tr_kernel(IGemmParams p, int ntiles, int cset) {
 
     // ---- this block's tiles: XCD x (= block % 8) owns a contiguous range; its blocks stride through it ----------
     const int tiles_c = p.Cout / TC;
-    int tile, tend, tdyn;
+    int tile, tend, tdyn;         // (kept in the kernel, like the accumulator zeroing below: igemm_pers_tile.h says why)
     const int xcd = blockIdx.x & 7;
     {
         const int nblk = gridDim.x;
         const int loc = blockIdx.x >> 3;
-        const int q = ntiles >> 3, r = ntiles & 7;
-        const int tstart = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-        tend = tstart + q + (xcd < r ? 1 : 0);
+        const int tstart = xcd_range_start(blockIdx.x, ntiles);
+        tend = tstart + (ntiles >> 3) + (xcd < (ntiles & 7) ? 1 : 0);
         tdyn = tstart + ((nblk - xcd + 7) >> 3);
         tile = tstart + loc;
     }
     int* const ctr = p.tile_ctr ? p.tile_ctr : &g_tile_ctr[cset][0];
-    auto finish = [&]() __attribute__((always_inline)) {
-        if (threadIdx.x == 0) {
-            if (atomicAdd(&ctr[CTR_DONE], 1) == (int)gridDim.x - 1) {
-#pragma unroll
-                for (int x = 0; x < 8; ++x) ctr[x * 32] = 0;
-                ctr[CTR_DONE] = 0;
-                __threadfence();
-            }
-        }
-    };
-    if (tile >= tend) { finish(); return; }
+    if (tile >= tend) { tiles_finish(ctr); return; }
 
     const int C1 = p.C1;
     const int C2 = p.Cin - C1;
@@ -85,7 +72,6 @@ void igemm_pers_tr_kernel(IGemmParams p, int ntiles, int cset) {
     const int ntrip = 3 * cpt;                                   // (dy, slab) pairs of a tile; k steps = 3 * ntrip
     const int Ktot = 9 * p.Cin;
     const int OHW = p.OH * p.OW;                                 // = H * W, a multiple of 256: a tile lies inside one sample
-    constexpr bool temb_lds = (EXTRA == PX_TEMB);
 
     // ---- load-side state -------------------------------------------------------------------------------------------
     int lp0 = 0, lc0 = 0;             // tile whose operands are being fetched
@@ -146,23 +132,14 @@ void igemm_pers_tr_kernel(IGemmParams p, int ntiles, int cset) {
         if (i == XI - 1 && wid >= XP - NW * (XI - 1)) return;                            // uniform per wave (i: run-time, uniform)
         lptr_t dst = (lptr_t)(xs0 + buf * XBYTES + (wid + i * NW) * 1024);
         const f16* a = (off >= 0) ? (xbase + (size_t)(unsigned)off)
-                                  : reinterpret_cast<const f16*>(p.zero_page) + ((ln & 7) ^ (ln >> 3)) * 8;
+                                  : reinterpret_cast<const f16*>(p.zero_page) + lds_chunk(ln);
         __builtin_amdgcn_global_load_lds((gptr_t)a, dst, 16, 0, 0);
     };
     auto load_aux = [&](int slot, int lc0, int lp0) __attribute__((always_inline)) {      // vectors of the tile at (lp0, lc0)
         char* ax = aux0 + slot * AUX_BYTES;
         const int lane = hw_lane();
         const char* zp = reinterpret_cast<const char*>(p.zero_page) + lane * 16;
-        if (wid == 0) {
-            const char* s = (p.bias && lane < TC / 8) ? reinterpret_cast<const char*>(p.bias + lc0) + lane * 16 : zp;
-            __builtin_amdgcn_global_load_lds((gptr_t)s, (lptr_t)(ax + AUX_BIAS), 16, 0, 0);
-        } else if (wid == 1) {
-            if (temb_lds) {
-                const int n = lp0 / OHW;
-                const char* s = (lane < TC / 8) ? reinterpret_cast<const char*>(p.temb + (size_t)n * p.temb_ld + lc0) + lane * 16 : zp;
-                __builtin_amdgcn_global_load_lds((gptr_t)s, (lptr_t)(ax + AUX_TEMB), 16, 0, 0);
-            }
-        }
+        (void)load_aux_bias_temb<EXTRA>(p, ax, wid, lane, zp, lc0, lp0, OHW);
     };
 
     floatx4 acc[CH][5][4];
@@ -233,158 +210,6 @@ void igemm_pers_tr_kernel(IGemmParams p, int ntiles, int cset) {
         }
     };
 
-    auto epilogue = [&](int p0, int c0out, int slot) __attribute__((always_inline)) {
-        const char* ax = aux0 + slot * AUX_BYTES;
-        constexpr int OCH = (EPI == EPI_GEGLU) ? 40 : 80;          // output channels of one (wave, h) sub-tile
-        constexpr bool RES = (EXTRA == PX_RES);
-        constexpr bool GNB = GNBK;
-        const int c0o = (EPI == EPI_GEGLU) ? c0out / 2 : c0out;
-        // the lane id is re-read from the hardware inside every epilogue: anything derived from the kernel-wide `lane`
-        // is hoisted out of the tile loop by the compiler and then lives (or spills) across the k loop, which runs
-        // at 256 registers; a spill reload here would also sit behind the LDS-DMA just issued (vmcnt is in-order)
-        const int eln = hw_lane();
-        const int e15 = eln & 15, eg = eln >> 4;
-        f16* const sink = reinterpret_cast<f16*>(g_store_sink) + (wid * 64 + eln) * 8;
-        // residual of unit u = (h, j) in the layout of the stores: 16 channels of block eg (two half8) + block 4's quarter
-        // Residual variant, two phases: (A) every unit is converted / transposed into packed registers while ALL residual
-        // loads are issued (unit u+1's right after unit u's conversion freed its 20 accumulator registers), (B) add + store.
-        // Every load is older than every store (vmcnt retires in order: a load queued behind stores would wait for them),
-        // and the wait for the first residual — which also sits behind the LDS-DMA of the next tile's first k step —
-        // overlaps the conversion work instead of preceding it.
-        constexpr int NU = 4 * CH;
-        half8 rlo[RES ? NU : 1], rhi[RES ? NU : 1], plo[RES ? NU : 1], phi[RES ? NU : 1];
-        half4 r4[RES ? NU : 1], p4[RES ? NU : 1];
-        f16* ypu[RES ? NU : 1];
-        auto load_res = [&](int u) __attribute__((always_inline)) {
-            const int h = u >> 2, j = u & 3;
-            int m = p0 + wp * 64 + 16 * j + e15;
-            m = m < p.M ? m : p.M - 1;
-            const f16* rp = p.res + (size_t)m * p.ldres + c0o + wc * (OCH * CH) + h * OCH;
-            rlo[RES ? u : 0] = *reinterpret_cast<const half8*>(rp + 16 * eg);
-            rhi[RES ? u : 0] = *reinterpret_cast<const half8*>(rp + 16 * eg + 8);
-            r4[RES ? u : 0] = *reinterpret_cast<const half4*>(rp + 64 + 4 * eg);
-        };
-        if (RES) load_res(0);
-#pragma unroll
-        for (int h = 0; h < CH; ++h) {
-            // GroupNorm block sums of the (wave, h) sub-tile's 64 rows x 80 channels (time-embedding launches = conv1, norm2's input):
-            // ten channel pairs per lane, accumulated over the four row blocks j, then the fixed 16-lane tree (dm_kernels.h)
-            float gs[GNB ? 10 : 1], gq[GNB ? 10 : 1];
-            if constexpr (GNB) {
-#pragma unroll
-                for (int k = 0; k < 10; ++k) { gs[k] = 0.f; gq[k] = 0.f; }
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int u = h * 4 + j;
-                const int pr = wp * 64 + 16 * j + e15;
-                const int m = p0 + pr;
-                // folded LayerNorm: y = rstd (acc - mean s) + t, evaluated as fma(rstd, acc, fma(-rstd mean, s, t)) — two fused
-                // operations per value instead of mul / sub / mul / add (r03: 4 of ~37 VALU instructions per GEGLU quad), and one
-                // rounding less; the 128-row tile (igemm_tile.h) uses the same form
-                float nrm = 0.f, rs = 1.f;
-                if (LN && !WS) {
-                    const float2 st = *reinterpret_cast<const float2*>(ax + AUX_STATS + pr * 8);
-                    rs = st.y; nrm = -(st.y * st.x);
-                }
-                constexpr int NWD = (EPI == EPI_GEGLU) ? 1 : 2;
-                unsigned R[4][NWD], R4[NWD];
-#pragma unroll
-                for (int i = 0; i < 5; ++i) {
-                    const int ct = wc * 80 * CH + h * 80 + 16 * i + 4 * eg;          // tile-local GEMM channel
-                    float v[4];
-                    if (LN) {
-                        const floatx4 t4 = *reinterpret_cast<const floatx4*>(ax + AUX_LNT + ct * 4);
-                        const floatx4 s4 = *reinterpret_cast<const floatx4*>(ax + AUX_LNS + ct * 4);
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) v[r] = __builtin_fmaf(rs, acc[h][i][j][r], __builtin_fmaf(nrm, s4[r], t4[r]));
-                    } else {
-                        const half4 bv = *reinterpret_cast<const half4*>(ax + AUX_BIAS + ct * 2);
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) v[r] = acc[h][i][j][r] + (float)bv[r];
-                    }
-                    unsigned w0, w1 = 0;
-                    if (EPI == EPI_GEGLU) {
-                        const f16 h0 = (f16)v[0], h1 = (f16)v[1], g0 = (f16)v[2], g1 = (f16)v[3];
-                        const f16 q0 = (f16)gelu_erf((float)g0), q1 = (f16)gelu_erf((float)g1);
-                        const half2_ o = half2_{(f16)((float)h0 * (float)q0), (f16)((float)h1 * (float)q1)};
-                        w0 = __builtin_bit_cast(unsigned, o);
-                    } else {
-                        half4 o = half4{(f16)v[0], (f16)v[1], (f16)v[2], (f16)v[3]};
-                        if (temb_lds) {
-                            const half4 tv = *reinterpret_cast<const half4*>(ax + AUX_TEMB + ct * 2);
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) o[r] = (f16)((float)o[r] + (float)tv[r]);
-                        }
-                        const uintx2 uu = __builtin_bit_cast(uintx2, o);
-                        w0 = uu[0]; w1 = uu[1];
-                    }
-                    if (i < 4) { R[i][0] = w0; if (NWD == 2) R[i][NWD - 1] = w1; }
-                    else { R4[0] = w0; if (NWD == 2) R4[NWD - 1] = w1; }
-                }
-                transpose4<NWD>(R);            // lane group eg now holds quarters 0..3 of channel block eg
-                f16* yp = (m < p.M) ? p.Y + (size_t)m * p.ldy + c0o + wc * (OCH * CH) + h * OCH : nullptr;
-                if (EPI == EPI_GEGLU) {
-                    const uintx4 o8 = uintx4{R[0][0], R[1][0], R[2][0], R[3][0]};           // 8 output channels of block eg
-                    *reinterpret_cast<uintx4*>(yp ? yp + 8 * eg : sink) = o8;
-                    *reinterpret_cast<unsigned*>(yp ? yp + 32 + 2 * eg : sink) = R4[0];
-                } else {
-                    half8 lo = __builtin_bit_cast(half8, uintx4{R[0][0], R[0][NWD - 1], R[1][0], R[1][NWD - 1]});
-                    half8 hi = __builtin_bit_cast(half8, uintx4{R[2][0], R[2][NWD - 1], R[3][0], R[3][NWD - 1]});
-                    half4 o4 = __builtin_bit_cast(half4, uintx2{R4[0], R4[NWD - 1]});
-                    if (RES) {
-                        plo[RES ? u : 0] = lo; phi[RES ? u : 0] = hi; p4[RES ? u : 0] = o4; ypu[RES ? u : 0] = yp;
-                        if (u + 1 < NU) load_res(u + 1);
-                    } else {
-                        *reinterpret_cast<half8*>(yp ? yp + 16 * eg : sink) = lo;
-                        *reinterpret_cast<half8*>(yp ? yp + 16 * eg + 8 : sink) = hi;
-                        *reinterpret_cast<half4*>(yp ? yp + 64 + 4 * eg : sink) = o4;
-                        if constexpr (GNB) {
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) {
-                                gn_pair_acc(gs[GNB ? 2 * i : 0], gq[GNB ? 2 * i : 0], R[i][0]);
-                                gn_pair_acc(gs[GNB ? 2 * i + 1 : 0], gq[GNB ? 2 * i + 1 : 0], R[i][NWD - 1]);
-                            }
-                            gn_pair_acc(gs[GNB ? 8 : 0], gq[GNB ? 8 : 0], R4[0]);
-                            gn_pair_acc(gs[GNB ? 9 : 0], gq[GNB ? 9 : 0], R4[NWD - 1]);
-                        }
-                    }
-                }
-            }
-            if constexpr (GNB) {
-#pragma unroll
-                for (int k = 0; k < 10; ++k) { gs[k] = gn_row16_sum(gs[k]); gq[k] = gn_row16_sum(gq[k]); }
-                const int r0 = p0 + wp * 64;
-                // every lane issues the five stores (the vmcnt count at the next tile's top is per instruction): lanes other than e15 = 0,
-                // blocks beyond M and launches without a block buffer write their slot of the sink page
-                float* const fsink = reinterpret_cast<float*>(sink);
-                float* const gb = (p.gn_blocks && e15 == 0 && r0 < p.M) ? p.gn_blocks + (size_t)(r0 >> 6) * p.Cout + c0o + wc * (OCH * CH) + h * OCH : nullptr;
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    *reinterpret_cast<floatx4*>(gb ? gb + 16 * eg + 4 * i : fsink) = floatx4{gs[GNB ? 2 * i : 0], gq[GNB ? 2 * i : 0], gs[GNB ? 2 * i + 1 : 0], gq[GNB ? 2 * i + 1 : 0]};
-                *reinterpret_cast<floatx4*>(gb ? gb + 64 + 4 * eg : fsink) = floatx4{gs[GNB ? 8 : 0], gq[GNB ? 8 : 0], gs[GNB ? 9 : 0], gq[GNB ? 9 : 0]};
-            }
-        }
-        if (RES) {
-#pragma unroll
-            for (int u = 0; u < NU; ++u) {
-                half8 lo = plo[RES ? u : 0], hi = phi[RES ? u : 0];
-                half4 o4 = p4[RES ? u : 0];
-#pragma unroll
-                for (int r = 0; r < 8; ++r) {
-                    lo[r] = (f16)((float)lo[r] + (float)rlo[RES ? u : 0][r]);
-                    hi[r] = (f16)((float)hi[r] + (float)rhi[RES ? u : 0][r]);
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) o4[r] = (f16)((float)o4[r] + (float)r4[RES ? u : 0][r]);
-                f16* yp = ypu[RES ? u : 0];
-                *reinterpret_cast<half8*>(yp ? yp + 16 * eg : sink) = lo;
-                *reinterpret_cast<half8*>(yp ? yp + 16 * eg + 8 : sink) = hi;
-                *reinterpret_cast<half4*>(yp ? yp + 64 + 4 * eg : sink) = o4;
-            }
-        }
-    };
-
     // ---- prologue: the first tile's k step 0 weights -> W stage 0, its first activation stage -> X stage 0, vectors -> slot 0 ----
     set_wtile(tile);
     set_xtile(tile);
@@ -415,9 +240,8 @@ void igemm_pers_tr_kernel(IGemmParams p, int ntiles, int cset) {
 
         // the tile's k step 0 weights, its first activation stage and its vectors were requested BEFORE the previous epilogue's
         // stores, so "at most NSTORE outstanding" proves they have landed (igemm_pers_tile.h)
-        if (first) asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-        else if (NSTORE == 34) asm volatile("s_waitcnt vmcnt(34)\n\ts_barrier" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(24)\n\ts_barrier" ::: "memory");
+        if (first) wait_vmcnt_barrier<0>();
+        else wait_vmcnt_barrier<NSTORE>();
         first = false;
         int ticket = 0;
         // thread 0; the block-sum instantiations re-derive it (threadIdx.x kept alive across their k loop is the register that spills)
@@ -436,22 +260,22 @@ void igemm_pers_tr_kernel(IGemmParams p, int ntiles, int cset) {
                 // the line (+ 64 - 2 Cin) / of the next line (+ 64)
                 step(g & 1, tg & 1, std::integral_constant<int, 0>{}, p.Cin);
                 ++g;
-                asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-                if (tr == 0 && thread0()) *(lds_word_t)(aux0 + slot * AUX_BYTES + 1020) = ticket;
+                wait_vmcnt_barrier<0>();
+                if (tr == 0 && thread0()) *ticket_word<lds_word_t, AUX_BYTES>(aux0, slot) = ticket;
                 step(g & 1, tg & 1, std::integral_constant<int, 1>{}, (cc == cpt - 1) ? BK : BK - 2 * p.Cin);
                 ++g;
                 if (last) {        // the weights of the NEXT tile's first k step are requested by this tile's last step
-                    next = tdyn + *(lds_word_t)(aux0 + slot * AUX_BYTES + 1020);
+                    next = tdyn + *ticket_word<lds_word_t, AUX_BYTES>(aux0, slot);
                     next = __builtin_amdgcn_readfirstlane(next);
                     has_next = next < tend;
                     set_wtile(has_next ? next : tile);
                 }
-                asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+                wait_vmcnt_barrier<0>();
                 step(g & 1, tg & 1, std::integral_constant<int, 2>{}, p.Cin);
                 ++g;
                 ++tg;
                 if (tr == ntrip - 2) {               // (the ticket was published after this tile's first k step; ntrip >= 15)
-                    int nx = tdyn + *(lds_word_t)(aux0 + slot * AUX_BYTES + 1020);
+                    int nx = tdyn + *ticket_word<lds_word_t, AUX_BYTES>(aux0, slot);
                     nx = __builtin_amdgcn_readfirstlane(nx);
                     const bool hn = nx < tend;
                     set_xtile(hn ? nx : tile);
@@ -459,7 +283,7 @@ void igemm_pers_tr_kernel(IGemmParams p, int ntiles, int cset) {
                 }
                 prepare_x();
                 if (++cc == cpt) cc = 0;
-                if (!last) asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+                if (!last) wait_vmcnt_barrier<0>();
             }
         } else {
         const int nk = 3 * ntrip;
@@ -471,7 +295,7 @@ void igemm_pers_tr_kernel(IGemmParams p, int ntiles, int cset) {
                 step(g & 1, tg & 1, dx, adv);
                 ++g;
                 if (dx == 1 && tr == ntrip - 1) {        // the weights of the NEXT tile's first k step are requested by this tile's last step
-                    next = tdyn + *(lds_word_t)(aux0 + slot * AUX_BYTES + 1020);
+                    next = tdyn + *ticket_word<lds_word_t, AUX_BYTES>(aux0, slot);
                     next = __builtin_amdgcn_readfirstlane(next);
                     has_next = next < tend;
                     set_wtile(has_next ? next : tile);
@@ -481,7 +305,7 @@ void igemm_pers_tr_kernel(IGemmParams p, int ntiles, int cset) {
                     // sources of the activation stage after the one just requested: from the second-to-last stage on they belong to the
                     // next tile (without one the block re-requests its own first stage: valid addresses, unused)
                     if (tr == ntrip - 2) {               // (the ticket was published after this tile's first k step; ntrip >= 15)
-                        int nx = tdyn + *(lds_word_t)(aux0 + slot * AUX_BYTES + 1020);
+                        int nx = tdyn + *ticket_word<lds_word_t, AUX_BYTES>(aux0, slot);
                         nx = __builtin_amdgcn_readfirstlane(nx);
                         const bool hn = nx < tend;
                         set_xtile(hn ? nx : tile);
@@ -491,16 +315,16 @@ void igemm_pers_tr_kernel(IGemmParams p, int ntiles, int cset) {
                     dx = 0; ++tr;
                     if (++cc == cpt) cc = 0;
                 } else ++dx;
-                if (kt < nk - 1) asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-                if (kt == 0 && thread0()) *(lds_word_t)(aux0 + slot * AUX_BYTES + 1020) = ticket;
+                if (kt < nk - 1) wait_vmcnt_barrier<0>();
+                if (kt == 0 && thread0()) *ticket_word<lds_word_t, AUX_BYTES>(aux0, slot) = ticket;
             }
         }
-        epilogue(p0, c0out, slot);
+        pers_epilogue<EPI_PLAIN, false, EXTRA, false, false, GNBK, AUX_BYTES>(p, acc, aux0, wid, wc, wp, p0, c0out, slot, 0);
         if (!has_next) break;
         tile = next;
         slot ^= 1;
     }
-    finish();
+    tiles_finish(ctr);
 }
 
 }  // namespace
@@ -525,48 +349,25 @@ template <> struct TrUnroll<PX_TEMB, 16> { static constexpr bool value = true; }
 #ifndef DM_TR_UP_UNROLL
 #define DM_TR_UP_UNROLL false
 #endif
-template <bool U>
-static hipError_t launch_tr_up64(const IGemmParams& p, hipStream_t s) {      // Upsample2D.conv onto a 64-pixel-wide image: bias only
-    constexpr size_t lds = 2 * (size_t)320 * 128 + 2 * (size_t)33 * 1024 + 2 * 2048;
-    const int ntiles = (p.M / 256) * (p.Cout / 320);
-    const int n_cu = device_cu_count();
-    static std::atomic<uint64_t> attr_seen{0};
-    if (first_use_on_device(attr_seen))
-        (void)hipFuncSetAttribute((const void*)igemm_pers_tr_kernel<PX_NONE, 64, U, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    static std::atomic<unsigned> launch_no{0};
-    const int cset = (int)(launch_no.fetch_add(1) % CSETS);
-    launch_timed((igemm_pers_tr_kernel<PX_NONE, 64, U, true>), dim3(ntiles < n_cu ? ntiles : n_cu), dim3(512), lds, s, with_zero_page(p), ntiles, cset);
-    return hipGetLastError();
-}
-
+// the kernel of (EXTRA, WIMG) with the k loop TrUnroll picks for it
 template <int EXTRA, int WIMG>
-static void launch_tr_k(const IGemmParams& p, int ntiles, int cset, dim3 g, size_t lds, hipStream_t s, bool set_attr) {
-    constexpr bool U = TrUnroll<EXTRA, WIMG>::value;
-    if (set_attr) (void)hipFuncSetAttribute((const void*)igemm_pers_tr_kernel<EXTRA, WIMG, U>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    else launch_timed((igemm_pers_tr_kernel<EXTRA, WIMG, U>), g, dim3(512), lds, s, with_zero_page(p), ntiles, cset);
-}
+constexpr pers_kernel_t tr_kernel = igemm_pers_tr_kernel<EXTRA, WIMG, TrUnroll<EXTRA, WIMG>::value>;
+
+template <int WIMG>
+constexpr size_t tr_lds = 2 * (size_t)PERS_TC * 128 + 2 * (size_t)(((PERS_TP / WIMG) * (WIMG + 2) + 7) / 8) * 1024 + 2 * 2048;      // weight + activation stages, vector slots
 
 template <int WIMG>
 static hipError_t launch_tr_w(const IGemmParams& p, hipStream_t s) {
-    constexpr int TP = 256, TC = 320;
-    constexpr int XP = ((TP / WIMG) * (WIMG + 2) + 7) / 8;
-    constexpr size_t lds = 2 * (size_t)TC * 128 + 2 * (size_t)XP * 1024 + 2 * 2048;
-    const int ntiles = (p.M / TP) * (p.Cout / TC);
-    const int n_cu = device_cu_count();
-    const int grid = ntiles < n_cu ? ntiles : n_cu;
-    const dim3 g(grid);
     static std::atomic<uint64_t> attr_seen{0};
-    if (first_use_on_device(attr_seen)) {
-        launch_tr_k<PX_NONE, WIMG>(p, 0, 0, g, lds, s, true);
-        launch_tr_k<PX_TEMB, WIMG>(p, 0, 0, g, lds, s, true);
-        launch_tr_k<PX_RES, WIMG>(p, 0, 0, g, lds, s, true);
-    }
-    static std::atomic<unsigned> launch_no{0};
-    const int cset = (int)(launch_no.fetch_add(1) % CSETS);
-    if (p.temb) launch_tr_k<PX_TEMB, WIMG>(p, ntiles, cset, g, lds, s, false);
-    else if (p.res) launch_tr_k<PX_RES, WIMG>(p, ntiles, cset, g, lds, s, false);
-    else launch_tr_k<PX_NONE, WIMG>(p, ntiles, cset, g, lds, s, false);
-    return hipGetLastError();
+    set_lds_once(attr_seen, tr_lds<WIMG>, {tr_kernel<PX_NONE, WIMG>, tr_kernel<PX_TEMB, WIMG>, tr_kernel<PX_RES, WIMG>});
+    return launch_pers(p.temb ? tr_kernel<PX_TEMB, WIMG> : p.res ? tr_kernel<PX_RES, WIMG> : tr_kernel<PX_NONE, WIMG>,
+                       tr_lds<WIMG>, (p.M / PERS_TP) * (p.Cout / PERS_TC), p, s);
+}
+
+static hipError_t launch_tr_up64(const IGemmParams& p, hipStream_t s) {      // Upsample2D.conv onto a 64-pixel-wide image: bias only
+    static std::atomic<uint64_t> attr_seen{0};
+    set_lds_once(attr_seen, tr_lds<64>, {igemm_pers_tr_kernel<PX_NONE, 64, DM_TR_UP_UNROLL, true>});
+    return launch_pers(igemm_pers_tr_kernel<PX_NONE, 64, DM_TR_UP_UNROLL, true>, tr_lds<64>, (p.M / PERS_TP) * (p.Cout / PERS_TC), p, s);
 }
 
 // shapes the tap-reuse tile takes (the caller has already established igemm_ko_layer(p))
@@ -577,9 +378,8 @@ bool igemm_pers_tr_ok(const IGemmParams& p) {
 }
 
 hipError_t launch_igemm_pers_tr(const IGemmParams& p, hipStream_t s) {
-    DM_REQUIRE_ZERO_PAGE();
     if (!igemm_ko_layer(p) || !igemm_pers_tr_ok(p)) return hipErrorInvalidValue;
-    if (p.mode == IG_CONV3_UP) return p.OW == 64 ? launch_tr_up64<DM_TR_UP_UNROLL>(p, s) : hipErrorInvalidValue;
+    if (p.mode == IG_CONV3_UP) return p.OW == 64 ? launch_tr_up64(p, s) : hipErrorInvalidValue;
     return p.OW == 128 ? launch_tr_w<128>(p, s) : p.OW == 64 ? launch_tr_w<64>(p, s) : p.OW == 32 ? launch_tr_w<32>(p, s) : launch_tr_w<16>(p, s);
 }
 

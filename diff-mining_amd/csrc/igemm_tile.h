@@ -3,39 +3,13 @@
 // 128/256/512).  Each instantiation lives in its own translation unit on purpose: co-compiling large
 // kernels perturbs the register allocation of both (measured).
 #pragma once
-#include "dm_kernels.h"
+#include "igemm_common.h"
 #include <cstdlib>
 #include <type_traits>
 
 namespace dm {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef _Float16 ln_half2 __attribute__((ext_vector_type(2)));
-
 namespace {
-
-constexpr int BK = 64;           // k per step (one tap, 64 input channels)
-
-// erf-GELU  x * Phi(x) = max(x, 0) - |x| * T(|x|),  T(a) = 0.5 * (1 - erf(a / sqrt 2)) by Abramowitz-Stegun 7.1.26
-// (|erf error| < 1.5e-7; measured over all 63 488 finite fp16 inputs: max |error| 3.3e-7, i.e. far below the fp16
-// rounding of the result): 1 rcp + 1 exp2 + 12 plain VALU instead of libm erff (~40 instructions), which dominated the
-// GEGLU epilogue (40 calls per lane per 256 x 320 tile).  The tail T is formed directly (no 1 - 1 cancellation for
-// negative x), the 0.5 lives in the coefficients and 1 / sqrt 2 in the constants, and the max / |x| form needs no
-// compare-and-select (r02: -2..3 % on the GEGLU launches against the x * (x < 0 ? T : 1 - T) form; a fused-multiply-add
-// form and an inline-asm max measured the same).
-__device__ __forceinline__ float gelu_erf(float x) {
-    const float ax = __builtin_fabsf(x);
-    const float t = __builtin_amdgcn_rcpf(__builtin_fmaf(0.3275911f * 0.70710678118654752440f, ax, 1.0f));
-    float poly = __builtin_fmaf(t, 0.5f * 1.061405429f, 0.5f * -1.453152027f);
-    poly = __builtin_fmaf(t, poly, 0.5f * 1.421413741f);
-    poly = __builtin_fmaf(t, poly, 0.5f * -0.284496736f);
-    poly = __builtin_fmaf(t, poly, 0.5f * 0.254829592f);
-    poly *= t;
-    const float e = __builtin_amdgcn_exp2f((x * x) * -0.72134752044448170368f);        // exp(-x^2 / 2)
-    return __builtin_fmaxf(x, 0.f) - ax * (poly * e);
-}
 
 // Epilogue staged through LDS: fragments (bias / time-embedding / GEGLU applied, rounded to fp16) are
 // written to an LDS tile [TP px][TCO ch] (row stride padded by 8 B: conflict-free ds_write_b64 /
@@ -107,7 +81,6 @@ __device__ __forceinline__ void epilogue_lds(const IGemmParams& p, floatx4 (&acc
                 if (EPI == EPI_GEGLU) {
                     const f16 h0 = (f16)v0, h1 = (f16)v1, g0 = (f16)v2, g1 = (f16)v3;
                     const f16 q0 = (f16)gelu_erf((float)g0), q1 = (f16)gelu_erf((float)g1);
-                    typedef _Float16 half2_ __attribute__((ext_vector_type(2)));
                     const half2_ o = half2_{(f16)((float)h0 * (float)q0), (f16)((float)h1 * (float)q1)};
                     const int ol = (cl >> 4) * 8 + 2 * lg;
                     *reinterpret_cast<half2_*>(smem + pr * ROWB + ol * 2) = o;
@@ -164,9 +137,6 @@ __device__ __forceinline__ void epilogue_lds(const IGemmParams& p, floatx4 (&acc
 
 __device__ __attribute__((aligned(256))) unsigned char g_zero_page[256];
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
 // WS: per-sample weights and bias row (GroupNorm folded into a 1x1 convolution), the 128-row partner of igemm_pers_tile.h's WS
 // variant: the same arithmetic (y = fp16(acc + t), the folded-LayerNorm epilogue with (mean, rstd) = (0, 1)).
 // SC: a ResNet block's conv_shortcut folded into its conv2 as extra k steps on a second tensor pair (igemm_pers_tile.h): the
@@ -195,13 +165,8 @@ void igemm_kernel(IGemmParams p) {
 
     const int tiles_c = p.Cout / TC;
     const int nblk = gridDim.x;
-    int v;
-    {
-        const int b = blockIdx.x;
-        const int q = nblk >> 3, r = nblk & 7;
-        const int xcd = b & 7, loc = b >> 3;
-        v = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-    }
+    const int b = blockIdx.x;
+    int v = xcd_range_start(b, nblk) + (b >> 3);              // consecutive tiles on one XCD (igemm_common.h)
     int split = 0;
     if (SPLIT) { split = v % p.ksplit; v = v / p.ksplit; }    // the parts of a tile sit next to each other (same XCD)
     const int pt = v / tiles_c;
@@ -265,8 +230,7 @@ void igemm_kernel(IGemmParams p) {
                 } else {
                     const int uh = xoh[k] + dy - 1, uw = xow[k] + dx - 1;
                     if (uh >= 0 && uh < p.OH && uw >= 0 && uw < p.OW) {
-                        int ih = (int)floorf((float)uh * sh); ih = ih < p.H - 1 ? ih : p.H - 1;
-                        int iw = (int)floorf((float)uw * sw); iw = iw < p.W - 1 ? iw : p.W - 1;
+                        const int ih = nearest_src(uh, sh, p.H), iw = nearest_src(uw, sw, p.W);
                         off = ((long long)xn[k] * p.H + ih) * p.W + iw;
                     }
                 }
@@ -390,7 +354,7 @@ void igemm_kernel(IGemmParams p) {
         *reinterpret_cast<float2*>(smem + 2 * STAGE + 1024 + 8 * TC + tid * 8) = *reinterpret_cast<const float2*>(p.ln_stats + 2 * (size_t)m);
     }
     // without a statistics kernel (p.ln_stats == nullptr): thread pair (2r, 2r + 1) accumulates row r of the tile from the k
-    // loop's LDS tiles — the same numbers in the same order as igemm_pers_tile.h (bit-identical statistics)
+    // loop's LDS tiles (ln_stats_acc / ln_stats_finish, igemm_common.h)
     const bool ln_ink = LN && !WS && p.ln_stats == nullptr && tid < 2 * TP;
     float ln_s1 = 0.f, ln_s2 = 0.f;
     prepare();
@@ -426,13 +390,7 @@ void igemm_kernel(IGemmParams p) {
             if (LN && g >= 2 && g < 6) {
                 if (ln_ink) {
                     const int row = tid >> 1, hf = tid & 1;
-                    const half8 xv = *reinterpret_cast<const half8*>(xt + row * 128 + (((4 * hf + (g - 2)) ^ (row & 7)) << 4));
-#pragma unroll
-                    for (int k = 0; k < 8; k += 2) {          // v_dot2_f32_f16: two exact fp16 products + the fp32 accumulator per instruction
-                        const ln_half2 v2 = ln_half2{xv[k], xv[k + 1]};
-                        ln_s1 = __builtin_amdgcn_fdot2(v2, ln_half2{(_Float16)1.0f, (_Float16)1.0f}, ln_s1, false);
-                        ln_s2 = __builtin_amdgcn_fdot2(v2, v2, ln_s2, false);
-                    }
+                    ln_stats_acc(*reinterpret_cast<const half8*>(xt + row * 128 + (((4 * hf + (g - 2)) ^ (row & 7)) << 4)), ln_s1, ln_s2);
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -461,25 +419,8 @@ void igemm_kernel(IGemmParams p) {
         return;
     }
     if (LN && !WS && p.ln_stats == nullptr) {
-        const float t1 = ln_s1 + __shfl_xor(ln_s1, 1), t2 = ln_s2 + __shfl_xor(ln_s2, 1);
-        const float mean = t1 / (float)p.Cin;
-        float var = t2 / (float)p.Cin - mean * mean;
-        var = var > 0.f ? var : 0.f;
-        if (ln_ink && mean * mean > LN_REDO_RATIO2 * var) {      // cancellation: exact second pass over this row (dm_kernels.h)
-            int m = p0 + (tid >> 1);
-            m = m < p.M ? m : p.M - 1;
-            const int half_c = p.Cin >> 1;
-            const f16* xr = p.X + (size_t)m * p.Cin + (tid & 1) * half_c;
-            float q = 0.f;
-            for (int c = 0; c < half_c; c += 8) {
-                const half8 v = *reinterpret_cast<const half8*>(xr + c);
-#pragma unroll
-                for (int k = 0; k < 8; ++k) { const float d = (float)v[k] - mean; q = __builtin_fmaf(d, d, q); }
-            }
-            var = (q + __shfl_xor(q, 1)) / (float)p.Cin;
-        }
-        if (ln_ink && (tid & 1) == 0)
-            *reinterpret_cast<float2*>(smem + 2 * STAGE + 1024 + 8 * TC + (tid >> 1) * 8) = float2{mean, rsqrtf(var + p.ln_eps)};
+        const float2 st = ln_stats_finish(p, ln_s1, ln_s2, p0 + (tid >> 1), tid & 1, ln_ink);
+        if (ln_ink && (tid & 1) == 0) *reinterpret_cast<float2*>(smem + 2 * STAGE + 1024 + 8 * TC + (tid >> 1) * 8) = st;
         __syncthreads();
     }
     epilogue_lds<EPI, 128 * WC, TP, TC, NI, LN>(p, acc, smem, smem + 2 * STAGE, p0, c0out, wc, wp, l15, lg, OHW);

@@ -6,8 +6,9 @@ its instruction count and the sha256 of its instruction stream.  Host only, no G
 
 Run it on two trees and `diff` the tables: a refactor that must not change device code shows equal lines.  The stream is
 what `hipcc -S --cuda-device-only` (build.FLAGS) prints between a kernel's label and its .Lfunc_end, without comments and
-assembler directives.  Two things are normalised before hashing, because renaming a constant changes them and nothing
-else: data-symbol names in @rel32 operands (replaced by the symbol's position in order of first use) and __hip_cuid_*.
+assembler directives.  Three things are normalised before hashing, because they change without the kernel changing:
+data-symbol names in @rel32 operands (replaced by the symbol's position in order of first use), __hip_cuid_*, and the
+function index in .LBB<index>_<n> branch labels (it counts the kernels emitted ahead of this one in the unit).
 --dump DIR also writes each normalised stream to DIR/<file>.<kernel>.s, so that two trees can be compared line by line.
 """
 import argparse
@@ -39,6 +40,7 @@ def kernels(asm):
             if not ln or (ln.startswith(".") and not ln.endswith(":")):      # comments, directives (.amdhsa_*, .p2align, ...)
                 continue
             ln = re.sub(r"[\w.$]+(?=@rel32)", lambda m: "sym%d" % syms.setdefault(m.group(0), len(syms)), ln)
+            ln = re.sub(r"\.LBB\d+_", ".LBB_", ln)
             lines.append(re.sub(r"__hip_cuid_\w+", "__hip_cuid", ln))
         out.append((f["name"], f, lines))
     return out

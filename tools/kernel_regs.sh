@@ -1,7 +1,7 @@
 #!/bin/bash
 # VGPRs / spilled VGPRs / scratch bytes of every kernel of the given translation units (default: all):
 #   bash tools/kernel_regs.sh [file.hip ...]
-# (the persistent igemm kernels sit at 236-256 VGPRs: check after any change to igemm_pers_tile.h; and compare the instruction
+# (the persistent igemm kernels sit at 236-256 VGPRs: check after any change to igemm_pers_tile.h / igemm_common.h; and compare the instruction
 #  stream of an untouched instantiation before / after: `python tools/kernel_isa.py [--dump DIR] [file.hip ...]` prints one line
 #  per kernel with its metadata, instruction count and stream hash — run it on both trees and diff the tables)
 cd "$(dirname "$0")/../diff-mining_amd/csrc" || exit 1
