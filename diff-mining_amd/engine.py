@@ -47,6 +47,8 @@ SIGNATURES = {
     "dm_typicality_image_batched": (_i32, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "dm_mine_patches": (_i32, [_vp] * 4 + [_i32] * 5 + [_vp] * 4),
     "dm_mine_parallel": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp] + [_i32] * 4 + [_vp] * 7),
+    "dm_clipmine_workspace_bytes": (_sz, [_i32, _i64, _i64]),
+    "dm_clipmine_rank": (_i32, [_vp, _vp, _vp, _i32, _vp, _i32, _vp] + [_i32] * 4 + [_vp, _sz] + [_vp] * 5),
     "dm_kmeans_workspace_bytes": (_i32, [_i32, _i32, _i32, _psz]),
     "dm_kmeans_fit": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _f32, _vp, _sz] + [_vp] * 5),
     "dm_cluster_rank": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _sz] + [_vp] * 5),

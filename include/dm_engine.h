@@ -233,6 +233,59 @@ int dm_mine_parallel(dm_engine* e, const void* maps_dev, const dm_mine_desc* des
                      void* median_out_dev, int32_t* boxes_out_dev, float* d_out_dev, float* set_d_out_dev, int32_t* count_out_dev,
                      void* stream);
 
+/* ---- CLIP baseline mining: token grid -> pooled score map -> eligible non-overlapping boxes -> box features (DESIGN.md 4u;
+ * csrc/clipmine.hip; clipmining/ranking.py:72-108 `dot_text_image`, clipmining/utils.py:75-94) ---------------------------------
+ * A stream-plus-workspace function (no engine handle).  Image b: projected patch tokens fp32 [P = gh*pw][E] at tokens +
+ * desc[b].token_offset floats (token p*pw + q, not normalised), image size (H, W); text: fp32 [2][E], used as given.
+ *   1. s[c][p][q] = sum_e text[c][e] tokens[pq][e] / |tokens[pq]|_2
+ *   2. m_c = avgpool_{kx x ky, stride 1}(bilinear_{align_corners=False}(s[c], (H, W))), computed as A s[c] B^T with the tables
+ *      A [OH = H-kx+1][gh] at tables_dev + a_offset and B [OW = W-ky+1][pw] at tables_dev + b_offset (fp32; A[i][p] = the mean over
+ *      image rows i ... i+kx-1 of the bilinear row weights onto token row p; built by the caller, clipmine.axis_weights), p then q
+ *      ascending.  D = m_0 - m_1 (DM_CLIPMINE_DIFF) or m_0 (DM_CLIPMINE_SIM).  Candidate (i, j) is the box (i, j, i+kx, j+ky),
+ *      x = rows.  maps_out_or_null: when given, D [OH][OW] is also written at maps_out + desc[b].map_offset floats.
+ *   3. Only the n = min(100 k_per_image, OH OW) candidates of largest D are candidates at all (the reference's topk before
+ *      get_non_overlapping).  Among equal values the lowest row-major index ranks first (torch.topk leaves ties undefined); a NaN
+ *      is never a candidate (torch.topk would rank it highest: non-finite tokens are outside the contract).
+ *   4. Up to k_per_image times: take the best eligible candidate still alive, drop every candidate with |i-i*| <= kx and
+ *      |j-j*| <= ky (inclusive, as dm_mine_patches); stop when no eligible candidate is alive.  boxes int32 [n_images][k][4],
+ *      d fp32 [n_images][k], count int32 [n_images]; unused slots hold -1 / NaN.
+ *   5. feats fp32 [n_images][k][E]: f[e] = sum_p sum_q A[i][p] B[j][q] tokens[pq][e] (the mean over the box of the bilinearly
+ *      upsampled raw tokens), then f / |f|_2; unused rows NaN.
+ * work: desc[b].work_offset floats into it image b owns 2 P + OH OW floats (contents do not matter; regions must not overlap);
+ * dm_clipmine_workspace_bytes(n_images, sum P, sum OH OW) leaves room to start every region on a multiple of 64 floats (0 = bad
+ * arguments).  fp32, fixed summation orders, no floating-point atomics: image b's results do not depend on the batch around it.
+ * Reads the descriptor table back once, so it synchronises `stream` before it launches.  Refused without a launch
+ * (DM_CLIPMINE_E_*): a window larger than an image or with exactly one side 1 (`pool` skips it) or OH OW >= 2^30, P != gh*pw or a
+ * grid side outside [1, DM_CLIPMINE_MAX_GRID], k_per_image outside [1, DM_MINE_MAX_K], E < 1, n_images outside [1, 65535], a
+ * negative offset, a region that
+ * does not fit in work_bytes, an unknown mode. */
+#define DM_CLIPMINE_MAX_GRID 1024
+#define DM_CLIPMINE_DIFF 0
+#define DM_CLIPMINE_SIM 1
+#define DM_CLIPMINE_E_NULL 1
+#define DM_CLIPMINE_E_IMAGES 2
+#define DM_CLIPMINE_E_E 3
+#define DM_CLIPMINE_E_K 4
+#define DM_CLIPMINE_E_MODE 5
+#define DM_CLIPMINE_E_WINDOW 6
+#define DM_CLIPMINE_E_GRID 7
+#define DM_CLIPMINE_E_OFFSET 8
+#define DM_CLIPMINE_E_WORK 9
+#define DM_CLIPMINE_E_HIP 10
+typedef struct dm_clipmine_desc {
+    int64_t token_offset;               /* floats from tokens to the image's [P][E] */
+    int64_t a_offset, b_offset;         /* floats from tables_dev to A [OH][gh] and B [OW][pw] */
+    int64_t work_offset;                /* floats from work to the image's scratch (2 P + OH OW floats) */
+    int64_t map_offset;                 /* floats from maps_out to the image's map (read only when maps_out is given) */
+    int32_t H, W;                       /* image size */
+    int32_t gh, pw, P;                  /* token grid, P = gh * pw */
+    int32_t reserved;
+} dm_clipmine_desc;
+size_t dm_clipmine_workspace_bytes(int n_images, int64_t total_tokens, int64_t total_candidates);
+int dm_clipmine_rank(void* stream, const void* tokens, const void* text, int E, const dm_clipmine_desc* desc_dev, int n_images,
+                     const void* tables_dev, int kx, int ky, int k_per_image, int mode, void* work, size_t work_bytes,
+                     void* maps_out_or_null, int32_t* boxes, float* d, int32_t* count, float* feats);
+
 /* ---- Clustering: scikit-learn's KMeans fit and the reference's ranked clusters (csrc/kmeans.hip) ------------------
  * Stream-plus-workspace functions (no engine handle): every launch goes to `stream`; `work` is device memory of at least
  * dm_kmeans_workspace_bytes(n, d, k) bytes whose contents do not matter.  They return 0 or one of the DM_KMEANS_E_* codes.
