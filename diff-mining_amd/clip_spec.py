@@ -166,3 +166,39 @@ def check_clip_vision_config(cfg: dict) -> None:
     proj = cfg.get("projection_dim", want.projection_dim)
     if proj != want.projection_dim:
         raise ValueError(f"projection_dim = {proj}, ViT-B/32 has {want.projection_dim}")
+
+
+# ---- the CLIP baseline's image tower (`CLIPModel.from_pretrained("geolocal/StreetCLIP")`, clipmining/ranking.py:58-70): ViT-L/14-336 -------
+# 577 tokens, 392 tensors, 304,293,888 parameters (vision_model + visual_projection)
+CLIP_L14_336_VISION = CLIPVisionConfig(hidden_size=1024, intermediate_size=4096, num_hidden_layers=24, num_attention_heads=16,
+                                       image_size=336, patch_size=14, projection_dim=768)
+
+
+def check_clip_tower_geometry(cfg: CLIPVisionConfig) -> None:
+    """What the fp32 net's configurable tower accepts (dm_f32_finalize_clip_tower applies the same rule), else ValueError: heads of 64
+    (the flash kernel's head_dim), widths the fp32 GEMM tiles (k a multiple of 32, outputs of 4), whole patches."""
+    if cfg.num_attention_heads < 1 or cfg.hidden_size != 64 * cfg.num_attention_heads:
+        raise ValueError(f"hidden_size {cfg.hidden_size} != 64 * num_attention_heads {cfg.num_attention_heads}")
+    if cfg.hidden_size % 32 or cfg.intermediate_size < 32 or cfg.intermediate_size % 32:
+        raise ValueError(f"hidden_size {cfg.hidden_size} and intermediate_size {cfg.intermediate_size} must be multiples of 32")
+    if cfg.projection_dim < 4 or cfg.projection_dim % 4:
+        raise ValueError(f"projection_dim {cfg.projection_dim} must be a multiple of 4")
+    if cfg.patch_size < 1 or cfg.image_size < cfg.patch_size or cfg.image_size % cfg.patch_size:
+        raise ValueError(f"image_size {cfg.image_size} is not a multiple of patch_size {cfg.patch_size}")
+    if cfg.num_hidden_layers < 1 or cfg.num_channels != 3:
+        raise ValueError(f"num_hidden_layers {cfg.num_hidden_layers} / num_channels {cfg.num_channels}")
+
+
+def check_clip_tower_config(cfg: dict, want: CLIPVisionConfig = CLIP_L14_336_VISION) -> None:
+    """`config.json` of a CLIPModel (e.g. StreetCLIP) or CLIPVisionModelWithProjection directory against the tower config `want`:
+    ValueError naming the first key that differs.  A CLIPModel config that leaves a vision key out means transformers' default for it."""
+    check_clip_tower_geometry(want)
+    v = cfg.get("vision_config", cfg)
+    for key in ("hidden_size", "intermediate_size", "num_hidden_layers", "num_attention_heads", "image_size", "patch_size"):
+        if key in v and v[key] != getattr(want, key):
+            raise ValueError(f"vision {key} = {v[key]}, the tower config has {getattr(want, key)}")
+    if v.get("hidden_act", "quick_gelu") != "quick_gelu":
+        raise ValueError(f"hidden_act {v['hidden_act']!r}: the tower implements quick_gelu")
+    proj = cfg.get("projection_dim", v.get("projection_dim", want.projection_dim))
+    if proj != want.projection_dim:
+        raise ValueError(f"projection_dim = {proj}, the tower config has {want.projection_dim}")

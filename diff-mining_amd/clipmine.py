@@ -21,9 +21,10 @@ The five steps, which `rank_patches_host` (numpy, float64 inside) and the kernel
                   around the peak, so an image often yields fewer than k_per_image boxes — that is the reference's behaviour.
   5. features     f[e] = sum_p sum_q A[i][p] B[j][q] tokens[pq][e], then f / |f|_2
 
-What is still missing: the tower that makes the tokens.  The reference uses StreetCLIP (ViT-L/14-336: 577 tokens, hidden 1024, then
-`post_layernorm` and `visual_projection` on the patch tokens) and its text projection; this project's fp32 net has ViT-B/32 only, so
-callers bring `tokens` and `text` from elsewhere (e.g. `transformers`).
+The tower that makes the tokens is on the fp32 net: `rank_images` runs the baseline from pixels — `center_crop`, the device
+preprocessing and StreetCLIP's ViT-L/14-336 image tower (`UNetEngineF32.clip_image_tokens`: 577 tokens, hidden 1024, `post_layernorm` and
+`visual_projection` on the patch tokens), `clip_text_embeds` for the two prompts, then `rank_device` on tensors that never leave the GPU.
+Callers that already hold `tokens` and `text` (e.g. from `transformers`) use `rank_patches`.
 """
 from __future__ import annotations
 
@@ -288,6 +289,56 @@ def rank_patches(tokens, text, image_sizes, pw=24, k_per_image=5, kx=64, ky=64, 
         got = rank_device(tokens[c0:c1], text, image_sizes[c0:c1], pws[c0:c1], k_per_image, kx, ky, mode, return_maps)
         bx, d, count = got[0].cpu().numpy(), got[1].cpu().numpy(), got[2].cpu().numpy()
         keep = np.arange(bx.shape[1])[None, :] < count[:, None]                          # [images, k], row-major = the row order
+        image.append(np.repeat(np.arange(c0, c1), count))
+        boxes.append(bx[keep])
+        Ds.append(d[keep])
+        feats.append(got[3][torch.from_numpy(keep).to(got[3].device)])
+        if return_maps:
+            maps += got[4]
+    out = (_rows(np.concatenate(image), np.concatenate(boxes), np.concatenate(Ds)), torch.cat(feats))
+    return out + (maps,) if return_maps else out
+
+
+def center_crop(image, size: int = 512) -> np.ndarray:
+    """torchvision's `CenterCrop(size)` (ranking.py:60) of a uint8 HWC image (or PIL image) at least `size` on both sides:
+    top = int(round((H - size) / 2.0)), left likewise, with Python's rounding (halves to even: 513 -> 0, 515 -> 2).  A smaller image
+    raises ValueError (torchvision would zero-pad it, which the reference's 512-px dataset never needs)."""
+    from .resample import check_clip_image
+    img = check_clip_image(image)
+    H, W = img.shape[:2]
+    size = int(size)
+    if size < 1 or H < size or W < size:
+        raise ValueError(f"center_crop: image {H}x{W} is smaller than the crop {size}x{size}")
+    top, left = int(round((H - size) / 2.0)), int(round((W - size) / 2.0))
+    return np.ascontiguousarray(img[top:top + size, left:left + size])
+
+
+def rank_images(net, images, input_ids, k_per_image=5, kx=64, ky=64, mode="diff", images_per_call=64, return_maps=False):
+    """The CLIP baseline from pixels (ranking.py:58-70, 110-125) on `net`, a `UNetEngineF32` holding the image tower
+    (load_clip_tower_state_dict) and the text tower with its projection (load_clip_state_dict): images = square uint8 HWC arrays /
+    PIL images (the reference's `center_crop(image, 512)`); input_ids [2, 77] = the tokenised [category, ""].  Device preprocessing
+    -> tower -> patch tokens (clip_image_tokens), the normalised text embeddings once (clip_text_embeds), then `rank_device` per
+    `images_per_call` images on tensors that never leave the GPU; (H, W) = each image's own size, the grid = the tower's.
+    Returns what `rank_patches` returns."""
+    import torch
+    from .resample import check_clip_tower_image
+    imgs = [check_clip_tower_image(a) for a in images]
+    if not imgs:
+        raise ValueError("clipmine: no images")
+    if int(images_per_call) < 1:
+        raise ValueError("clipmine: images_per_call < 1")
+    text = net.clip_text_embeds(input_ids, normalize=True)
+    if text.shape[0] != 2:
+        raise ValueError(f"clipmine: input_ids must hold the two prompts [category, \"\"], got {text.shape[0]} rows")
+    n = len(imgs)
+    image, boxes, Ds, feats, maps = [], [], [], [], []
+    for c0 in range(0, n, int(images_per_call)):
+        c1 = min(n, c0 + int(images_per_call))
+        tokens = net.clip_image_tokens(imgs[c0:c1])                                     # [m, G^2, E]
+        pw = int(round(tokens.shape[1] ** 0.5))
+        got = rank_device(list(tokens), text, [a.shape[:2] for a in imgs[c0:c1]], pw, k_per_image, kx, ky, mode, return_maps)
+        bx, d, count = got[0].cpu().numpy(), got[1].cpu().numpy(), got[2].cpu().numpy()
+        keep = np.arange(bx.shape[1])[None, :] < count[:, None]
         image.append(np.repeat(np.arange(c0, c1), count))
         boxes.append(bx[keep])
         Ds.append(d[keep])

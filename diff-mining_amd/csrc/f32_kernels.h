@@ -36,7 +36,7 @@ struct AttnParams {
     long long bsq, bsk, bsv, bso;      // batch strides in elements
     const int32_t* kv_slot = nullptr;  // optional: K/V batch index per sample (prompt slot), clamped to [0, n_slots)
     int n_slots = 0;
-    int B, heads, Tq, Tk, D;           // D in {40, 80, 160, 512}
+    int B, heads, Tq, Tk, D;           // D in {40, 64, 80, 160, 512}
     float scale;
 };
 hipError_t launch_attention(const AttnParams& p, hipStream_t s);
@@ -61,6 +61,16 @@ hipError_t launch_clip_patchify(const float* pix, int n, float* rows, hipStream_
 hipError_t launch_clip_tokens(const float* pe, const float* cls, const float* pos, int n, int C, float* x, hipStream_t s);
 hipError_t launch_clip_cls(const float* x, int n, int C, float* y, hipStream_t s);
 hipError_t launch_clip_l2norm(const float* x, int n, int C, float* y, hipStream_t s);
+// The configurable image tower's glue (clip_vision.hip; CLIP ViT-L/14-336: S = 336, PS = 14, T = 577): the processor WITHOUT the center
+// crop on square uint8 images (layout 0: [n][3][S][S], 1: patch rows [n*G^2][KPAD], columns >= 3 PS PS written as zeros); pixel_values ->
+// the same patch rows; class token + patch embeddings + positions [n*T][C]; post_layernorm of the patch tokens X [n][T][C] ->
+// Y [n*(T-1)][C] (CLS skipped); text pooling: the hidden row at the first maximum of each ids row, hidden [n][T][C] -> y [n][C]
+hipError_t launch_clip_tower_preprocess(const uint8_t* images, const dm_clip_pre_desc* desc, const int32_t* tables, int n, int S, int PS, int KPAD,
+                                        int layout, float* out, hipStream_t s);
+hipError_t launch_clip_tower_patchify(const float* pix, int n, int S, int PS, int KPAD, float* rows, hipStream_t s);
+hipError_t launch_clip_tower_tokens(const float* pe, const float* cls, const float* pos, int n, int T, int C, float* x, hipStream_t s);
+hipError_t launch_clip_tower_patch_ln(const float* X, int n, int T, int C, const float* gamma, const float* beta, float eps, float* Y, hipStream_t s);
+hipError_t launch_clip_eos_gather(const int32_t* ids, const float* hidden, int n, int T, int C, float* y, hipStream_t s);
 hipError_t launch_silu(const float* in, float* out, long long n, hipStream_t s);
 // Timesteps(dim, flip_sin_to_cos=True, downscale_freq_shift=0): out [B][dim] = [cos | sin]
 hipError_t launch_timestep_embed(const int64_t* t, int B, int dim, float* out, hipStream_t s);

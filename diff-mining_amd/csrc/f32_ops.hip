@@ -17,7 +17,7 @@ __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_ex
 // One block = 64 QT queries of one (sample, head): 4 waves x QT 16-query MFMA tiles (QT = 2; 1 for the VAE's head_dim 512).  Key tiles of KT keys are staged
 // in LDS as fp32 rows: K rows of D + 2 floats, V rows of D + 4 (r05).  The fragment reads are 4-byte reads, which the LDS serves 32
 // lanes at a time over 32 banks: a K read of lanes (c, g in {0, 1}) hits banks c * LDK + g, distinct for the 16 keys c iff LDK / 2 is
-// odd (D + 2: 42 / 82 / 162 / 514); the r04 stride D + 4 put keys c and c + 8 on one bank — a two-way conflict on every K read, the
+// odd (D + 2: 42 / 66 / 82 / 162 / 514); the r04 stride D + 4 put keys c and c + 8 on one bank — a two-way conflict on every K read, the
 // 30.7 % of profiles/r04_final_dift_f32_pmc.json.  A V read (rows 4 g + r, column c) wants the two rows 4 floats * odd * 4 apart:
 // D + 4 (rows r and r + 4 are 16 banks apart) is conflict-free and stays.
 //   S^T[key][query] = K Q^T   : A = K rows  (lane (c, g): key c, d = 4 s + g),  B = Q^T (query c, d = 4 s + g), D/4 k steps — head_dim
@@ -479,6 +479,7 @@ hipError_t launch_attention(const AttnParams& p, hipStream_t s) {
     if (p.B <= 0 || p.Tq <= 0 || p.Tk <= 0 || (p.ldq | p.ldk | p.ldv | p.ldo) % 4 != 0) return hipErrorInvalidValue;
     switch (p.D) {
         case 40: return launch_attn_t<40, 64, 2>(p, s);
+        case 64: return launch_attn_t<64, 64, 2>(p, s);         // CLIP ViT-L/14-336 image tower (577 tokens; LDK = 66: 33 odd, LD = 68 = 4 * 17; 68.7 KB for two stages)
         case 80: return launch_attn_t<80, 64, 2>(p, s);
         case 160: return launch_attn_t<160, 64, 2>(p, s);
         case 512: return launch_attn_t<512, 16, 1>(p, s);       // AutoencoderKL mid-block attention (one head)

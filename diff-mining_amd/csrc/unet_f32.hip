@@ -57,11 +57,21 @@ struct Vae32 {
 
 // CLIP ViT-L/14 text tower (`pipe.text_encoder` of the featuriser's fp32 pipeline: dift.py:197-199, 222-226)
 struct ClipLayer32 { Norm ln1, ln2; Conv qkv, o, fc1, fc2; };
-struct Clip32 { size_t tok = NONE, pos = NONE; ClipLayer32 layer[CL_LAYERS]; Norm final_ln; };
+struct Clip32 { size_t tok = NONE, pos = NONE; ClipLayer32 layer[CL_LAYERS]; Norm final_ln; Conv tproj; bool has_tproj = false; };     // tproj: optional text_projection [768][768]
 
 // CLIP ViT-B/32 image tower (`CLIPModel.get_image_features` of the clustering stage, cluster.py:224-231): same layer as the text tower
 constexpr int CV_T = 50, CV_NPATCH = 49, CV_KP = 3 * 32 * 32, CV_PROJ = 512, CV_TENSORS = 200, CV_CHUNK = 512;
 struct ClipVis32 { size_t cls = NONE, pos = NONE; Conv patch; Norm pre_ln; ClipLayer32 layer[CL_LAYERS]; Norm post_ln; Conv proj; };
+
+// The configurable image tower (dm_f32_finalize_clip_tower; product config CLIP ViT-L/14-336 = StreetCLIP's of the CLIP baseline,
+// clipmining/ranking.py:58-70): G x G patches, T = G^2 + 1 tokens, patch rows of KP = 3 PS PS values padded to KPAD (a multiple of 32:
+// gemm32's k step) with zeros on both sides of the product; heads of 64 on the MFMA flash kernel; every patch token projected
+constexpr int CT_CHUNK = 64;         // images per run: ~14.2 MB of fp32 activations per L/14-336 image at the fc2 GEMM; the arena of a full run measures 1011 MB
+struct ClipTower32 {
+    dm_clip_tower_config cfg{};
+    int G = 0, T = 0, KP = 0, KPAD = 0;
+    size_t cls = NONE, pos = NONE; Conv patch; Norm pre_ln; std::vector<ClipLayer32> layer; Norm post_ln; Conv proj;
+};
 
 struct T32 {                // NHWC fp32 activation in the arena
     size_t off = NONE; float* p = nullptr; int N = 0, H = 0, W = 0, C = 0;
@@ -87,6 +97,9 @@ struct dm_f32_net {
     // optional CLIP ViT-B/32 image tower (dm_f32_load_clip_vision_weight / dm_f32_finalize_clip_vision)
     dm::WeightSet<float> w_clipv;
     ClipVis32 clipv;
+    // optional configurable image tower (dm_f32_load_clip_tower_weight / dm_f32_finalize_clip_tower), beside the ViT-B/32 one
+    dm::WeightSet<float> w_clipt;
+    ClipTower32 clipt;
     Conv conv_in, conv_out, time1, time2, tproj_all;
     Norm norm_out;
     DownB down[NB]; Res mid_res[2]; Tfm mid_tf; UpB up[NB];
@@ -232,13 +245,13 @@ int pack_res(Packer32& P, const std::string& name, int cin, int cout, Res* r) {
     P.tb.insert(P.tb.end(), b->data.begin(), b->data.end());
     return pack_vae_res(P, name, cin, cout, r);
 }
-int pack_clip_layer(Packer32& P, const std::string& b, ClipLayer32* L) {       // CLIPEncoderLayer, text and image tower alike
-    DM_TRY(pack_norm(P, b + ".layer_norm1", CL_H, &L->ln1));
-    DM_TRY(pack_qkv(P, {b + ".self_attn.q_proj", b + ".self_attn.k_proj", b + ".self_attn.v_proj"}, CL_H, &L->qkv));
-    DM_TRY(pack_dense(P, b + ".self_attn.out_proj", CL_H, CL_H, false, true, &L->o));
-    DM_TRY(pack_norm(P, b + ".layer_norm2", CL_H, &L->ln2));
-    DM_TRY(pack_dense(P, b + ".mlp.fc1", CL_F, CL_H, false, true, &L->fc1));
-    return pack_dense(P, b + ".mlp.fc2", CL_H, CL_F, false, true, &L->fc2);
+int pack_clip_layer(Packer32& P, const std::string& b, ClipLayer32* L, int H = CL_H, int F = CL_F) {       // CLIPEncoderLayer, text and image towers alike
+    DM_TRY(pack_norm(P, b + ".layer_norm1", H, &L->ln1));
+    DM_TRY(pack_qkv(P, {b + ".self_attn.q_proj", b + ".self_attn.k_proj", b + ".self_attn.v_proj"}, H, &L->qkv));
+    DM_TRY(pack_dense(P, b + ".self_attn.out_proj", H, H, false, true, &L->o));
+    DM_TRY(pack_norm(P, b + ".layer_norm2", H, &L->ln2));
+    DM_TRY(pack_dense(P, b + ".mlp.fc1", F, H, false, true, &L->fc1));
+    return pack_dense(P, b + ".mlp.fc2", H, F, false, true, &L->fc2);
 }
 int pack_tfm(Packer32& P, const std::string& name, int c, Tfm* t) {
     dm_f32_net* e = P.e;
@@ -419,6 +432,28 @@ struct Fwd32 {
         *x = x2;
         return 0;
     }
+    // the same layer at any width with heads of 64, x [n * T][H]: the attention runs on the MFMA flash kernel (attn32_kernel<64>) over
+    // the stacked q|k|v rows — a whole-sequence-per-block kernel does not hold the tower's 577 tokens; scale 1/8 exact
+    int tower_layer(const ClipLayer32& L, int n, int T, int H, int heads, int Fi, T32* x) {
+        const int M = n * T;
+        T32 h, qkv, a, x1, f, x2;
+        DM_TRY(layernorm(L.ln1, *x, &h));
+        DM_TRY(dense(L.qkv, h, nullptr, nullptr, &qkv));
+        free(h);
+        DM_TRY(alloc(&a, 1, 1, M, H));
+        if (!dry) DM_TRY(attention(qkv.p, 3 * H, (long long)T * 3 * H, qkv.p + H, qkv.p + 2 * H, 3 * H, (long long)T * 3 * H, nullptr, n, T, T, H, a.p, heads));
+        free(qkv);
+        DM_TRY(dense(L.o, a, nullptr, x, &x1));
+        free(a); free(*x);
+        DM_TRY(layernorm(L.ln2, x1, &h));
+        DM_TRY(dense(L.fc1, h, nullptr, nullptr, &f));
+        free(h);
+        if (!dry) DM_HIP(e, launch_quick_gelu(f.p, (long long)M * Fi, s));
+        DM_TRY(dense(L.fc2, f, nullptr, &x1, &x2));
+        free(f); free(x1);
+        *x = x2;
+        return 0;
+    }
 };
 
 struct Args32 {
@@ -569,7 +604,9 @@ int run_vae32(dm_f32_net* e, const VaeArgs32& A, hipStream_t s, bool dry) {
 
 // ---- CLIP text tower: token ids -> last_hidden_state, CLIPTextTransformer op by op in fp32 ---------------------------------------------
 // (embeddings; 12 x [LN1 -> q|k|v -> causal attention -> out_proj + residual -> LN2 -> fc1 -> quick_gelu -> fc2 + residual]; final LN)
-int run_clip32(dm_f32_net* e, const int32_t* ids, int n, float* out, hipStream_t s, bool dry) {
+// out: last_hidden_state [n][77][768], or nullptr; embeds: `CLIPTextModelWithProjection.text_embeds` [n][768] (the final-LN row at the first
+// maximum of the ids = the EOS token, times text_projection^T, optionally / ||.||), or nullptr
+int run_clip32(dm_f32_net* e, const int32_t* ids, int n, float* out, float* embeds, int normalize, hipStream_t s, bool dry) {
     Fwd32 F{e, s, dry, e->w_clip.slab};
     const Clip32& c = e->clip;
     const int M = n * CL_T;
@@ -580,8 +617,65 @@ int run_clip32(dm_f32_net* e, const int32_t* ids, int n, float* out, hipStream_t
     T32 y;
     DM_TRY(F.layernorm(c.final_ln, x, &y));
     F.free(x);
-    if (!dry) DM_HIP(e, hipMemcpyAsync(out, y.p, (size_t)M * CL_H * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (out && !dry) DM_HIP(e, hipMemcpyAsync(out, y.p, (size_t)M * CL_H * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (embeds) {
+        T32 pooled, emb;
+        DM_TRY(F.alloc(&pooled, 1, 1, n, CL_H));
+        if (!dry) DM_HIP(e, launch_clip_eos_gather(ids, y.p, n, CL_T, CL_H, pooled.p, s));
+        DM_TRY(F.dense(c.tproj, pooled, nullptr, nullptr, &emb));
+        F.free(pooled);
+        if (!dry) {
+            if (normalize) DM_HIP(e, launch_clip_l2norm(emb.p, n, c.tproj.cout, embeds, s));
+            else DM_HIP(e, hipMemcpyAsync(embeds, emb.p, (size_t)n * c.tproj.cout * sizeof(float), hipMemcpyDeviceToDevice, s));
+        }
+        F.free(emb);
+    }
     F.free(y);
+    return 0;
+}
+
+// ---- the configurable image tower: pixel_values (or square uint8 images) -> projected patch tokens ------------------------------------
+// CLIPVisionModel op by op in fp32, then `visual_projection(post_layernorm(last_hidden_state[:, 1:, :]))` (ranking.py:66-70): patch rows
+// (KPAD wide) -> patch embedding GEMM; class token + positions; pre_layrnorm; layers x [LN1 -> q|k|v -> flash attention over T tokens ->
+// out_proj + residual -> LN2 -> fc1 -> quick_gelu -> fc2 + residual]; post_layernorm of rows 1..G^2 -> visual_projection
+struct TowerArgs {
+    const float* pix = nullptr;                                                    // [n][3][S][S], or
+    const uint8_t* images = nullptr; const dm_clip_pre_desc* desc = nullptr; const int32_t* tables = nullptr;     // square images to preprocess
+    int n = 0;
+    float* tokens = nullptr;                                                       // [n][G^2][projection_dim] or nullptr
+    float* hidden = nullptr;                                                       // last_hidden_state [n][T][hidden] or nullptr
+};
+
+int run_tower32(dm_f32_net* e, const TowerArgs& A, hipStream_t s, bool dry) {
+    Fwd32 F{e, s, dry, e->w_clipt.slab};
+    const ClipTower32& c = e->clipt;
+    const int n = A.n, G2 = c.G * c.G, H = c.cfg.hidden, M = n * c.T;
+    T32 rows, pe, x, x0;
+    DM_TRY(F.alloc(&rows, 1, 1, n * G2, c.KPAD));
+    if (!dry) {
+        if (A.pix) DM_HIP(e, launch_clip_tower_patchify(A.pix, n, c.cfg.image_size, c.cfg.patch_size, c.KPAD, rows.p, s));
+        else DM_HIP(e, launch_clip_tower_preprocess(A.images, A.desc, A.tables, n, c.cfg.image_size, c.cfg.patch_size, c.KPAD, 1, rows.p, s));
+    }
+    DM_TRY(F.dense(c.patch, rows, nullptr, nullptr, &pe));          // the stride-PS convolution, no bias
+    F.free(rows);
+    DM_TRY(F.alloc(&x, 1, 1, M, H));
+    if (!dry) DM_HIP(e, launch_clip_tower_tokens(pe.p, F.P(c.cls), F.P(c.pos), n, c.T, H, x.p, s));
+    F.free(pe);
+    DM_TRY(F.layernorm(c.pre_ln, x, &x0));
+    F.free(x);
+    x = x0;
+    for (const ClipLayer32& L : c.layer) DM_TRY(F.tower_layer(L, n, c.T, H, c.cfg.heads, c.cfg.intermediate, &x));
+    if (A.hidden && !dry) DM_HIP(e, hipMemcpyAsync(A.hidden, x.p, (size_t)M * H * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (A.tokens) {
+        T32 pl, emb;
+        DM_TRY(F.alloc(&pl, 1, 1, n * G2, H));
+        if (!dry) DM_HIP(e, launch_clip_tower_patch_ln(x.p, n, c.T, H, F.P(c.post_ln.g), F.P(c.post_ln.b), LN_EPS, pl.p, s));
+        DM_TRY(F.dense(c.proj, pl, nullptr, nullptr, &emb));
+        F.free(pl);
+        if (!dry) DM_HIP(e, hipMemcpyAsync(A.tokens, emb.p, (size_t)n * G2 * c.cfg.projection_dim * sizeof(float), hipMemcpyDeviceToDevice, s));
+        F.free(emb);
+    }
+    F.free(x);
     return 0;
 }
 
@@ -687,6 +781,28 @@ int run_clipvis_chunked32(dm_f32_net* e, ClipVisArgs A, void* stream, const char
     return 0;
 }
 
+// runs of at most CT_CHUNK images (the fc1 output alone is 9.5 MB per L/14-336 image); rows of different images meet in no sum, so the
+// split does not change a bit
+int run_tower_chunked32(dm_f32_net* e, const TowerArgs& full, void* stream, const char* what) {
+    if (!e->w_clipt.ready) DM_FAIL(e, "%s: CLIP tower weights not loaded (dm_f32_load_clip_tower_weight / dm_f32_finalize_clip_tower)", what);
+    if (full.n <= 0) DM_FAIL(e, "%s: bad image count %d", what, full.n);
+    DM_HIP(e, hipSetDevice(e->device));
+    hipStream_t s = (hipStream_t)stream;
+    const ClipTower32& c = e->clipt;
+    const size_t S = (size_t)c.cfg.image_size, G2 = (size_t)c.G * c.G;
+    for (int n0 = 0; n0 < full.n; n0 += CT_CHUNK) {
+        TowerArgs C = full;
+        C.n = (full.n - n0 < CT_CHUNK) ? full.n - n0 : CT_CHUNK;
+        if (full.pix) C.pix = full.pix + (size_t)n0 * 3 * S * S;
+        if (full.desc) C.desc = full.desc + n0;
+        if (full.tokens) C.tokens = full.tokens + (size_t)n0 * G2 * c.cfg.projection_dim;
+        if (full.hidden) C.hidden = full.hidden + (size_t)n0 * c.T * c.cfg.hidden;
+        DM_TRY(ensure_arena_for32(e, s, {4, C.n, C.pix ? 1 : 0, C.hidden ? 1 : 0, C.tokens ? 1 : 0}, [&]() { return run_tower32(e, C, s, true); }));
+        DM_TRY(run_tower32(e, C, s, false));
+    }
+    return 0;
+}
+
 int run_chunked32(dm_f32_net* e, Args32 A, void* stream) {
     if (!e->finalized) DM_FAIL(e, "fp32 net not finalized");
     if (e->n_prompts <= 0) DM_FAIL(e, "dm_f32_set_prompts must be called first");
@@ -734,7 +850,7 @@ void dm_f32_destroy(dm_f32_net* e) {
     if (!e) return;
     (void)hipSetDevice(e->device);
     (void)hipDeviceSynchronize();
-    for (float* slab : {e->w_unet.slab, e->w_vae.slab, e->w_clip.slab, e->w_clipv.slab}) if (slab) (void)hipFree(slab);
+    for (float* slab : {e->w_unet.slab, e->w_vae.slab, e->w_clip.slab, e->w_clipv.slab, e->w_clipt.slab}) if (slab) (void)hipFree(slab);
     if (e->sched_tab) (void)hipFree(e->sched_tab);
     if (e->score_tmp) (void)hipFree(e->score_tmp);
     if (e->arena_base) (void)hipFree(e->arena_base);
@@ -1004,7 +1120,12 @@ int dm_f32_finalize_clip(dm_f32_net* e) {
     }
     for (int l = 0; l < CL_LAYERS; ++l) DM_TRY(pack_clip_layer(P, "encoder.layers." + std::to_string(l), &c.layer[l]));
     DM_TRY(pack_norm(P, "final_layer_norm", CL_H, &c.final_ln));
-    return P.finish("CLIP text", 196);
+    // optional 197th tensor: `CLIPTextModelWithProjection.text_projection` (no bias), for dm_f32_clip_text_embeds
+    const bool proj = e->w_clip.host.count("text_projection.weight") != 0;
+    if (proj) DM_TRY(pack_dense(P, "text_projection", CL_H, CL_H, false, false, &c.tproj));
+    DM_TRY(P.finish("CLIP text", proj ? 197 : 196));
+    c.has_tproj = proj;
+    return 0;
 }
 
 /* `text_encoder(input_ids)[0]` in fp32 — what `pipe.encode_prompt` of the featuriser's fp32 pipeline returns (dift.py:222-226):
@@ -1021,8 +1142,8 @@ int dm_f32_clip_encode(dm_f32_net* e, const int32_t* input_ids_dev, int n_prompt
         const int n = (n_prompts - n0 < chunk) ? (n_prompts - n0) : chunk;
         const int32_t* ids = input_ids_dev + (size_t)n0 * CL_T;
         float* o = (float*)out_f32_dev + (size_t)n0 * CL_T * CL_H;
-        DM_TRY(ensure_arena_for32(e, s, {2, n, 0, 0, 0}, [&]() { return run_clip32(e, ids, n, o, s, true); }));
-        DM_TRY(run_clip32(e, ids, n, o, s, false));
+        DM_TRY(ensure_arena_for32(e, s, {2, n, 0, 0, 0}, [&]() { return run_clip32(e, ids, n, o, nullptr, 0, s, true); }));
+        DM_TRY(run_clip32(e, ids, n, o, nullptr, 0, s, false));
     }
     return 0;
 }
@@ -1100,6 +1221,124 @@ int dm_f32_clip_patch_features(dm_f32_net* e, const void* images_u8_dev, const d
     return run_clipvis_chunked32(e, A, stream, "dm_f32_clip_patch_features");
 }
 
+/* `CLIPTextModelWithProjection(input_ids).text_embeds` in fp32 (ranking.py:58-64): the text tower, the final-LN row at the first position of the
+ * largest id (`argmax(input_ids)`: the EOS token, which both of transformers' pooling rules pick), text_projection, optionally / ||.||.
+ * input_ids_dev [n, 77] int32; out_f32_dev [n, 768].  The reference pads with padding=True and the engine takes 77 ids: the tower is causal,
+ * so the EOS row does not see what follows it. */
+int dm_f32_clip_text_embeds(dm_f32_net* e, const int32_t* input_ids_dev, int n_prompts, int seq_len, int normalize, void* out_f32_dev, void* stream) {
+    if (!e) return 1;
+    if (!e->w_clip.ready) DM_FAIL(e, "dm_f32_clip_text_embeds: CLIP text weights not loaded (dm_f32_load_clip_weight / dm_f32_finalize_clip)");
+    if (!e->clip.has_tproj) DM_FAIL(e, "dm_f32_clip_text_embeds: the CLIP text weights were loaded without text_projection.weight");
+    if (!input_ids_dev || !out_f32_dev || n_prompts <= 0) DM_FAIL(e, "dm_f32_clip_text_embeds: bad argument");
+    if (seq_len != CL_T) DM_FAIL(e, "dm_f32_clip_text_embeds: seq_len must be %d", CL_T);
+    DM_HIP(e, hipSetDevice(e->device));
+    hipStream_t s = (hipStream_t)stream;
+    const int chunk = 128;                                   // prompts per pass, as dm_f32_clip_encode
+    for (int n0 = 0; n0 < n_prompts; n0 += chunk) {
+        const int n = (n_prompts - n0 < chunk) ? (n_prompts - n0) : chunk;
+        const int32_t* ids = input_ids_dev + (size_t)n0 * CL_T;
+        float* o = (float*)out_f32_dev + (size_t)n0 * CL_H;
+        DM_TRY(ensure_arena_for32(e, s, {2, n, 1, 0, 0}, [&]() { return run_clip32(e, ids, n, nullptr, o, normalize, s, true); }));
+        DM_TRY(run_clip32(e, ids, n, nullptr, o, normalize != 0, s, false));
+    }
+    return 0;
+}
+
+int dm_f32_load_clip_tower_weight(dm_f32_net* e, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim) {
+    if (!e || !name || !host_ptr || !shape) return 1;
+    if (e->w_clipt.ready) DM_FAIL(e, "load_clip_tower_weight after finalize_clip_tower");
+    std::string nm(name);
+    // a full CLIPModel state dict: the text half and the logit scale are not on this path; position_ids is an index buffer
+    if (nm.rfind("text_model.", 0) == 0 || nm == "text_projection.weight" || nm == "logit_scale") return 0;
+    if (nm.size() >= 12 && nm.compare(nm.size() - 12, 12, "position_ids") == 0) return 0;
+    if (nm.rfind("vision_model.", 0) == 0) nm = nm.substr(strlen("vision_model."));
+    return dm::stage_tensor(e->w_clipt.host, nm, host_ptr, dtype, shape, ndim, e->err);
+}
+
+int dm_f32_finalize_clip_tower(dm_f32_net* e, const dm_clip_tower_config* cfg) {
+    if (!e) return 1;
+    if (!cfg) DM_FAIL(e, "dm_f32_finalize_clip_tower: no config");
+    const dm_clip_tower_config c0 = *cfg;
+    if (e->w_clipt.ready) {
+        if (memcmp(&e->clipt.cfg, &c0, sizeof(c0)) != 0) DM_FAIL(e, "dm_f32_finalize_clip_tower: a tower with another config is already loaded");
+        return 0;
+    }
+    if (c0.hidden < 64 || c0.heads < 1 || c0.hidden != c0.heads * 64) DM_FAIL(e, "CLIP tower config: hidden %d != heads %d * 64", c0.hidden, c0.heads);
+    if (c0.hidden % 32 != 0 || c0.intermediate < 32 || c0.intermediate % 32 != 0)
+        DM_FAIL(e, "CLIP tower config: hidden %d and intermediate %d must be multiples of 32", c0.hidden, c0.intermediate);
+    if (c0.projection_dim < 4 || c0.projection_dim % 4 != 0) DM_FAIL(e, "CLIP tower config: projection_dim %d must be a multiple of 4", c0.projection_dim);
+    if (c0.layers < 1 || c0.layers > 64 || c0.hidden > 8192 || c0.intermediate > 32768 || c0.projection_dim > 8192)
+        DM_FAIL(e, "CLIP tower config: layers %d / widths out of range", c0.layers);
+    if (c0.patch_size < 1 || c0.patch_size > 64 || c0.image_size < c0.patch_size || c0.image_size > 2048 || c0.image_size % c0.patch_size != 0)
+        DM_FAIL(e, "CLIP tower config: image_size %d is not a multiple of patch_size %d (or out of range)", c0.image_size, c0.patch_size);
+    DM_HIP(e, hipSetDevice(e->device));
+    Packer32 P{e, e->w_clipt};
+    ClipTower32 c;
+    c.cfg = c0;
+    c.G = c0.image_size / c0.patch_size; c.T = c.G * c.G + 1;
+    c.KP = 3 * c0.patch_size * c0.patch_size; c.KPAD = (c.KP + 31) / 32 * 32;
+    const int H = c0.hidden;
+    {
+        HostT* cls = P.get("embeddings.class_embedding", {H});
+        HostT* pos = P.get("embeddings.position_embedding.weight", {c.T, H});
+        HostT* pw = P.get("embeddings.patch_embedding.weight", {H, 3, c0.patch_size, c0.patch_size});      // [H][(c, ky, kx)]: the patch rows' k order
+        if (!cls || !pos || !pw) return 1;
+        c.cls = P.put(cls->data.data(), cls->data.size());
+        c.pos = P.put(pos->data.data(), pos->data.size());
+        std::vector<float> pk((size_t)H * c.KPAD, 0.f);           // zero columns KP .. KPAD - 1 against the zero columns of the rows
+        for (int o = 0; o < H; ++o) memcpy(pk.data() + (size_t)o * c.KPAD, pw->data.data() + (size_t)o * c.KP, (size_t)c.KP * sizeof(float));
+        c.patch.w = P.put(pk.data(), pk.size());
+        c.patch.cin = c.KPAD; c.patch.cout = H; c.patch.k = 1; c.patch.b = NONE;
+    }
+    DM_TRY(pack_norm(P, "pre_layrnorm", H, &c.pre_ln));
+    c.layer.resize(c0.layers);
+    for (int l = 0; l < c0.layers; ++l) DM_TRY(pack_clip_layer(P, "encoder.layers." + std::to_string(l), &c.layer[l], H, c0.intermediate));
+    DM_TRY(pack_norm(P, "post_layernorm", H, &c.post_ln));
+    DM_TRY(pack_dense(P, "visual_projection", c0.projection_dim, H, false, false, &c.proj));
+    DM_TRY(P.finish("CLIP tower", (size_t)8 + 16 * (size_t)c0.layers));
+    e->clipt = std::move(c);
+    return 0;
+}
+
+/* The tower's processor on square uint8 images, bit-equal to `CLIPImageProcessor(size={"shortest_edge": S}, do_center_crop=False)` (PIL
+ * backend): layout 0 -> pixel_values [n][3][S][S]; layout 1 -> the patch rows of the embedding GEMM [n*G^2][KPAD] (KPAD = 3 PS^2 rounded up to
+ * 32; the padding columns are written as zeros).  Descriptors as dm_f32_clip_preprocess, crop = the whole image, left = top = 0. */
+int dm_f32_clip_tower_preprocess(dm_f32_net* e, const void* images_u8_dev, const dm_clip_pre_desc* descs_dev, const int32_t* tables_dev, int n,
+                                 int layout, void* out_dev, void* stream) {
+    if (!e) return 1;
+    if (!e->w_clipt.ready) DM_FAIL(e, "dm_f32_clip_tower_preprocess: CLIP tower weights not loaded (the config names the image and patch size)");
+    if (!images_u8_dev || !descs_dev || !tables_dev || !out_dev || n <= 0 || (layout != 0 && layout != 1)) DM_FAIL(e, "dm_f32_clip_tower_preprocess: bad argument");
+    DM_HIP(e, hipSetDevice(e->device));
+    const ClipTower32& c = e->clipt;
+    const size_t per = layout == 0 ? (size_t)3 * c.cfg.image_size * c.cfg.image_size : (size_t)c.G * c.G * c.KPAD;
+    for (int n0 = 0; n0 < n; n0 += 65535) {
+        const int m = (n - n0 < 65535) ? n - n0 : 65535;
+        DM_HIP(e, launch_clip_tower_preprocess((const uint8_t*)images_u8_dev, descs_dev + n0, tables_dev, m, c.cfg.image_size, c.cfg.patch_size, c.KPAD,
+                                              layout, (float*)out_dev + (size_t)n0 * per, (hipStream_t)stream));
+    }
+    return 0;
+}
+
+/* pixel_values_dev [n][3][S][S] -> out_tokens_dev [n][G^2][projection_dim] = visual_projection(post_layernorm(last_hidden_state[:, 1:, :])) and /
+ * or out_hidden_dev [n][G^2+1][hidden] = last_hidden_state (either may be NULL, not both) */
+int dm_f32_clip_tower_tokens(dm_f32_net* e, const void* pixel_values_dev, int n, void* out_tokens_dev, void* out_hidden_dev, void* stream) {
+    if (!e) return 1;
+    if (!pixel_values_dev || (!out_tokens_dev && !out_hidden_dev)) DM_FAIL(e, "dm_f32_clip_tower_tokens: bad argument");
+    TowerArgs A;
+    A.pix = (const float*)pixel_values_dev; A.n = n; A.tokens = (float*)out_tokens_dev; A.hidden = (float*)out_hidden_dev;
+    return run_tower_chunked32(e, A, stream, "dm_f32_clip_tower_tokens");
+}
+
+/* dm_f32_clip_tower_preprocess + dm_f32_clip_tower_tokens in one call: the preprocessing writes the patch rows; bit-equal to the two calls */
+int dm_f32_clip_tower_image_tokens(dm_f32_net* e, const void* images_u8_dev, const dm_clip_pre_desc* descs_dev, const int32_t* tables_dev, int n,
+                                   void* out_tokens_dev, void* stream) {
+    if (!e) return 1;
+    if (!images_u8_dev || !descs_dev || !tables_dev || !out_tokens_dev) DM_FAIL(e, "dm_f32_clip_tower_image_tokens: bad argument");
+    TowerArgs A;
+    A.images = (const uint8_t*)images_u8_dev; A.desc = descs_dev; A.tables = tables_dev; A.n = n; A.tokens = (float*)out_tokens_dev;
+    return run_tower_chunked32(e, A, stream, "dm_f32_clip_tower_image_tokens");
+}
+
 int dm_f32_prof_enable(dm_f32_net* e, int on) {
     if (!e) return 1;
     e->prof = on != 0;
@@ -1134,7 +1373,7 @@ int dm_f32_prof_read(dm_f32_net* e, double* gemm_ms, double* gemm_flops, int64_t
 
 int dm_f32_memory(dm_f32_net* e, size_t* weights_bytes, size_t* arena_bytes) {
     if (!e) return 1;
-    if (weights_bytes) *weights_bytes = e->w_unet.bytes + e->w_vae.bytes + e->w_clip.bytes + e->w_clipv.bytes;
+    if (weights_bytes) *weights_bytes = e->w_unet.bytes + e->w_vae.bytes + e->w_clip.bytes + e->w_clipv.bytes + e->w_clipt.bytes;
     if (arena_bytes) *arena_bytes = e->arena_cap;
     return 0;
 }
@@ -1169,6 +1408,11 @@ int dm_f32_op_groupnorm(void* stream, const void* X, const void* X2, int N, int 
 
 int dm_f32_op_layernorm(void* stream, const void* X, int rows, int C, const float* gamma, const float* beta, float eps, void* Y) {
     return launch_layernorm((const float*)X, rows, C, gamma, beta, eps, (float*)Y, (hipStream_t)stream) == hipSuccess ? 0 : 1;
+}
+
+/* the patch-token head's first half: LayerNorm of rows 1 .. T-1 of every image, X [n][T][C] -> Y [n*(T-1)][C] */
+int dm_f32_op_clip_patch_ln(void* stream, const void* X, int n, int T, int C, const float* gamma, const float* beta, float eps, void* Y) {
+    return launch_clip_tower_patch_ln((const float*)X, n, T, C, gamma, beta, eps, (float*)Y, (hipStream_t)stream) == hipSuccess ? 0 : 1;
 }
 
 }  // extern "C"

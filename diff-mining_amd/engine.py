@@ -122,6 +122,12 @@ SIGNATURES = {
     "dm_f32_clip_image_features": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp]),
     "dm_f32_clip_vision_hidden": (_i32, [_vp, _vp, _i32, _vp, _vp]),
     "dm_f32_clip_patch_features": (_i32, [_vp] * 4 + [_i32, _i32, _vp, _vp]),
+    "dm_f32_clip_text_embeds": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),
+    "dm_f32_load_clip_tower_weight": (_i32, _WEIGHT),
+    "dm_f32_finalize_clip_tower": (_i32, [_vp, _vp]),
+    "dm_f32_clip_tower_preprocess": (_i32, [_vp] * 4 + [_i32, _i32, _vp, _vp]),
+    "dm_f32_clip_tower_tokens": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp]),
+    "dm_f32_clip_tower_image_tokens": (_i32, [_vp] * 4 + [_i32, _vp, _vp]),
     "dm_f32_prof_enable": (_i32, [_vp, _i32]),
     "dm_f32_prof_read": (_i32, _PROF),
     "dm_f32_memory": (_i32, [_vp, _psz, _psz]),
@@ -129,6 +135,7 @@ SIGNATURES = {
     "dm_f32_op_attention": (_i32, [_vp] * 5 + [_i32] * 4 + [_i64] * 4 + [_vp] + [_i32] * 6 + [_f32]),
     "dm_f32_op_groupnorm": (_i32, [_vp, _vp, _vp] + [_i32] * 5 + [_f32, _vp, _vp, _i32, _vp, _vp]),
     "dm_f32_op_layernorm": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _f32, _vp]),
+    "dm_f32_op_clip_patch_ln": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _f32, _vp]),
 }
 SYMBOLS = list(SIGNATURES)
 
@@ -137,6 +144,7 @@ MINE_DESC_DTYPE = np.dtype([("grid_offset", "<i8"), ("work_offset", "<i8"), ("ma
                             ("h", "<i4"), ("w", "<i4"), ("H", "<i4"), ("W", "<i4")])
 MINE_MAX_K = 64
 MINE_MAX_SETS = 16          # DM_MINE_MAX_SETS: the set counts median_maps_kernel is instantiated for
+CLIP_TOWER_CHUNK = 64       # CT_CHUNK (unet_f32.hip): images per run of the configurable CLIP image tower
 
 
 def get_options(names=("ln_fold", "gn_fold", "ff_fold", "sc_fold", "up_fold", "tap_reuse", "ln_inkernel", "igemm_splitk", "q_once", "gn_epi", "conv_out_rows", "gn_skip", "attn_pipe", "graph")) -> dict:
@@ -317,9 +325,10 @@ class _EngineBase:
             pass
 
     # -- weights ---------------------------------------------------------------------------------
-    def _load(self, what: str, sd):
+    def _load(self, what: str, sd, *finalize_args):
         """Every tensor of a state dict (numpy or torch; fp16 and fp32 as they are, anything else widened to fp32) to
-        <_OBJ>load<what>_weight, then <_OBJ>finalize<what>; what = "" (the U-Net), "_vae", "_clip", "_clip_vision"."""
+        <_OBJ>load<what>_weight, then <_OBJ>finalize<what>(handle, *finalize_args); what = "" (the U-Net), "_vae", "_clip",
+        "_clip_vision", "_clip_tower"."""
         torch = self._torch
         fn = getattr(self.lib, f"{self._OBJ}load{what}_weight")
         for name, t in sd.items():
@@ -337,7 +346,7 @@ class _EngineBase:
             shape = (C.c_int64 * a.ndim)(*a.shape)
             self._check(fn(self._h, name.encode(), a.ctypes.data_as(C.c_void_p), dt, shape, a.ndim),
                         f"{self._RUN[3:]}load{what}_weight({name})")
-        self._call(self._OBJ, f"finalize{what}")
+        self._call(self._OBJ, f"finalize{what}", *finalize_args)
 
     def load_state_dict(self, sd: Dict[str, "np.ndarray"]):
         """sd: diffusers-named U-Net state dict (numpy or torch tensors, fp16/fp32/bf16; the fp32 engine keeps fp32 as it is and
@@ -353,7 +362,8 @@ class _EngineBase:
 
     def load_clip_state_dict(self, sd: Dict[str, "np.ndarray"]):
         """sd: `CLIPTextModel.state_dict()` (`pipe.text_encoder`, compute.py:68; the featuriser's pipeline keeps it in fp32,
-        dift.py:197-199).  Optional."""
+        dift.py:197-199).  Optional.  The fp32 net also takes `CLIPTextModelWithProjection.state_dict()`: its 197th tensor
+        `text_projection.weight` enables `UNetEngineF32.clip_text_embeds`."""
         self._load("_clip", sd)
         self._clip_ready = True
 
@@ -971,6 +981,123 @@ class UNetEngineF32(_EngineBase):
                                                         _p(tab_d), P, int(bool(normalize)), _p(out),
                                                         self._stream()), "dm_f32_clip_patch_features")
         return out
+
+
+    # -- the CLIP baseline from pixels (clipmining/ranking.py:58-70): text embeddings + the configurable image tower ---------------
+    def clip_text_embeds(self, input_ids, normalize: bool = True):
+        """`CLIPTextModelWithProjection(input_ids).text_embeds` in fp32 -> [n, 768] on the GPU; normalize=True divides each row by
+        its L2 norm (ranking.py:63).  input_ids [n, 77]: the reference tokenises with padding=True (the longest prompt), the engine
+        takes 77 ids — the text tower is causal, so the pooled row (the first position of the largest id = the EOS token) does not
+        see the padding behind it.  Needs `text_projection.weight` in the state dict given to load_clip_state_dict."""
+        torch = self._torch
+        ids = torch.as_tensor(input_ids).to(self.device, torch.int32).contiguous()
+        if ids.dim() != 2 or ids.shape[1] != 77 or ids.shape[0] < 1:
+            raise ValueError(f"input_ids must be [n, 77], got {tuple(ids.shape)}")
+        out = torch.empty(ids.shape[0], 768, dtype=torch.float32, device=self.device)
+        self._check(self.lib.dm_f32_clip_text_embeds(self._h, _p(ids), ids.shape[0], 77, int(bool(normalize)), _p(out),
+                                                     self._stream()), "dm_f32_clip_text_embeds")
+        return out
+
+    def load_clip_tower_state_dict(self, sd: Dict[str, "np.ndarray"], cfg=None):
+        """The configurable image tower (default clip_spec.CLIP_L14_336_VISION = StreetCLIP's): sd = a full `CLIPModel.state_dict()`
+        or `CLIPVisionModelWithProjection.state_dict()` (the text half, `logit_scale` and `position_ids` are skipped).  Checked against
+        clip_spec.clip_vision_tensor_spec(cfg); kept in fp32.  A second weight set beside the ViT-B/32 tower's."""
+        from .clip_spec import CLIP_L14_336_VISION, check_clip_tower_geometry, map_clip_vision_state_dict
+        cfg = cfg or CLIP_L14_336_VISION
+        try:
+            check_clip_tower_geometry(cfg)
+            canon = map_clip_vision_state_dict(sd, cfg)
+        except ValueError as e:
+            raise EngineError(f"CLIP tower state dict: {e}") from None
+        c = (C.c_int32 * 7)(cfg.hidden_size, cfg.intermediate_size, cfg.num_hidden_layers, cfg.num_attention_heads, cfg.image_size,
+                            cfg.patch_size, cfg.projection_dim)             # dm_clip_tower_config
+        names = {k: (k if k == "visual_projection.weight" else "vision_model." + k) for k in canon}
+        self._load("_clip_tower", {names[k]: v for k, v in canon.items()}, C.cast(c, C.c_void_p))
+        self._clip_tower_cfg = cfg
+
+    def load_clip_tower_dir(self, path: str, cfg=None):
+        """A local `geolocal/StreetCLIP` (CLIPModel) or CLIPVisionModelWithProjection directory: `config.json` is checked against cfg
+        (clip_spec.check_clip_tower_config names the offending key), then `model.safetensors` or `pytorch_model.bin` is loaded."""
+        import json
+        from .clip_spec import CLIP_L14_336_VISION, check_clip_tower_config
+        cfg = cfg or CLIP_L14_336_VISION
+        cj = os.path.join(path, "config.json")
+        if not os.path.isfile(cj):
+            raise EngineError(f"{cj} not found")
+        try:
+            with open(cj) as f:
+                check_clip_tower_config(json.load(f), cfg)
+        except ValueError as e:
+            raise EngineError(f"{cj}: {e}") from None
+        st, pt = os.path.join(path, "model.safetensors"), os.path.join(path, "pytorch_model.bin")
+        if os.path.isfile(st):
+            from safetensors.numpy import load_file
+            sd = load_file(st)
+        elif os.path.isfile(pt):
+            sd = self._torch.load(pt, map_location="cpu", weights_only=True)
+        else:
+            raise EngineError(f"{path}: neither model.safetensors nor pytorch_model.bin")
+        self.load_clip_tower_state_dict(sd, cfg)
+
+    def _tower_cfg(self, what: str):
+        cfg = getattr(self, "_clip_tower_cfg", None)
+        if cfg is None:
+            raise EngineError(f"{what}: CLIP tower weights not loaded (load_clip_tower_state_dict)")
+        return cfg
+
+    def _tower_batch(self, images, cfg):
+        """Checked square uint8 images on the device + the call's descriptors and tables (resample.clip_tower_plan)."""
+        torch = self._torch
+        from . import resample as RS
+        if isinstance(images, np.ndarray) or hasattr(images, "convert"):
+            raise TypeError("images must be a list of uint8 HWC arrays / PIL images")
+        imgs = [RS.check_clip_tower_image(a) for a in images]
+        if not imgs:
+            raise ValueError("no images")
+        desc, tables = RS.clip_tower_plan(imgs, cfg.image_size)
+        src = torch.from_numpy(np.concatenate([a.reshape(-1) for a in imgs])).to(self.device)
+        desc_d = torch.from_numpy(desc.view(np.uint8)).to(self.device)
+        tab_d = torch.from_numpy(tables).to(self.device)
+        return src, desc_d, tab_d, len(imgs)
+
+    def clip_tower_preprocess(self, images):
+        """`CLIPImageProcessor(size={"shortest_edge": S}, do_center_crop=False)(images=image)["pixel_values"]` (ranking.py:66) for a
+        list of SQUARE uint8 HWC RGB arrays / PIL images (the reference center-crops to 512 x 512 first: clipmine.center_crop), bit-equal
+        to it, on the device -> [n, 3, S, S] fp32.  Anything non-square raises ValueError."""
+        torch = self._torch
+        cfg = self._tower_cfg("clip_tower_preprocess")
+        src, desc_d, tab_d, n = self._tower_batch(images, cfg)
+        out = torch.empty(n, 3, cfg.image_size, cfg.image_size, dtype=torch.float32, device=self.device)
+        self._check(self.lib.dm_f32_clip_tower_preprocess(self._h, _p(src), _p(desc_d), _p(tab_d), n, 0, _p(out), self._stream()),
+                    "dm_f32_clip_tower_preprocess")
+        return out
+
+    def clip_patch_tokens(self, pixel_values, return_hidden: bool = False):
+        """`visual_projection(post_layernorm(vision_model(pixel_values).last_hidden_state[:, 1:, :]))` (ranking.py:66-70) in fp32:
+        pixel_values [n, 3, S, S] -> tokens [n, G^2, projection_dim] on the GPU (every patch token, CLS dropped); return_hidden adds
+        last_hidden_state [n, G^2 + 1, hidden]."""
+        torch = self._torch
+        cfg = self._tower_cfg("clip_patch_tokens")
+        S, g2 = cfg.image_size, (cfg.image_size // cfg.patch_size) ** 2
+        pv = torch.as_tensor(pixel_values).to(self.device, torch.float32).contiguous()
+        if pv.dim() != 4 or tuple(pv.shape[1:]) != (3, S, S) or pv.shape[0] < 1:
+            raise ValueError(f"pixel_values must be [n, 3, {S}, {S}], got {tuple(pv.shape)}")
+        tok = torch.empty(pv.shape[0], g2, cfg.projection_dim, dtype=torch.float32, device=self.device)
+        hid = torch.empty(pv.shape[0], g2 + 1, cfg.hidden_size, dtype=torch.float32, device=self.device) if return_hidden else None
+        self._check(self.lib.dm_f32_clip_tower_tokens(self._h, _p(pv), pv.shape[0], _p(tok), _p(hid), self._stream()),
+                    "dm_f32_clip_tower_tokens")
+        return (tok, hid) if return_hidden else tok
+
+    def clip_image_tokens(self, images):
+        """clip_patch_tokens(clip_tower_preprocess(images)) fused — the preprocessing writes the patch rows of the embedding GEMM —
+        and bit-equal to it: square uint8 images -> [n, G^2, projection_dim] fp32 on the GPU."""
+        torch = self._torch
+        cfg = self._tower_cfg("clip_image_tokens")
+        src, desc_d, tab_d, n = self._tower_batch(images, cfg)
+        tok = torch.empty(n, (cfg.image_size // cfg.patch_size) ** 2, cfg.projection_dim, dtype=torch.float32, device=self.device)
+        self._check(self.lib.dm_f32_clip_tower_image_tokens(self._h, _p(src), _p(desc_d), _p(tab_d), n, _p(tok), self._stream()),
+                    "dm_f32_clip_tower_image_tokens")
+        return tok
 
     def vae_encode(self, image, noise=None, scaling_factor: float = 0.18215, return_moments=False, draws_per_image: int = 1):
         """`vae.encode(image).latent_dist.sample() * scaling_factor` in fp32 (dift.py:187) with the N(0,1) draw injected (`noise`

@@ -348,3 +348,50 @@ def clip_preprocess_numpy(image_u8, box=None) -> np.ndarray:
     crop = img[r0:r0 + rh, c0:c0 + cw]
     need_h, need_v, left, top, xt, yt = clip_patch_tables(cw, rh)
     return clip_normalize_numpy(resize_numpy_tables(crop, xt, yt, need_h, need_v, left, top))
+
+
+# ---- the configurable tower's processor (CLIP baseline, clipmining/ranking.py:60-66): `CLIPImageProcessor(size={"shortest_edge": S},
+# do_center_crop=False)` on the 512 x 512 center crop.  Only square inputs: a non-square one would change the token grid, which the
+# reference never does.  The whole s x s image maps onto S x S, so left = top = 0 and the tables cover every output column / row.
+def check_clip_tower_image(img) -> np.ndarray:
+    img = check_clip_image(img)
+    if img.shape[0] != img.shape[1]:
+        raise ValueError(f"the tower takes square images (the reference center-crops to 512 x 512 first), got {img.shape[0]}x{img.shape[1]}")
+    return img
+
+
+def clip_tower_plan(images: Sequence[np.ndarray], size: int = 336):
+    """Descriptors + tables of one dm_f32_clip_tower_preprocess / dm_f32_clip_tower_image_tokens call: checked square uint8 HWC
+    images packed back to back -> (desc [n] CLIP_DESC_DTYPE, tables int32 [T]).  One copy of the table of each distinct side."""
+    desc = np.zeros(len(images), dtype=CLIP_DESC_DTYPE)
+    parts, at, where = [], 0, {}
+    src_off = 0
+    for p, img in enumerate(images):
+        s = check_clip_tower_image(img).shape[0]
+        if s not in where:
+            b, k = bicubic_axis(s, size)
+            assert (b[:, 0] >= 0).all() and (b[:, 0] + b[:, 1] <= s).all()
+            where[s] = (at, at + b.size, k.shape[1])
+            parts += [b.reshape(-1), k.reshape(-1)]
+            at += b.size + k.size
+        b_off, k_off, taps = where[s]
+        d = desc[p]
+        d["src_offset"], d["src_w"], d["src_h"] = src_off, s, s
+        d["crop_col0"], d["crop_row0"], d["crop_w"], d["crop_h"] = 0, 0, s, s
+        d["left"], d["top"], d["kx"], d["ky"] = 0, 0, taps, taps
+        d["xb_off"], d["xk_off"], d["yb_off"], d["yk_off"] = b_off, k_off, b_off, k_off
+        d["flags"] = (CLIP_NEED_H | CLIP_NEED_V) if s != size else 0
+        src_off += s * s * 3
+    if at >= 2 ** 31:
+        raise ValueError("too many distinct image sizes in one call")
+    tables = np.concatenate(parts).astype(np.int32) if parts else np.zeros(0, np.int32)
+    return desc, tables
+
+
+def clip_tower_preprocess_numpy(image, size: int = 336) -> np.ndarray:
+    """`CLIPImageProcessor(size={"shortest_edge": size}, do_center_crop=False)(images=image)["pixel_values"][0]` for a square image,
+    restated on the host with `bicubic_axis`'s tables (what the device kernel computes) -> float32 [3, size, size]."""
+    img = check_clip_tower_image(image)
+    t = bicubic_axis(img.shape[0], size)
+    need = img.shape[0] != size
+    return clip_normalize_numpy(resize_numpy_tables(img, t, t, need, need))

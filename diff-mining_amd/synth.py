@@ -291,16 +291,21 @@ def synth_clip_vision_state_dict(seed: int = 0, cfg=None, dtype=np.float32) -> d
     return out
 
 
-def synth_clip_pixel_values(n: int, seed: int = 0) -> np.ndarray:
-    """Deterministic processor-like input [n, 3, 224, 224] fp32: a smooth per-image pattern plus noise, in the range the processor
+def synth_clip_pixel_values(n: int, seed: int = 0, size: int = 224) -> np.ndarray:
+    """Deterministic processor-like input [n, 3, size, size] fp32: a smooth per-image pattern plus noise, in the range the processor
     produces ((x - mean) / std of x in [0, 1], about [-1.8, 2.2])."""
-    u = hash_uniform("input.clip_pixels", n * 3 * 224 * 224, seed).reshape(n, 3, 224, 224)
-    yy, xx = np.meshgrid(np.linspace(0.0, 1.0, 224), np.linspace(0.0, 1.0, 224), indexing="ij")
+    u = hash_uniform("input.clip_pixels", n * 3 * size * size, seed).reshape(n, 3, size, size)
+    yy, xx = np.meshgrid(np.linspace(0.0, 1.0, size), np.linspace(0.0, 1.0, size), indexing="ij")
     base = 0.5 + 0.4 * np.sin(3.0 * xx + 5.0 * yy + np.arange(n * 3).reshape(n, 3, 1, 1))
     x = np.clip(0.7 * base + 0.3 * u, 0.0, 1.0).astype(np.float32)
     mean = np.array([0.48145466, 0.4578275, 0.40821073], dtype=np.float32).reshape(1, 3, 1, 1)
     std = np.array([0.26862954, 0.26130258, 0.27577711], dtype=np.float32).reshape(1, 3, 1, 1)
     return np.ascontiguousarray((x - mean) / std)
+
+
+def synth_clip_text_projection(seed: int = 0, dim: int = 768) -> np.ndarray:
+    """Synthetic `text_projection.weight` [dim, dim] of `CLIPTextModelWithProjection`, fan-in scaled like the other linear layers."""
+    return synth_tensor("clip.text_projection.weight", (dim, dim), seed)
 
 
 def synth_token_ids(n: int, cfg=None, seed: int = 3) -> np.ndarray:

@@ -827,6 +827,38 @@ int dm_f32_clip_vision_hidden(dm_f32_net* e, const void* pixel_values_dev, int n
  * directly; bit-equal to the two calls */
 int dm_f32_clip_patch_features(dm_f32_net* e, const void* images_u8_dev, const dm_clip_pre_desc* descs_dev, const int32_t* tables_dev,
                                int n_patches, int normalize, void* out_f32_dev, void* stream);
+/* `CLIPTextModelWithProjection(input_ids).text_embeds` of the CLIP baseline (clipmining/ranking.py:58-64) on the fp32 text tower:
+ * dm_f32_load_clip_weight accepts an optional 197th tensor `text_projection.weight` [768, 768] (without it everything behaves as before and this
+ * entry fails).  The final-LayerNorm row at the first position of the largest id (`argmax(input_ids)`: the EOS token, so both of transformers'
+ * pooling rules agree with it) times text_projection^T, divided by its L2 norm when normalize != 0.  input_ids_dev [n_prompts, 77] int32: the
+ * reference pads with padding=True, the engine takes 77 ids — the tower is causal, so the EOS row does not see the padding.
+ * out_f32_dev [n_prompts, 768]. */
+int dm_f32_clip_text_embeds(dm_f32_net* e, const int32_t* input_ids_dev, int n_prompts, int seq_len, int normalize, void* out_f32_dev,
+                            void* stream);
+/* optional configurable CLIP image tower in fp32, beside the ViT-B/32 one (own weight set; nothing on that path changes): the patch tokens of
+ * the CLIP baseline, `visual_projection(post_layernorm(vision_model(pixel_values).last_hidden_state[:, 1:, :]))` (ranking.py:66-70, StreetCLIP =
+ * ViT-L/14-336: (1024, 4096, 24, 16, 336, 14, 768), 392 tensors).  The config is accepted only when hidden == heads * 64, hidden % 32 == 0,
+ * intermediate % 32 == 0, projection_dim % 4 == 0 and image_size % patch_size == 0; finalize checks every tensor's shape against it (8 + 16 layers
+ * tensors; names as dm_f32_load_clip_vision_weight).  G = image_size / patch_size, T = G^2 + 1 tokens; the patch rows of the embedding GEMM
+ * are 3 patch_size^2 values padded with zeros to a multiple of 32 (588 -> 608); attention: heads of 64 on the fp32 MFMA flash kernel; calls
+ * split into runs of 64 images, bit-equal whatever the split. */
+typedef struct dm_clip_tower_config {
+    int32_t hidden, intermediate, layers, heads, image_size, patch_size, projection_dim;
+} dm_clip_tower_config;
+int dm_f32_load_clip_tower_weight(dm_f32_net* e, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim);
+int dm_f32_finalize_clip_tower(dm_f32_net* e, const dm_clip_tower_config* cfg);
+/* The tower's processor, `CLIPImageProcessor(size={"shortest_edge": S}, do_center_crop=False)` (PIL backend), on SQUARE uint8 images, bit-equal
+ * to it: descriptors and tables as dm_f32_clip_preprocess with crop = the whole image, left = top = 0 and tables of all S columns / rows
+ * (resample.clip_tower_plan).  layout 0: out_dev = pixel_values [n, 3, S, S]; layout 1: the patch rows [n * G^2][KPAD], row = patch
+ * (py * G + px), k = (c, ky, kx), columns 3 patch_size^2 .. KPAD - 1 written as zeros.  Needs the finalized tower (its config names S). */
+int dm_f32_clip_tower_preprocess(dm_f32_net* e, const void* images_u8_dev, const dm_clip_pre_desc* descs_dev, const int32_t* tables_dev,
+                                 int n, int layout, void* out_dev, void* stream);
+/* pixel_values_dev [n, 3, S, S] -> out_tokens_dev [n, G^2, projection_dim] and / or out_hidden_dev [n, G^2 + 1, hidden] = last_hidden_state
+ * (either may be NULL, not both) */
+int dm_f32_clip_tower_tokens(dm_f32_net* e, const void* pixel_values_dev, int n, void* out_tokens_dev, void* out_hidden_dev, void* stream);
+/* dm_f32_clip_tower_preprocess + dm_f32_clip_tower_tokens in one call (the preprocessing writes the patch rows); bit-equal to the two calls */
+int dm_f32_clip_tower_image_tokens(dm_f32_net* e, const void* images_u8_dev, const dm_clip_pre_desc* descs_dev, const int32_t* tables_dev,
+                                   int n, void* out_tokens_dev, void* stream);
 int dm_f32_prof_enable(dm_f32_net* e, int on);
 int dm_f32_prof_read(dm_f32_net* e, double* gemm_ms, double* gemm_flops, int64_t* gemm_launches, double* attn_ms,
                      double* attn_flops, int64_t* attn_launches);
@@ -837,10 +869,12 @@ int dm_f32_op_gemm(void* stream, const void* X, const void* X2, const void* Wp, 
                    void* Y, int N, int H, int W, int OH, int OW, int Cin, int C1, int Cout, int mode, int temb_ld);
 int dm_f32_op_attention(void* stream, const void* Q, const void* K, const void* V, void* O, int ldq, int ldk, int ldv, int ldo,
                         int64_t bsq, int64_t bsk, int64_t bsv, int64_t bso, const int32_t* kv_slot, int n_slots, int B, int heads,
-                        int Tq, int Tk, int D, float scale);
+                        int Tq, int Tk, int D, float scale);     /* D in {40, 64, 80, 160, 512} */
 int dm_f32_op_groupnorm(void* stream, const void* X, const void* X2, int N, int HW, int C, int C1, int G, float eps,
                         const float* gamma, const float* beta, int silu, void* stats_work, void* Y);
 int dm_f32_op_layernorm(void* stream, const void* X, int rows, int C, const float* gamma, const float* beta, float eps, void* Y);
+/* the tower's patch-token head, first half: LayerNorm of rows 1 .. T-1 of every image (the CLS row skipped), X [n][T][C] -> Y [n*(T-1)][C] */
+int dm_f32_op_clip_patch_ln(void* stream, const void* X, int n, int T, int C, const float* gamma, const float* beta, float eps, void* Y);
 
 #ifdef __cplusplus
 }
