@@ -89,5 +89,17 @@ hipError_t launch_posterior(const float* Hm, const float* qw, const float* qb, c
                             float* latent, float* moments, hipStream_t s);
 // mean over groups of `ens` consecutive samples, NHWC -> NCHW
 hipError_t launch_ensemble_mean(const float* X, int groups, int ens, int HW, int C, float* Y, hipStream_t s);
+// The parallel-dataset generator's kernels (pnp.hip).  DDIM update out = c0 * ((x - c1 * eps) / c2) + c3 * eps with coef = (c0, c1, c2, c3) on
+// the device, every operation rounded on its own; eps = eps_u, or eps_u + g * (eps_c - eps_u) when eps_c is given; out may be x
+hipError_t launch_ddim_step(const float* x, const float* eps_u, const float* eps_c, float g, const float* coef, long long n, float* out, hipStream_t s);
+// Y[b] = R[b] + Hs, b < B, `per` (a multiple of 4) elements per sample
+hipError_t launch_bcast_add(const float* R, const float* Hs, int B, long long per, float* Y, hipStream_t s);
+// z = post_quant_conv(latent * scale), 1x1 4 -> 4, NCHW [B,4,HW] in and out
+hipError_t launch_decoder_head(const float* lat, const float* w, const float* b, int B, int HW, float scale, float* z, hipStream_t s);
+// the decoder's tail on X NHWC [B,H,W,128] (the input of conv_norm_out) with its GroupNorm(32) statistics from launch_gn_stats: affine + SiLU
+// while loading, conv3x3 pad 1 128 -> 3 (Wp [3][9*128], k = (tap, c)), then out_f32 NCHW [B,3,H,W] (raw ? the sample : (sample / 2 + 0.5)
+// .clamp(0, 1)) and / or out_u8 NHWC [B,H,W,3] = that image * 255, truncated
+hipError_t launch_decoder_tail(const float* X, const float* stats, const float* gamma, const float* beta, const float* Wp, const float* bias, int B,
+                               int H, int W, int C, int raw, float* out_f32, uint8_t* out_u8, hipStream_t s);
 
 }  // namespace dm32

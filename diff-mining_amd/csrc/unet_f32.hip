@@ -55,6 +55,17 @@ struct Vae32 {
     size_t qw = NONE, qb = NONE;   // quant_conv [8][8], [8]
 };
 
+// SDv1.5 AutoencoderKL decoder (+ post_quant_conv): a weight set of its own (pnp.py:137-142, :531-536).  Up blocks of three resnets with
+// 512 / 512 / 256 / 128 output channels; blocks 0-2 end in nearest-2x + conv3x3 (up), or its fold onto the source grid (up4)
+struct VaeDec32 {
+    size_t pqw = NONE, pqb = NONE; // post_quant_conv [4][4], [4]
+    Conv conv_in;                  // transposed [36][512] for the direct kernel
+    Res mid[2];
+    Norm attn_gn; Conv qkv, o;
+    Res up[VNB][3]; Conv us[VNB - 1], us4[VNB - 1];
+    Norm norm_out; Conv conv_out;  // [3][9*128]: the fused tail's layout
+};
+
 // CLIP ViT-L/14 text tower (`pipe.text_encoder` of the featuriser's fp32 pipeline: dift.py:197-199, 222-226)
 struct ClipLayer32 { Norm ln1, ln2; Conv qkv, o, fc1, fc2; };
 struct Clip32 { size_t tok = NONE, pos = NONE; ClipLayer32 layer[CL_LAYERS]; Norm final_ln; Conv tproj; bool has_tproj = false; };     // tproj: optional text_projection [768][768]
@@ -91,6 +102,10 @@ struct dm_f32_net {
     // optional VAE encoder (dm_f32_load_vae_weight / dm_f32_finalize_vae): the reference's featuriser encodes the image in fp32 too
     dm::WeightSet<float> w_vae;
     Vae32 vae;
+    // optional VAE decoder (dm_f32_load_vae_decoder_weight / dm_f32_finalize_vae_decoder) and the buffers of the DDIM / PnP loops
+    dm::WeightSet<float> w_vaed;
+    VaeDec32 vaed;
+    char* loop_buf = nullptr; size_t loop_bytes = 0;
     // optional CLIP text tower (dm_f32_load_clip_weight / dm_f32_finalize_clip): `pipe.encode_prompt` is fp32 there too (dift.py:222-226)
     dm::WeightSet<float> w_clip;
     Clip32 clip;
@@ -350,9 +365,15 @@ struct Fwd32 {
         if (!dry) DM_HIP(e, launch_layernorm(x.p, (int)x.rows(), x.C, P(nw.g), P(nw.b), LN_EPS, y->p, s));
         return 0;
     }
-    int resnet(const Res& r, const T32& x, const T32* x2, const float* tproj, T32* out) {      // ResnetBlock2D
-        T32 n1, h1, n2, sc;
-        DM_TRY(groupnorm(r.n1, x, x2, res_eps, true, &n1));
+    // ResnetBlock2D.  inject (Plug-and-Play's feature injection, pnp.py:345-350; sample 0 = the source): norm1 .. conv2 run for the source
+    // alone, and every sample's output is shortcut(x_n) + h_src — one addition, `input_tensor + hidden_states` (pnp.py:357); for the source
+    // that is the sum the fused epilogue forms ((acc + bias) + residual), so its row does not change
+    int resnet(const Res& r, const T32& x, const T32* x2, const float* tproj, T32* out, bool inject = false) {
+        T32 n1, h1, n2, sc, xs = x, x2s;
+        if (inject) { xs.N = 1; if (x2) { x2s = *x2; x2s.N = 1; } }
+        const T32& xa = inject ? xs : x;
+        const T32* x2a = (inject && x2) ? &x2s : x2;
+        DM_TRY(groupnorm(r.n1, xa, x2a, res_eps, true, &n1));
         DM_TRY(gemm(r.c1, 1, n1, nullptr, x.H, x.W, tproj ? tproj + r.temb_off : nullptr, e->tproj_total, nullptr, &h1));
         free(n1);
         DM_TRY(groupnorm(r.n2, h1, nullptr, res_eps, true, &n2));
@@ -360,23 +381,33 @@ struct Fwd32 {
         const T32* resid = &x;
         if (r.has_sc) { DM_TRY(dense(r.sc, x, x2, nullptr, &sc)); resid = &sc; }
         else if (x2) DM_FAIL(e, "resnet32: concat input without shortcut conv");
-        DM_TRY(gemm(r.c2, 1, n2, nullptr, x.H, x.W, nullptr, 0, resid, out));
+        if (!inject) DM_TRY(gemm(r.c2, 1, n2, nullptr, x.H, x.W, nullptr, 0, resid, out));
+        else {
+            T32 hs;
+            DM_TRY(gemm(r.c2, 1, n2, nullptr, x.H, x.W, nullptr, 0, nullptr, &hs));
+            DM_TRY(alloc(out, x.N, x.H, x.W, r.c2.cout));
+            if (!dry) DM_HIP(e, launch_bcast_add(resid->p, hs.p, x.N, (long long)x.H * x.W * r.c2.cout, out->p, s));
+            free(hs);
+        }
         free(n2);
         if (r.has_sc) free(sc);
         return 0;
     }
+    // bsk < 0: K shares V's batch stride (every caller but the self-attention injection)
     int attention(const float* Q, int ldq, long long bsq, const float* K, const float* V, int ldkv, long long bskv, const int32_t* slots,
-                  int B, int Tq, int Tk, int C, float* O, int heads = HEADS) {
+                  int B, int Tq, int Tk, int C, float* O, int heads = HEADS, long long bsk = -1) {
         AttnParams a;
         a.Q = Q; a.K = K; a.V = V; a.O = O; a.ldq = ldq; a.ldk = ldkv; a.ldv = ldkv; a.ldo = C;
-        a.bsq = bsq; a.bsk = bskv; a.bsv = bskv; a.bso = (long long)Tq * C;
+        a.bsq = bsq; a.bsk = bsk < 0 ? bskv : bsk; a.bsv = bskv; a.bso = (long long)Tq * C;
         a.kv_slot = slots; a.n_slots = e->n_prompts; a.B = B; a.heads = heads; a.Tq = Tq; a.Tk = Tk; a.D = C / heads;
         a.scale = 1.0f / sqrtf((float)a.D);
         DM_TRY(prof_begin(1, 4.0 * B * heads * (double)Tq * Tk * a.D, B * Tq, Tk, a.D, Tq == Tk ? 100 : 101));
         DM_HIP(e, launch_attention(a, s));
         return prof_end();
     }
-    int transformer(const Tfm& t, const T32& x, const int32_t* slots, T32* out) {       // Transformer2DModel + BasicTransformerBlock
+    // Transformer2DModel + BasicTransformerBlock.  src_qk (Plug-and-Play's self-attention injection, pnp.py:424-432): every sample attends with
+    // the queries and keys of sample 0 (the source) and its own values — batch strides of 0 for Q and K, no copy
+    int transformer(const Tfm& t, const T32& x, const int32_t* slots, T32* out, bool src_qk = false) {
         const int C = t.c, T = x.H * x.W, B = x.N;
         T32 n, t0, ln, qkv, a, t1, q, t2, ff, t3;
         DM_TRY(groupnorm(t.gn, x, nullptr, ATTN_GN_EPS, false, &n));
@@ -386,7 +417,8 @@ struct Fwd32 {
         DM_TRY(dense(t.qkv, ln, nullptr, nullptr, &qkv));
         free(ln);
         DM_TRY(alloc(&a, B, x.H, x.W, C));
-        if (!dry) DM_TRY(attention(qkv.p, 3 * C, (long long)T * 3 * C, qkv.p + C, qkv.p + 2 * C, 3 * C, (long long)T * 3 * C, nullptr, B, T, T, C, a.p));
+        if (!dry) DM_TRY(attention(qkv.p, 3 * C, src_qk ? 0 : (long long)T * 3 * C, qkv.p + C, qkv.p + 2 * C, 3 * C, (long long)T * 3 * C, nullptr, B, T, T, C, a.p,
+                                   HEADS, src_qk ? 0 : -1));
         free(qkv);
         DM_TRY(dense(t.o1, a, nullptr, &t0, &t1));
         free(a); free(t0);
@@ -459,6 +491,8 @@ struct Fwd32 {
 struct Args32 {
     const float* x; const int64_t* t; const int32_t* slots; int B, H, W; int up_ft_index;
     float* out; float* feat; float* feat_mean; int ensemble;
+    // Plug-and-Play injection (sample 0 = the source): bit 3 * res + block = up_blocks[res] resnet / attn1 `block`, bits 12.. = the mid block's
+    unsigned conv_mask = 0, attn_mask = 0;
 };
 
 int run_forward32(dm_f32_net* e, const Args32& A, hipStream_t s, bool dry) {
@@ -503,10 +537,10 @@ int run_forward32(dm_f32_net* e, const Args32& A, hipStream_t s, bool dry) {
         }
     }
     T32 m0, m1, m2;
-    DM_TRY(F.resnet(e->mid_res[0], cur, nullptr, tproj.p, &m0));
-    DM_TRY(F.transformer(e->mid_tf, m0, A.slots, &m1));
+    DM_TRY(F.resnet(e->mid_res[0], cur, nullptr, tproj.p, &m0, (A.conv_mask >> 12) & 1));
+    DM_TRY(F.transformer(e->mid_tf, m0, A.slots, &m1, (A.attn_mask >> 12) & 1));
     F.free(m0);
-    DM_TRY(F.resnet(e->mid_res[1], m1, nullptr, tproj.p, &m2));
+    DM_TRY(F.resnet(e->mid_res[1], m1, nullptr, tproj.p, &m2, (A.conv_mask >> 13) & 1));
     F.free(m1);
     cur = m2;                        // owned from here on
     const bool fwd_up_size = (A.H % 8 != 0) || (A.W % 8 != 0);          // dift.py:54-56
@@ -516,9 +550,9 @@ int run_forward32(dm_f32_net* e, const Args32& A, hipStream_t s, bool dry) {
         for (int j = 0; j < LAYERS + 1; ++j) {
             T32 skip = skips.back(); skips.pop_back();
             T32 r;
-            DM_TRY(F.resnet(u.res[j], cur, &skip, tproj.p, &r));
+            DM_TRY(F.resnet(u.res[j], cur, &skip, tproj.p, &r, (A.conv_mask >> (3 * i + j)) & 1));
             F.free(cur); F.free(skip);
-            if (u.attn) { T32 a; DM_TRY(F.transformer(u.tf[j], r, A.slots, &a)); F.free(r); r = a; }
+            if (u.attn) { T32 a; DM_TRY(F.transformer(u.tf[j], r, A.slots, &a, (A.attn_mask >> (3 * i + j)) & 1)); F.free(r); r = a; }
             cur = r;
         }
         if (u.has_up) {
@@ -599,6 +633,67 @@ int run_vae32(dm_f32_net* e, const VaeArgs32& A, hipStream_t s, bool dry) {
     F.free(nrm);
     if (!dry) DM_HIP(e, launch_posterior(co.p, F.P(v.qw), F.P(v.qb), A.noise, A.B, A.draws, co.H * co.W, A.scaling, A.latent, A.moments, s));
     F.free(co);
+    return 0;
+}
+
+// ---- VAE decoder: latent -> image (pnp.py:137-142 / :531-536: `vae.decode(1 / 0.18215 * latents).sample`, `(imgs / 2 + 0.5).clamp(0, 1)`, fp32) ----
+// post_quant_conv; conv_in 4 -> 512; mid block (resnet, one-head attention, resnet); four up blocks of three resnets (512, 512, 256, 128),
+// blocks 0-2 followed by nearest-2x + conv3x3; conv_norm_out + SiLU + conv_out 128 -> 3 and the post-processing in one kernel (pnp.hip)
+struct VaeDecArgs32 { const float* latent; int B, h, w; float scale; int raw; float* out_f32; uint8_t* out_u8; };
+
+int run_vae_dec32(dm_f32_net* e, const VaeDecArgs32& A, hipStream_t s, bool dry) {
+    Fwd32 F{e, s, dry, e->w_vaed.slab};
+    F.res_eps = VAE_EPS;
+    const VaeDec32& v = e->vaed;
+    const int C = VBOC[VNB - 1];
+    T32 z, cur;
+    DM_TRY(F.alloc(&z, A.B, 1, 1, 4 * A.h * A.w));
+    if (!dry) DM_HIP(e, launch_decoder_head(A.latent, F.P(v.pqw), F.P(v.pqb), A.B, A.h * A.w, A.scale, z.p, s));
+    DM_TRY(F.alloc(&cur, A.B, A.h, A.w, C));
+    if (!dry) DM_HIP(e, launch_conv_in(z.p, F.P(v.conv_in.w), F.P(v.conv_in.b), A.B, 4, A.h, A.w, C, cur.p, s));
+    F.free(z);
+    {
+        T32 m0, n, qkv, a, m1, m2;
+        DM_TRY(F.resnet(v.mid[0], cur, nullptr, nullptr, &m0));
+        F.free(cur);
+        const int T = m0.H * m0.W;
+        DM_TRY(F.groupnorm(v.attn_gn, m0, nullptr, VAE_EPS, false, &n));
+        DM_TRY(F.dense(v.qkv, n, nullptr, nullptr, &qkv));
+        F.free(n);
+        DM_TRY(F.alloc(&a, m0.N, m0.H, m0.W, C));
+        if (!dry) DM_TRY(F.attention(qkv.p, 3 * C, (long long)T * 3 * C, qkv.p + C, qkv.p + 2 * C, 3 * C, (long long)T * 3 * C, nullptr,
+                                    m0.N, T, T, C, a.p, 1));
+        F.free(qkv);
+        DM_TRY(F.dense(v.o, a, nullptr, &m0, &m1));
+        F.free(a); F.free(m0);
+        DM_TRY(F.resnet(v.mid[1], m1, nullptr, nullptr, &m2));
+        F.free(m1);
+        cur = m2;
+    }
+    for (int i = 0; i < VNB; ++i) {
+        for (int j = 0; j < 3; ++j) {
+            T32 r;
+            DM_TRY(F.resnet(v.up[i][j], cur, nullptr, nullptr, &r));
+            F.free(cur);
+            cur = r;
+        }
+        if (i != VNB - 1) {
+            T32 upc;
+            if (dm::option(dm::OPT_UP_FOLD)) DM_TRY(F.upconv4(v.us4[i], cur, &upc));
+            else DM_TRY(F.gemm(v.us[i], 3, cur, nullptr, 2 * cur.H, 2 * cur.W, nullptr, 0, nullptr, &upc));
+            F.free(cur);
+            cur = upc;
+        }
+    }
+    T32 st;
+    DM_TRY(F.alloc(&st, 1, 1, cur.N * GROUPS, 2));
+    if (!dry) {
+        DM_HIP(e, launch_gn_stats(cur.p, nullptr, cur.N, cur.H * cur.W, cur.C, cur.C, GROUPS, VAE_EPS, st.p, s));
+        DM_HIP(e, launch_decoder_tail(cur.p, st.p, F.P(v.norm_out.g), F.P(v.norm_out.b), F.P(v.conv_out.w), F.P(v.conv_out.b), cur.N, cur.H, cur.W, cur.C,
+                                      A.raw, A.out_f32, A.out_u8, s));
+    }
+    F.free(st);
+    F.free(cur);
     return 0;
 }
 
@@ -757,7 +852,7 @@ int chunk32(int h, int w) {
 }
 
 int ensure_arena32(dm_f32_net* e, const Args32& A, hipStream_t s) {
-    return ensure_arena_for32(e, s, {0, A.B, A.H, A.W, A.up_ft_index}, [&]() { return run_forward32(e, A, s, true); });
+    return ensure_arena_for32(e, s, {0, A.B, A.H, A.W, A.up_ft_index, A.conv_mask}, [&]() { return run_forward32(e, A, s, true); });
 }
 
 // runs of at most CV_CHUNK images: the fc1 output is 614 KB per image, so the workspace is bounded whatever the call's size;
@@ -800,6 +895,15 @@ int run_tower_chunked32(dm_f32_net* e, const TowerArgs& full, void* stream, cons
         DM_TRY(ensure_arena_for32(e, s, {4, C.n, C.pix ? 1 : 0, C.hidden ? 1 : 0, C.tokens ? 1 : 0}, [&]() { return run_tower32(e, C, s, true); }));
         DM_TRY(run_tower32(e, C, s, false));
     }
+    return 0;
+}
+
+// the buffer of the DDIM / PnP loops (predictions, the per-step timestep rows and coefficients); grows before a loop starts, never inside one
+int loop_reserve32(dm_f32_net* e, hipStream_t s, size_t bytes) {
+    if (bytes <= e->loop_bytes) return 0;
+    if (e->loop_buf) { DM_HIP(e, hipStreamSynchronize(s)); DM_HIP(e, hipFree(e->loop_buf)); e->loop_buf = nullptr; e->loop_bytes = 0; }
+    DM_HIP(e, hipMalloc((void**)&e->loop_buf, bytes));
+    e->loop_bytes = bytes;
     return 0;
 }
 
@@ -850,7 +954,8 @@ void dm_f32_destroy(dm_f32_net* e) {
     if (!e) return;
     (void)hipSetDevice(e->device);
     (void)hipDeviceSynchronize();
-    for (float* slab : {e->w_unet.slab, e->w_vae.slab, e->w_clip.slab, e->w_clipv.slab, e->w_clipt.slab}) if (slab) (void)hipFree(slab);
+    for (float* slab : {e->w_unet.slab, e->w_vae.slab, e->w_vaed.slab, e->w_clip.slab, e->w_clipv.slab, e->w_clipt.slab}) if (slab) (void)hipFree(slab);
+    if (e->loop_buf) (void)hipFree(e->loop_buf);
     if (e->sched_tab) (void)hipFree(e->sched_tab);
     if (e->score_tmp) (void)hipFree(e->score_tmp);
     if (e->arena_base) (void)hipFree(e->arena_base);
@@ -1339,6 +1444,196 @@ int dm_f32_clip_tower_image_tokens(dm_f32_net* e, const void* images_u8_dev, con
     return run_tower_chunked32(e, A, stream, "dm_f32_clip_tower_image_tokens");
 }
 
+int dm_f32_load_vae_decoder_weight(dm_f32_net* e, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim) {
+    if (!e || !name || !host_ptr || !shape) return 1;
+    if (e->w_vaed.ready) DM_FAIL(e, "load_vae_decoder_weight after finalize_vae_decoder");
+    std::string nm(name);
+    if (nm.rfind("vae.", 0) == 0) nm = nm.substr(4);
+    if (nm.rfind("encoder.", 0) == 0 || nm.rfind("quant_conv.", 0) == 0) return 0;          // the encoder's half
+    static const char* legacy[4][2] = {{".query.", ".to_q."}, {".key.", ".to_k."}, {".value.", ".to_v."}, {".proj_attn.", ".to_out.0."}};
+    for (auto& l : legacy) { const size_t at = nm.find(l[0]); if (at != std::string::npos) nm.replace(at, strlen(l[0]), l[1]); }
+    if (nm.find(".attentions.0.to_") != std::string::npos && ndim == 4 && shape[2] == 1 && shape[3] == 1) ndim = 2;      // [C, C, 1, 1] -> [C, C]
+    return dm::stage_tensor(e->w_vaed.host, nm, host_ptr, dtype, shape, ndim, e->err);
+}
+
+int dm_f32_finalize_vae_decoder(dm_f32_net* e) {
+    if (!e) return 1;
+    if (e->w_vaed.ready) return 0;
+    DM_HIP(e, hipSetDevice(e->device));
+    Packer32 P{e, e->w_vaed};
+    VaeDec32& v = e->vaed;
+    const int C = VBOC[VNB - 1];
+    {
+        HostT* qw = P.get("post_quant_conv.weight", {4, 4, 1, 1});
+        HostT* qb = P.get("post_quant_conv.bias", {4});
+        HostT* w = P.get("decoder.conv_in.weight", {C, 4, 3, 3});
+        if (!qw || !qb || !w) return 1;
+        v.pqw = P.put(qw->data.data(), 16);
+        v.pqb = P.put(qb->data.data(), 4);
+        std::vector<float> wt((size_t)36 * C);
+        for (int co = 0; co < C; ++co)
+            for (int k = 0; k < 36; ++k) wt[(size_t)k * C + co] = w->data[(size_t)co * 36 + k];
+        v.conv_in.w = P.put(wt.data(), wt.size());
+        v.conv_in.cin = 4; v.conv_in.cout = C; v.conv_in.k = 3;
+        DM_TRY(pack_vec(P, "decoder.conv_in.bias", C, &v.conv_in.b));
+    }
+    DM_TRY(pack_vae_res(P, "decoder.mid_block.resnets.0", C, C, &v.mid[0]));
+    {
+        const std::string a = "decoder.mid_block.attentions.0";
+        DM_TRY(pack_norm(P, a + ".group_norm", C, &v.attn_gn));
+        DM_TRY(pack_qkv(P, {a + ".to_q", a + ".to_k", a + ".to_v"}, C, &v.qkv));
+        DM_TRY(pack_dense(P, a + ".to_out.0", C, C, false, true, &v.o));
+    }
+    DM_TRY(pack_vae_res(P, "decoder.mid_block.resnets.1", C, C, &v.mid[1]));
+    int cin = C;
+    for (int i = 0; i < VNB; ++i) {
+        const int cout = VBOC[VNB - 1 - i];
+        const std::string bn = "decoder.up_blocks." + std::to_string(i);
+        for (int j = 0; j < 3; ++j) DM_TRY(pack_vae_res(P, bn + ".resnets." + std::to_string(j), j == 0 ? cin : cout, cout, &v.up[i][j]));
+        if (i != VNB - 1) {
+            DM_TRY(pack_conv3(P, bn + ".upsamplers.0.conv", cout, cout, &v.us[i]));
+            DM_TRY(pack_upconv4(P, bn + ".upsamplers.0.conv", cout, cout, v.us[i], &v.us4[i]));
+        }
+        cin = cout;
+    }
+    DM_TRY(pack_norm(P, "decoder.conv_norm_out", VBOC[0], &v.norm_out));
+    DM_TRY(pack_conv3(P, "decoder.conv_out", 3, VBOC[0], &v.conv_out));
+    return P.finish("VAE decoder", 140);
+}
+
+/* `vae.decode(latent * latent_scale).sample` in fp32 and the reference's post-processing (pnp.py:137-142, :531-536, :590-591) */
+int dm_f32_vae_decode(dm_f32_net* e, const void* latent_dev, int batch, int h, int w, float latent_scale, int raw, void* out_f32_dev,
+                      void* out_u8_dev, void* stream) {
+    if (!e) return 1;
+    if (!e->w_vaed.ready) DM_FAIL(e, "dm_f32_vae_decode: no VAE decoder weights (dm_f32_load_vae_decoder_weight / dm_f32_finalize_vae_decoder)");
+    if (!latent_dev || (!out_f32_dev && !out_u8_dev)) DM_FAIL(e, "dm_f32_vae_decode: bad argument");
+    if (batch <= 0 || h < 1 || w < 1 || h > 8192 || w > 8192) DM_FAIL(e, "dm_f32_vae_decode: bad batch / latent size");
+    DM_HIP(e, hipSetDevice(e->device));
+    hipStream_t s = (hipStream_t)stream;
+    const long long area = 64LL * h * w;
+    long long chunk = 2LL * 512 * 512 / area;                 // ~1.2 GB of fp32 activations per 512 x 512 image (four live [512,512,256] tensors in a resnet)
+    chunk = chunk < 1 ? 1 : chunk;
+    for (int b0 = 0; b0 < batch; b0 += (int)chunk) {
+        VaeDecArgs32 A;
+        A.B = batch - b0 < chunk ? batch - b0 : (int)chunk; A.h = h; A.w = w; A.scale = latent_scale; A.raw = raw != 0;
+        A.latent = (const float*)latent_dev + (size_t)b0 * 4 * h * w;
+        A.out_f32 = out_f32_dev ? (float*)out_f32_dev + (size_t)b0 * 3 * area : nullptr;
+        A.out_u8 = out_u8_dev ? (uint8_t*)out_u8_dev + (size_t)b0 * 3 * area : nullptr;
+        DM_TRY(ensure_arena_for32(e, s, {5, A.B, A.h, A.w, dm::option(dm::OPT_UP_FOLD) ? 1 : 0}, [&]() { return run_vae_dec32(e, A, s, true); }));
+        DM_TRY(run_vae_dec32(e, A, s, false));
+    }
+    return 0;
+}
+
+/* One U-Net forward with Plug-and-Play's injection (pnp.py:345-350, :424-432): sample 0 is the source; masks of 0 = dm_f32_unet_forward */
+int dm_f32_unet_forward_inject(dm_f32_net* e, const void* sample_dev, const int64_t* t_dev, const int32_t* slot_dev, int batch, int h, int w,
+                               int conv_mask, int attn_mask, void* out_dev, void* stream) {
+    if (!e || !sample_dev || !t_dev || !slot_dev || !out_dev) return 1;
+    if (conv_mask < 0 || attn_mask < 0 || conv_mask >= (1 << 14) || attn_mask >= (1 << 13)) DM_FAIL(e, "dm_f32_unet_forward_inject: bad layer mask");
+    if ((conv_mask || attn_mask) && batch > chunk32(h, w))
+        DM_FAIL(e, "dm_f32_unet_forward_inject: %d samples do not fit one run (%d at %d x %d): the source must share a run with its targets", batch, chunk32(h, w), h, w);
+    Args32 A{(const float*)sample_dev, t_dev, slot_dev, batch, h, w, -1, (float*)out_dev, nullptr, nullptr, 1};
+    A.conv_mask = (unsigned)conv_mask; A.attn_mask = (unsigned)attn_mask;
+    return run_chunked32(e, A, stream);
+}
+
+/* n_steps DDIM updates on the device queue (pnp.py:156-203): eps = UNet(x, t_i, prompt[slot]); x = step(x, eps, coef_i); optionally
+ * traj[save_row[i]] = x.  No host synchronisation inside the loop; tables uploaded and the arena sized before it. */
+int dm_f32_ddim_run(dm_f32_net* e, void* x_dev, const int64_t* t_host, const float* coef_host, const int32_t* slot_dev, const int32_t* save_row_host,
+                    void* traj_dev, int B, int h, int w, int n_steps, void* stream) {
+    if (!e) return 1;
+    if (n_steps <= 0) DM_FAIL(e, "dm_f32_ddim_run: n_steps %d", n_steps);
+    if (!x_dev || !t_host || !coef_host || !slot_dev) DM_FAIL(e, "dm_f32_ddim_run: bad argument");
+    if (save_row_host && !traj_dev) DM_FAIL(e, "dm_f32_ddim_run: save rows without a trajectory buffer");
+    if (!e->finalized) DM_FAIL(e, "fp32 net not finalized");
+    if (e->n_prompts <= 0) DM_FAIL(e, "dm_f32_set_prompts must be called first");
+    if (B <= 0 || h < 1 || w < 1) DM_FAIL(e, "dm_f32_ddim_run: bad batch / latent size");
+    if (B > chunk32(h, w)) DM_FAIL(e, "dm_f32_ddim_run: batch %d over the %d samples of one run at %d x %d", B, chunk32(h, w), h, w);
+    for (int i = 0; i < n_steps; ++i) if (t_host[i] < 0 || t_host[i] > 999) DM_FAIL(e, "dm_f32_ddim_run: timestep %lld out of range", (long long)t_host[i]);
+    DM_HIP(e, hipSetDevice(e->device));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t per = (size_t)4 * h * w, n = (size_t)B * per;
+    const size_t off_t = (n * sizeof(float) + 255) & ~(size_t)255, off_c = off_t + (((size_t)n_steps * B * sizeof(int64_t) + 255) & ~(size_t)255);
+    DM_TRY(loop_reserve32(e, s, off_c + (size_t)n_steps * 4 * sizeof(float)));
+    float* eps = (float*)e->loop_buf;
+    int64_t* t_dev = (int64_t*)(e->loop_buf + off_t);
+    float* coef = (float*)(e->loop_buf + off_c);
+    {
+        std::vector<int64_t> tt((size_t)n_steps * B);
+        for (int i = 0; i < n_steps; ++i) for (int b = 0; b < B; ++b) tt[(size_t)i * B + b] = t_host[i];
+        // the loop buffer is shared by every loop of this net: an earlier loop queued on `s` may still read its tables, and the blocking copy
+        // runs on the null stream, which a non-blocking `s` is not ordered with — so the queue drains first (once, before the loop)
+        DM_HIP(e, hipStreamSynchronize(s));
+        DM_HIP(e, hipMemcpy(t_dev, tt.data(), tt.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+        DM_HIP(e, hipMemcpy(coef, coef_host, (size_t)n_steps * 4 * sizeof(float), hipMemcpyHostToDevice));
+    }
+    Args32 A{(const float*)x_dev, t_dev, slot_dev, B, h, w, -1, eps, nullptr, nullptr, 1};
+    DM_TRY(ensure_arena32(e, A, s));
+    for (int i = 0; i < n_steps; ++i) {
+        A.t = t_dev + (size_t)i * B;
+        DM_TRY(ensure_arena32(e, A, s));              // a map lookup: the dry run and the allocation happened before the loop
+        DM_TRY(run_forward32(e, A, s, false));
+        DM_HIP(e, launch_ddim_step((const float*)x_dev, eps, nullptr, 0.f, coef + 4 * i, (long long)n, (float*)x_dev, s));
+        if (save_row_host && save_row_host[i] >= 0)
+            DM_HIP(e, hipMemcpyAsync((float*)traj_dev + (size_t)save_row_host[i] * n, x_dev, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    }
+    return 0;
+}
+
+/* Plug-and-Play sampling (pnp.py:538-577) for B targets of one source: per step the batch [source_i, x (uncond slots), x (cond slots)], the
+ * injected forward, classifier-free guidance and DDIMScheduler.step.  The reference repeats the source B times; its rows are identical. */
+int dm_f32_pnp_run(dm_f32_net* e, void* x_dev, const void* src_dev, const int64_t* t_host, const float* coef_host, const uint8_t* conv_on_host,
+                   const uint8_t* attn_on_host, int conv_mask, int attn_mask, const int32_t* slot_dev, int B, int h, int w, int n_steps,
+                   float guidance_scale, void* stream) {
+    if (!e) return 1;
+    if (n_steps <= 0) DM_FAIL(e, "dm_f32_pnp_run: n_steps %d", n_steps);
+    if (!x_dev || !src_dev || !t_host || !coef_host || !conv_on_host || !attn_on_host || !slot_dev) DM_FAIL(e, "dm_f32_pnp_run: bad argument");
+    if (conv_mask < 0 || attn_mask < 0 || conv_mask >= (1 << 14) || attn_mask >= (1 << 13)) DM_FAIL(e, "dm_f32_pnp_run: bad layer mask");
+    if (!e->finalized) DM_FAIL(e, "fp32 net not finalized");
+    if (e->n_prompts <= 0) DM_FAIL(e, "dm_f32_set_prompts must be called first");
+    if (B <= 0 || h < 1 || w < 1) DM_FAIL(e, "dm_f32_pnp_run: bad batch / latent size");
+    const int N = 1 + 2 * B;
+    if (N > chunk32(h, w))
+        DM_FAIL(e, "dm_f32_pnp_run: 1 + 2 * %d samples over the %d of one run at %d x %d: the source must share a run with its targets", B, chunk32(h, w), h, w);
+    for (int i = 0; i < n_steps; ++i) if (t_host[i] < 0 || t_host[i] > 999) DM_FAIL(e, "dm_f32_pnp_run: timestep %lld out of range", (long long)t_host[i]);
+    DM_HIP(e, hipSetDevice(e->device));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t per = (size_t)4 * h * w, nb = (size_t)B * per;
+    const size_t in_bytes = ((size_t)N * per * sizeof(float) + 255) & ~(size_t)255;
+    const size_t off_t = 2 * in_bytes, off_c = off_t + (((size_t)n_steps * N * sizeof(int64_t) + 255) & ~(size_t)255);
+    DM_TRY(loop_reserve32(e, s, off_c + (size_t)n_steps * 4 * sizeof(float)));
+    float* in = (float*)e->loop_buf;
+    float* eps = (float*)(e->loop_buf + in_bytes);
+    int64_t* t_dev = (int64_t*)(e->loop_buf + off_t);
+    float* coef = (float*)(e->loop_buf + off_c);
+    {
+        std::vector<int64_t> tt((size_t)n_steps * N);
+        for (int i = 0; i < n_steps; ++i) for (int b = 0; b < N; ++b) tt[(size_t)i * N + b] = t_host[i];
+        // the loop buffer is shared by every loop of this net: an earlier loop queued on `s` may still read its tables, and the blocking copy
+        // runs on the null stream, which a non-blocking `s` is not ordered with — so the queue drains first (once, before the loop)
+        DM_HIP(e, hipStreamSynchronize(s));
+        DM_HIP(e, hipMemcpy(t_dev, tt.data(), tt.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+        DM_HIP(e, hipMemcpy(coef, coef_host, (size_t)n_steps * 4 * sizeof(float), hipMemcpyHostToDevice));
+    }
+    Args32 A{in, t_dev, slot_dev, N, h, w, -1, eps, nullptr, nullptr, 1};
+    for (int pass = 0; pass < 2; ++pass) {            // both arena sizes (with and without the feature injection) before the loop
+        A.conv_mask = pass ? (unsigned)conv_mask : 0;
+        DM_TRY(ensure_arena32(e, A, s));
+    }
+    for (int i = 0; i < n_steps; ++i) {
+        DM_HIP(e, hipMemcpyAsync(in, (const float*)src_dev + (size_t)i * per, per * sizeof(float), hipMemcpyDeviceToDevice, s));
+        DM_HIP(e, hipMemcpyAsync(in + per, x_dev, nb * sizeof(float), hipMemcpyDeviceToDevice, s));
+        DM_HIP(e, hipMemcpyAsync(in + per + nb, x_dev, nb * sizeof(float), hipMemcpyDeviceToDevice, s));
+        A.t = t_dev + (size_t)i * N;
+        A.conv_mask = conv_on_host[i] ? (unsigned)conv_mask : 0;
+        A.attn_mask = attn_on_host[i] ? (unsigned)attn_mask : 0;
+        DM_TRY(ensure_arena32(e, A, s));
+        DM_TRY(run_forward32(e, A, s, false));
+        DM_HIP(e, launch_ddim_step((const float*)x_dev, eps + per, eps + per + nb, guidance_scale, coef + 4 * i, (long long)nb, (float*)x_dev, s));
+    }
+    return 0;
+}
+
 int dm_f32_prof_enable(dm_f32_net* e, int on) {
     if (!e) return 1;
     e->prof = on != 0;
@@ -1373,7 +1668,7 @@ int dm_f32_prof_read(dm_f32_net* e, double* gemm_ms, double* gemm_flops, int64_t
 
 int dm_f32_memory(dm_f32_net* e, size_t* weights_bytes, size_t* arena_bytes) {
     if (!e) return 1;
-    if (weights_bytes) *weights_bytes = e->w_unet.bytes + e->w_vae.bytes + e->w_clip.bytes + e->w_clipv.bytes + e->w_clipt.bytes;
+    if (weights_bytes) *weights_bytes = e->w_unet.bytes + e->w_vae.bytes + e->w_vaed.bytes + e->w_clip.bytes + e->w_clipv.bytes + e->w_clipt.bytes;
     if (arena_bytes) *arena_bytes = e->arena_cap;
     return 0;
 }
@@ -1404,6 +1699,31 @@ int dm_f32_op_groupnorm(void* stream, const void* X, const void* X2, int N, int 
     hipStream_t s = (hipStream_t)stream;
     if (launch_gn_stats((const float*)X, (const float*)X2, N, HW, C, C1, G, eps, (float*)stats_work, s) != hipSuccess) return 1;
     return launch_gn_apply((const float*)X, (const float*)X2, N, HW, C, C1, G, gamma, beta, (const float*)stats_work, silu, (float*)Y, s) == hipSuccess ? 0 : 1;
+}
+
+/* the kernels of the parallel-dataset generator (pnp.hip), one by one */
+int dm_f32_op_ddim_step(void* stream, const void* x, const void* eps, const float* coef4, int64_t n, void* out) {
+    return launch_ddim_step((const float*)x, (const float*)eps, nullptr, 0.f, coef4, (long long)n, (float*)out, (hipStream_t)stream) == hipSuccess ? 0 : 1;
+}
+
+int dm_f32_op_ddim_step_cfg(void* stream, const void* x, const void* eps_u, const void* eps_c, float g, const float* coef4, int64_t n, void* out) {
+    if (!eps_c) return 1;
+    return launch_ddim_step((const float*)x, (const float*)eps_u, (const float*)eps_c, g, coef4, (long long)n, (float*)out, (hipStream_t)stream) == hipSuccess ? 0 : 1;
+}
+
+int dm_f32_op_bcast_add(void* stream, const void* R, const void* Hs, int B, int64_t per, void* Y) {
+    return launch_bcast_add((const float*)R, (const float*)Hs, B, (long long)per, (float*)Y, (hipStream_t)stream) == hipSuccess ? 0 : 1;
+}
+
+int dm_f32_op_decoder_tail(void* stream, const void* X, const void* stats, const float* gamma, const float* beta, const void* Wp, const float* bias,
+                           int B, int H, int W, int C, int raw, void* out_f32, void* out_u8) {
+    return launch_decoder_tail((const float*)X, (const float*)stats, gamma, beta, (const float*)Wp, bias, B, H, W, C, raw, (float*)out_f32, (uint8_t*)out_u8,
+                               (hipStream_t)stream) == hipSuccess ? 0 : 1;
+}
+
+/* conv_out of the two-kernel tail (X NHWC [B,H,W,C] already normalised, Wp [Cout <= 8][9 C], Y NCHW): what the fused tail is measured against */
+int dm_f32_op_conv_out(void* stream, const void* X, const void* Wp, const float* bias, int B, int H, int W, int C, int Cout, void* Y) {
+    return launch_conv_out((const float*)X, (const float*)Wp, bias, B, H, W, C, Cout, (float*)Y, (hipStream_t)stream) == hipSuccess ? 0 : 1;
 }
 
 int dm_f32_op_layernorm(void* stream, const void* X, int rows, int C, const float* gamma, const float* beta, float eps, void* Y) {

@@ -113,6 +113,12 @@ SIGNATURES = {
     "dm_f32_load_vae_weight": (_i32, _WEIGHT),
     "dm_f32_finalize_vae": (_i32, [_vp]),
     "dm_f32_vae_encode": (_i32, [_vp, _vp, _vp] + [_i32] * 4 + [_f32, _vp, _vp, _vp]),
+    "dm_f32_load_vae_decoder_weight": (_i32, _WEIGHT),
+    "dm_f32_finalize_vae_decoder": (_i32, [_vp]),
+    "dm_f32_vae_decode": (_i32, [_vp, _vp, _i32, _i32, _i32, _f32, _i32, _vp, _vp, _vp]),
+    "dm_f32_unet_forward_inject": (_i32, [_vp] * 4 + [_i32] * 5 + [_vp, _vp]),
+    "dm_f32_ddim_run": (_i32, [_vp] * 7 + [_i32] * 4 + [_vp]),
+    "dm_f32_pnp_run": (_i32, [_vp] * 7 + [_i32, _i32, _vp] + [_i32] * 4 + [_f32, _vp]),
     "dm_f32_load_clip_weight": (_i32, _WEIGHT),
     "dm_f32_finalize_clip": (_i32, [_vp]),
     "dm_f32_clip_encode": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp]),
@@ -136,6 +142,11 @@ SIGNATURES = {
     "dm_f32_op_groupnorm": (_i32, [_vp, _vp, _vp] + [_i32] * 5 + [_f32, _vp, _vp, _i32, _vp, _vp]),
     "dm_f32_op_layernorm": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _f32, _vp]),
     "dm_f32_op_clip_patch_ln": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _f32, _vp]),
+    "dm_f32_op_ddim_step": (_i32, [_vp] * 4 + [_i64, _vp]),
+    "dm_f32_op_ddim_step_cfg": (_i32, [_vp] * 4 + [_f32, _vp, _i64, _vp]),
+    "dm_f32_op_bcast_add": (_i32, [_vp, _vp, _vp, _i32, _i64, _vp]),
+    "dm_f32_op_decoder_tail": (_i32, [_vp] * 7 + [_i32] * 5 + [_vp, _vp]),
+    "dm_f32_op_conv_out": (_i32, [_vp] * 4 + [_i32] * 5 + [_vp]),
 }
 SYMBOLS = list(SIGNATURES)
 
@@ -1117,6 +1128,90 @@ class UNetEngineF32(_EngineBase):
                                                B, int(draws_per_image), H, W, float(scaling_factor), _p(lat),
                                                _p(mom), self._stream()), "dm_f32_vae_encode")
         return (lat, mom) if return_moments else lat
+
+    # -- the parallel-dataset generator (applications/parallel-dataset/pnp.py; see diff_mining_amd.pnp) ------------------------------
+    def load_vae_decoder_state_dict(self, sd: Dict[str, "np.ndarray"]):
+        """sd: `AutoencoderKL.state_dict()`; only `post_quant_conv.*` and `decoder.*` are used (140 tensors), the encoder half is
+        ignored.  A weight set of its own, beside `load_vae_state_dict`."""
+        self._load("_vae_decoder", sd)
+        self._vae_decoder_ready = True
+
+    def vae_decode(self, latent, raw: bool = False, want: str = "f32", latent_scale=None):
+        """`vae.decode(1 / 0.18215 * latent).sample` in fp32 (pnp.py:137-142, :531-536).  latent [B,4,h,w].  want "f32": [B,3,8h,8w]
+        fp32, the sample if `raw`, else `(sample / 2 + 0.5).clamp(0, 1)`; "u8": [B,8h,8w,3] uint8 = that image * 255 truncated
+        (`pilify`, pnp.py:590-591); "both": the pair."""
+        torch = self._torch
+        assert want in ("f32", "u8", "both"), want
+        latent = latent.to(self.device, torch.float32).contiguous()
+        B, c, h, w = latent.shape
+        assert c == 4, latent.shape
+        scale = np.float32(1 / 0.18215) if latent_scale is None else np.float32(latent_scale)      # fp32 tensor * Python scalar
+        f = torch.empty(B, 3, 8 * h, 8 * w, dtype=torch.float32, device=self.device) if want != "u8" else None
+        u = torch.empty(B, 8 * h, 8 * w, 3, dtype=torch.uint8, device=self.device) if want != "f32" else None
+        self._check(self.lib.dm_f32_vae_decode(self._h, _p(latent), B, h, w, float(scale), int(bool(raw)), _p(f), _p(u), self._stream()),
+                    "dm_f32_vae_decode")
+        return f if want == "f32" else u if want == "u8" else (f, u)
+
+    def unet_inject(self, sample, t, slots, conv_mask: int = 0, attn_mask: int = 0):
+        """One U-Net forward with Plug-and-Play's injection (pnp.py:345-350, :424-432): sample [1 + n,4,h,w], row 0 the source.  Masks as
+        `pnp.injection_plan` gives them; masks of 0 = `unet`."""
+        torch = self._torch
+        sample = sample.to(self.device, torch.float32).contiguous()
+        B, _, h, w = sample.shape
+        t = self._timesteps(t, B)
+        s = self._slots(slots, B)
+        out = torch.empty(B, 4, h, w, dtype=torch.float32, device=self.device)
+        self._check(self.lib.dm_f32_unet_forward_inject(self._h, _p(sample), _p(t), _p(s), B, h, w, int(conv_mask), int(attn_mask), _p(out),
+                                                        self._stream()), "dm_f32_unet_forward_inject")
+        return out
+
+    @staticmethod
+    def _loop_tables(timesteps, coef):
+        t = np.ascontiguousarray(np.asarray(timesteps, dtype=np.int64).reshape(-1))
+        c = np.ascontiguousarray(np.asarray(coef, dtype=np.float32).reshape(-1, 4))
+        if c.shape[0] != t.shape[0]:
+            raise ValueError(f"{t.shape[0]} timesteps but {c.shape[0]} coefficient rows")
+        return t, c
+
+    def ddim_run(self, x, timesteps, coef, slots, save_rows=None, n_rows: int = 0):
+        """`len(timesteps)` DDIM updates of x [B,4,h,w] on the device queue (pnp.py:156-203): eps = unet(x, t_i, slots), then
+        x = c0 * ((x - c1 * eps) / c2) + c3 * eps with row i of `coef` (`pnp.ddim_coefficients`).  save_rows [n] (-1: not kept) names the
+        row of the returned trajectory [n_rows,B,4,h,w] that keeps the x after step i.  Returns (x, trajectory or None); x is a new
+        tensor."""
+        torch = self._torch
+        x = x.to(self.device, torch.float32).contiguous().clone()
+        B, _, h, w = x.shape
+        t, c = self._loop_tables(timesteps, coef)
+        s = self._slots(slots, B)
+        save = traj = None
+        if save_rows is not None:
+            save = np.ascontiguousarray(np.asarray(save_rows, dtype=np.int32).reshape(-1))
+            if save.shape[0] != t.shape[0] or (save.size and int(save.max()) >= n_rows):
+                raise ValueError("save_rows must hold one row index below n_rows (or -1) per step")
+            traj = torch.zeros(max(n_rows, 1), B, 4, h, w, dtype=torch.float32, device=self.device)
+        self._check(self.lib.dm_f32_ddim_run(self._h, _p(x), t.ctypes.data_as(C.c_void_p), c.ctypes.data_as(C.c_void_p), _p(s),
+                                             save.ctypes.data_as(C.c_void_p) if save is not None else None, _p(traj), B, h, w, int(t.shape[0]),
+                                             self._stream()), "dm_f32_ddim_run")
+        return x, traj
+
+    def pnp_run(self, x, source, timesteps, coef, conv_on, attn_on, conv_mask: int, attn_mask: int, slots, guidance_scale: float = 7.5):
+        """Plug-and-Play sampling (pnp.py:538-577) of B targets x [B,4,h,w] of one source: source [n,4,h,w] = its latent at
+        timesteps[i]; slots [1 + 2B] = (source, B unconditional, B conditional prompts).  Returns the new x."""
+        torch = self._torch
+        x = x.to(self.device, torch.float32).contiguous().clone()
+        B, _, h, w = x.shape
+        t, c = self._loop_tables(timesteps, coef)
+        n = int(t.shape[0])
+        source = source.to(self.device, torch.float32).contiguous()
+        assert source.shape == (n, 4, h, w), (source.shape, (n, 4, h, w))
+        on_c = np.ascontiguousarray(np.asarray(conv_on, dtype=np.uint8).reshape(-1))
+        on_a = np.ascontiguousarray(np.asarray(attn_on, dtype=np.uint8).reshape(-1))
+        assert on_c.shape == (n,) and on_a.shape == (n,), (on_c.shape, on_a.shape, n)
+        s = self._slots(slots, 1 + 2 * B)
+        self._check(self.lib.dm_f32_pnp_run(self._h, _p(x), _p(source), t.ctypes.data_as(C.c_void_p), c.ctypes.data_as(C.c_void_p),
+                                            on_c.ctypes.data_as(C.c_void_p), on_a.ctypes.data_as(C.c_void_p), int(conv_mask), int(attn_mask), _p(s),
+                                            B, h, w, n, float(guidance_scale), self._stream()), "dm_f32_pnp_run")
+        return x
 
     def score(self, x, eps, t, slots, x_index=None):
         """SD.compute_loss (compute.py:95-102) with no autocast: fp32 add_noise, fp32 U-Net, fp32 squared error -> [B,4,h,w] fp32.

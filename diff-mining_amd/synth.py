@@ -259,6 +259,16 @@ def synth_vae_state_dict(cfg=None, seed: int = 0, dtype=np.float32) -> dict:
     return out
 
 
+def synth_vae_decoder_state_dict(cfg=None, seed: int = 0, dtype=np.float32) -> dict:
+    """Synthetic `post_quant_conv.*` / `decoder.*` tensors of the SDv1.5 VAE (see vae_spec.py)."""
+    from .vae_spec import SD15_VAE, vae_decoder_tensor_spec
+    out = {}
+    for name, shape in vae_decoder_tensor_spec(cfg or SD15_VAE):
+        t = synth_tensor("vae." + name, shape, seed)
+        out[name] = t if dtype == np.float32 else t.astype(dtype)
+    return out
+
+
 def synth_clip_state_dict(cfg=None, seed: int = 0, dtype=np.float32) -> dict:
     """Synthetic CLIP text-tower tensors (see clip_spec.py).  Embeddings ~ N(0, 0.02) like the real model's
     initialiser range; linear layers fan-in scaled."""

@@ -7,7 +7,10 @@ the un-vendored diffusers dependency; this module restates the names and shapes 
 state dict from the public SDv1.5 `vae/config.json` (block_out_channels 128/256/512/512,
 layers_per_block 2, 32 groups, latent_channels 4, scaling_factor 0.18215) so a checkpoint can be
 checked before packing and synthetic weights of that architecture can be generated offline.
-`decoder.*` / `post_quant_conv.*` tensors of a full VAE state dict are not on the path and are ignored.
+`decoder.*` / `post_quant_conv.*` tensors of a full VAE state dict are not on that path and are ignored there.
+
+The decoder half (`vae.decode`, the parallel-dataset generator: `applications/parallel-dataset/pnp.py:137-142`, `:531-536`) is a weight
+set of its own with an inventory of its own: `vae_decoder_tensor_spec` / `canonical_vae_decoder_name`.
 """
 from __future__ import annotations
 
@@ -92,6 +95,57 @@ def canonical_vae_name(name: str):
     if name.startswith("vae."):
         name = name[4:]
     if name.startswith("decoder.") or name.startswith("post_quant_conv."):
+        return None
+    if ".attentions.0." in name:
+        head, leaf = name.split(".attentions.0.", 1)
+        mod, _, wb = leaf.rpartition(".")
+        if mod in LEGACY_ATTN_NAMES:
+            return f"{head}.attentions.0.{LEGACY_ATTN_NAMES[mod]}.{wb}"
+    return name
+
+
+def vae_decoder_tensor_spec(cfg: VAEConfig = SD15_VAE) -> List[Tuple[str, Tuple[int, ...]]]:
+    """Ordered (name, shape) list: `post_quant_conv.*` and `decoder.*` of `AutoencoderKL.state_dict()` (diffusers 0.24 `Decoder`:
+    conv_in, mid block, four `UpDecoderBlock2D` of layers_per_block + 1 resnets over the reversed channel list, all but the last followed
+    by `Upsample2D`; conv_norm_out, conv_out)."""
+    boc = tuple(reversed(cfg.block_out_channels))
+    t: List[Tuple[str, Tuple[int, ...]]] = []
+    t += _conv("post_quant_conv", cfg.latent_channels, cfg.latent_channels, 1)
+    c = boc[0]
+    t += _conv("decoder.conv_in", c, cfg.latent_channels, 3)
+    t += _resnet("decoder.mid_block.resnets.0", c, c)
+    a = "decoder.mid_block.attentions.0"
+    t += _norm(f"{a}.group_norm", c)
+    for leaf in ("to_q", "to_k", "to_v", "to_out.0"):
+        t += [(f"{a}.{leaf}.weight", (c, c)), (f"{a}.{leaf}.bias", (c,))]
+    t += _resnet("decoder.mid_block.resnets.1", c, c)
+    cin = c
+    for i, cout in enumerate(boc):
+        for j in range(cfg.layers_per_block + 1):
+            t += _resnet(f"decoder.up_blocks.{i}.resnets.{j}", cin if j == 0 else cout, cout)
+        if i != len(boc) - 1:
+            t += _conv(f"decoder.up_blocks.{i}.upsamplers.0.conv", cout, cout, 3)
+        cin = cout
+    t += _norm("decoder.conv_norm_out", boc[-1])
+    t += _conv("decoder.conv_out", cfg.in_channels, boc[-1], 3)
+    return t
+
+
+def vae_decoder_param_count(cfg: VAEConfig = SD15_VAE) -> int:
+    n = 0
+    for _, shp in vae_decoder_tensor_spec(cfg):
+        k = 1
+        for s in shp:
+            k *= s
+        n += k
+    return n
+
+
+def canonical_vae_decoder_name(name: str):
+    """Map a key of a VAE state dict to the decoder set's name; None for the encoder's half."""
+    if name.startswith("vae."):
+        name = name[4:]
+    if name.startswith("encoder.") or name.startswith("quant_conv."):
         return None
     if ".attentions.0." in name:
         head, leaf = name.split(".attentions.0.", 1)

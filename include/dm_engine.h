@@ -781,6 +781,39 @@ int dm_f32_load_vae_weight(dm_f32_net* e, const char* name, const void* host_ptr
 int dm_f32_finalize_vae(dm_f32_net* e);
 int dm_f32_vae_encode(dm_f32_net* e, const void* image_dev, const void* noise_dev, int batch, int draws_per_image, int H, int W,
                       float scaling_factor, void* latent_dev, void* moments_dev, void* stream);
+/* optional AutoencoderKL decoder in fp32, a weight set of its own: `vae.decode(1 / 0.18215 * latents).sample` of the parallel-dataset generator
+ * (applications/parallel-dataset/pnp.py:137-142, :531-536; its pipelines have no torch_dtype and no autocast).  State-dict names:
+ * `post_quant_conv.*` and `decoder.*` of a full AutoencoderKL state dict (140 tensors), optional `vae.` prefix, encoder tensors ignored, legacy
+ * attention names accepted.  latent_dev [batch,4,h,w] fp32; z = latent * latent_scale (pass (float)(1 / 0.18215)); out_f32_dev [batch,3,8h,8w]
+ * fp32 = the sample if raw, else `(sample / 2 + 0.5).clamp(0, 1)`; out_u8_dev [batch,8h,8w,3] uint8 = that image * 255, truncated as the
+ * reference's `.astype(np.uint8)` (pnp.py:590-591).  Either output may be NULL, not both. */
+int dm_f32_load_vae_decoder_weight(dm_f32_net* e, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim);
+int dm_f32_finalize_vae_decoder(dm_f32_net* e);
+int dm_f32_vae_decode(dm_f32_net* e, const void* latent_dev, int batch, int h, int w, float latent_scale, int raw, void* out_f32_dev,
+                      void* out_u8_dev, void* stream);
+/* The generator's loops on the device queue (pnp.py:156-203, :538-577): no host synchronisation inside, tables uploaded and the arena sized
+ * before the first step.  coef_host [n_steps][4] = (c0, c1, c2, c3) of x' = c0 * ((x - c1 * eps) / c2) + c3 * eps, built by the host as the
+ * reference builds its scalars (fp32 torch, diff_mining_amd.pnp.ddim_coefficients); t_host [n_steps] = the timestep of every sample of step i.
+ * dm_f32_unet_forward_inject: one forward with Plug-and-Play's injection, sample 0 = the source; mask bit 3 * res + block = up_blocks[res]
+ * resnet (conv_mask) or attn1 (attn_mask) `block`, bits 12.. = the mid block's; at a masked resnet every sample's output is
+ * shortcut(x_n) + the source's conv2 output, at a masked attn1 every sample attends with the source's queries and keys and its own values;
+ * masks of 0 = dm_f32_unet_forward.  With a mask set the whole batch must fit one run.
+ * dm_f32_ddim_run: x_dev [B,4,h,w] in / out; per step eps = UNet(x, t_i, prompt[slot_dev[b]]), the update, and, if save_row_host[i] >= 0, a copy
+ * of the new x to row save_row_host[i] of traj_dev [rows][B,4,h,w] (both may be NULL).
+ * dm_f32_pnp_run: B targets of one source.  src_dev [n_steps][4][h][w] = the source's latent at t_i; per step the batch [source, x, x] of
+ * 1 + 2 B samples with slot_dev [1 + 2 B] = (source, B unconditional, B conditional prompts), the injected forward (conv_on_host[i] /
+ * attn_on_host[i] switch the masks per step), eps = eps_u + g * (eps_c - eps_u), the update of x_dev [B,4,h,w].
+ * Prompt slots live on the device, as for dm_f32_unet_forward: these entries cannot range-check them without a synchronisation and do not;
+ * the attention kernels clamp a slot to the registered prompts (memory-safe), and the Python binding range-checks host-side slots before
+ * the call (EngineError).  The loops of one net share its loop buffer and arena: a call waits for the work already queued on `stream` before
+ * it uploads its tables (once, before its first step); use one stream at a time per net. */
+int dm_f32_unet_forward_inject(dm_f32_net* e, const void* sample_dev, const int64_t* t_dev, const int32_t* slot_dev, int batch, int h, int w,
+                               int conv_mask, int attn_mask, void* out_dev, void* stream);
+int dm_f32_ddim_run(dm_f32_net* e, void* x_dev, const int64_t* t_host, const float* coef_host, const int32_t* slot_dev,
+                    const int32_t* save_row_host, void* traj_dev, int B, int h, int w, int n_steps, void* stream);
+int dm_f32_pnp_run(dm_f32_net* e, void* x_dev, const void* src_dev, const int64_t* t_host, const float* coef_host, const uint8_t* conv_on_host,
+                   const uint8_t* attn_on_host, int conv_mask, int attn_mask, const int32_t* slot_dev, int B, int h, int w, int n_steps,
+                   float guidance_scale, void* stream);
 /* optional CLIP ViT-L/14 text tower in fp32: `pipe.encode_prompt(prompt, ...)[0]` of the featuriser (dift.py:222-226) — its pipeline is built
  * with no torch_dtype (dift.py:197-199), so `text_encoder(input_ids)[0]` is fp32 there; replaces transformers' CLIPTextModel.forward for that
  * call (12 layers, causal attention over 77 tokens, quick-GELU, final LayerNorm; fp32 GEMMs on the fp32 matrix cores).  State-dict names as
@@ -875,6 +908,16 @@ int dm_f32_op_groupnorm(void* stream, const void* X, const void* X2, int N, int 
 int dm_f32_op_layernorm(void* stream, const void* X, int rows, int C, const float* gamma, const float* beta, float eps, void* Y);
 /* the tower's patch-token head, first half: LayerNorm of rows 1 .. T-1 of every image (the CLS row skipped), X [n][T][C] -> Y [n*(T-1)][C] */
 int dm_f32_op_clip_patch_ln(void* stream, const void* X, int n, int T, int C, const float* gamma, const float* beta, float eps, void* Y);
+/* the generator's kernels one by one: the DDIM update out = c0 * ((x - c1 * eps) / c2) + c3 * eps on n elements, coef4 on the device, every
+ * operation rounded on its own (out may be x); its guided form with eps = eps_u + g * (eps_c - eps_u); Y[b] = R[b] + Hs for B samples of `per`
+ * elements; the decoder's tail (X NHWC [B,H,W,128], stats [B*32][2] from dm_f32_op_groupnorm's stats_work, Wp [3][9*128]) */
+int dm_f32_op_ddim_step(void* stream, const void* x, const void* eps, const float* coef4, int64_t n, void* out);
+int dm_f32_op_ddim_step_cfg(void* stream, const void* x, const void* eps_u, const void* eps_c, float g, const float* coef4, int64_t n, void* out);
+int dm_f32_op_bcast_add(void* stream, const void* R, const void* Hs, int B, int64_t per, void* Y);
+int dm_f32_op_decoder_tail(void* stream, const void* X, const void* stats, const float* gamma, const float* beta, const void* Wp, const float* bias,
+                           int B, int H, int W, int C, int raw, void* out_f32, void* out_u8);
+/* the two-kernel tail's convolution: X NHWC [B,H,W,C] (already normalised), Wp [Cout <= 8][9 C], Y NCHW [B,Cout,H,W] */
+int dm_f32_op_conv_out(void* stream, const void* X, const void* Wp, const float* bias, int B, int H, int W, int C, int Cout, void* Y);
 
 #ifdef __cplusplus
 }
