@@ -157,9 +157,22 @@ int igemm_head_rows(const IGemmParams& p);       // rows [0, r) run on the 256 x
 // shapes the persistent 256 x 320 tile (igemm_pers_tile.h) takes; the others run on the 128-row tile of igemm_tile.h
 // (bit-identical results): >= 4 k steps, a time embedding only when every 256-row tile lies
 // inside one sample, never a time embedding and a residual together
+// Longest row of ONE k-loop source (C1, Cin - C1, C3 or Csc - C3 channels) the persistent tile takes.  Its halo lanes and rows
+// beyond M advance through the zero page one 64-channel step at a time like every other lane (no per-piece test in the k
+// step), so the zero page is as long as the longest such row: 2 * IGEMM_PERS_MAX_SRC_C bytes (igemm_pers_tile.h).
+constexpr int IGEMM_PERS_MAX_SRC_C = 16384;
+inline long long igemm_pers_src_row(const IGemmParams& p) {          // channels of the launch's longest single-source row
+    long long cmax = p.C1 > p.Cin - p.C1 ? p.C1 : p.Cin - p.C1;
+    if (p.X3) {
+        const long long c3 = p.C3 > p.Csc - p.C3 ? p.C3 : p.Csc - p.C3;
+        cmax = cmax > c3 ? cmax : c3;
+    }
+    return cmax;
+}
 inline bool igemm_pers_ok(const IGemmParams& p) {
     const int nk = ((p.mode == IG_DENSE) ? 1 : 9) * (p.Cin / 64);
     if (nk < 4 || p.Cout % 320 != 0 || p.M < 2) return false;
+    if (igemm_pers_src_row(p) > IGEMM_PERS_MAX_SRC_C) return false;
     {   // the kernel keeps activation element offsets (row * channels + chunk) in 32 bits: larger tensors take the 128-row tile
         long long cmax = p.C1 > p.Cin - p.C1 ? p.C1 : p.Cin - p.C1;
         if (p.X3) {                          // the folded shortcut's sources (third / fourth k-loop source) use the same 32-bit offsets

@@ -60,6 +60,8 @@ int dm_op_igemm_tile(int M, int Cin, int Cout, int mode) {
     return igemm_tile_choice(p);
 }
 
+int dm_op_igemm_pers_max_source_channels(void) { return IGEMM_PERS_MAX_SRC_C; }
+
 int dm_op_igemm_head_rows(int M, int spatial, int Cin, int Cout, int mode) {
     IGemmParams p{};
     p.M = M; p.Cin = Cin; p.C1 = Cin; p.Cout = Cout; p.mode = mode; p.epi = EPI_PLAIN;

@@ -37,7 +37,10 @@ namespace {
 #endif
 constexpr int TILE_SWZ_G = DM_TILE_SWZ;       // pixel tiles per group of the wide layers' tile order (0 = channel-minor everywhere)
 
-__device__ __attribute__((aligned(256))) unsigned char g_zero_page_pers[1024];
+// Source of the halo / out-of-range LDS-DMA lanes.  Such a lane starts at its 16-byte chunk of the page and advances 128 bytes per k
+// step like the lanes that read the tensor (igemm_pers_kernel: load_piece), so the page covers the longest single-source row a
+// launch can have (launch_pers checks it); vector-slot and tap-reuse users only read its first KiB.
+__device__ __attribute__((aligned(256))) unsigned char g_zero_page_pers[2 * IGEMM_PERS_MAX_SRC_C];
 __device__ __attribute__((aligned(256))) unsigned char g_store_sink[8 * 64 * 16];      // one 16-byte slot per (wave, lane)
 // Dynamic tile hand-out: one counter per XCD (its blocks share an L2, so an XCD keeps its contiguous tile range) +
 // one completion counter; the last block to finish resets them, so a launch finds and leaves them at zero.  Static
@@ -399,9 +402,20 @@ void igemm_pers_kernel(IGemmParams p, int ntiles, int cset) {
     // (kept minimal: the k loop runs at 256 registers; the pixel coordinates of a lane's rows are re-derived from the
     // row index at every tap change instead of being held)
     int lp0 = 0, lc0 = 0;
-    int xpk[XI], xoff[XI];            // xpk: sample << 18 | oh << 9 | ow of this lane's activation rows, -1 beyond M (n < 8192, oh / ow < 512)
-    unsigned woff = 0;
-    const unsigned wstride = (unsigned)(NW * 8) * (unsigned)Ktot;
+    int xpk[XI];                      // sample << 18 | oh << 9 | ow of this lane's activation rows, -1 beyond M (n < 8192, oh / ow < 512)
+    // LDS-DMA sources.  Weights: one wave-uniform byte address (piece 0's eight rows at the stream's k position, advanced by scalar
+    // adds) + this lane's constant 32-bit offset — the SGPR-base form of global_load_lds, no vector instruction per piece.
+    // Activations: a 64-bit lane address per piece, set at a tap / source change and advanced by ONE v_lshl_add_u64 per piece and
+    // step; halo lanes and rows beyond M walk the zero page the same way (no test, no select).
+    const char* wbase = reinterpret_cast<const char*>(p.Wp);
+    unsigned wlane = 0;
+    const size_t wstride = (size_t)(NW * 8) * (size_t)Ktot * sizeof(f16);
+    // LEAN_X = false (the residual instantiations: their epilogue holds the residual rows, and four more registers across the k loop
+    // are four more spilled): the earlier form — a 32-bit element offset per piece (-1: zero page), widened onto xbase, selected and
+    // advanced under a test in every step.
+    constexpr bool LEAN_X = (EXTRA != PX_RES);
+    const char* xaddr[LEAN_X ? XI : 1];
+    int xoff[LEAN_X ? 1 : XI];
     const f16* xbase = p.X;
     int ld_tap = 0, ld_cc = 0;
     int ld_ph = 0;                    // UP4: output parity class (py << 1 | px) of the tile being fetched
@@ -449,9 +463,11 @@ void igemm_pers_kernel(IGemmParams p, int ntiles, int cset) {
         lc0 = ct * TC;
         const int ln = hw_lane();
         const int lrow = ln >> 3, lchunk = ((ln & 7) ^ lrow) * 8;
-        woff = (unsigned)((size_t)(lc0 + wid * 8 + lrow) * Ktot + lchunk) + (unsigned)(tap0 * p.Cin);
-        if constexpr (WS) woff += (unsigned)((long long)(lp0 / p.rows_per_sample) * p.w_sample_stride);
-        if constexpr (UP4) woff += (unsigned)ld_ph * (unsigned)p.Cout * (unsigned)Ktot;
+        long long wrow0 = (long long)(lc0 + wid * 8) * Ktot + tap0 * p.Cin;             // wave-uniform, in elements
+        if constexpr (WS) wrow0 += (long long)(lp0 / p.rows_per_sample) * p.w_sample_stride;
+        if constexpr (UP4) wrow0 += (long long)ld_ph * p.Cout * Ktot;
+        wbase = reinterpret_cast<const char*>(p.Wp + wrow0);
+        wlane = (unsigned)(lrow * Ktot + lchunk) * (unsigned)sizeof(f16);
         ld_tap = tap0; ld_cc = 0;
 #pragma unroll
         for (int k = 0; k < XI; ++k) xpk[k] = pack_row(lp0 + (wid + k * NW) * 8 + lrow);
@@ -482,41 +498,52 @@ void igemm_pers_kernel(IGemmParams p, int ntiles, int cset) {
         }
         return xnb + ih * p.W + iw;
     };
-    auto set_src = [&](int tap, int cs) __attribute__((always_inline)) {
+    auto set_src = [&](const f16* src, int tap, int cs) __attribute__((always_inline)) {
         const int dy = UP4 ? tap >> 1 : tap / 3, dx = UP4 ? tap & 1 : tap - dy * 3;
         const int lchunk = lds_chunk(hw_lane());
 #pragma unroll
         for (int k = 0; k < XI; ++k) {
             const int pix = src_pixel(k, dy, dx);
-            xoff[k] = (pix >= 0) ? (pix * cs + lchunk) : -1;
+            if constexpr (LEAN_X)
+                xaddr[LEAN_X ? k : 0] = reinterpret_cast<const char*>((pix >= 0) ? src + (size_t)(unsigned)(pix * cs + lchunk)
+                                                                                 : reinterpret_cast<const f16*>(p.zero_page) + lchunk);
+            else xoff[LEAN_X ? 0 : k] = (pix >= 0) ? (pix * cs + lchunk) : -1;
         }
+        if constexpr (!LEAN_X) xbase = src;
     };
     auto prepare = [&]() __attribute__((always_inline)) {    // sources of the next k tile to load
         if constexpr (SC) {
             if (ld_tap == ntaps) {                           // the folded second GEMM: centre tap (dense: the row itself) on cat([X3, X4])
                 const int ctap = (p.mode == IG_DENSE) ? 0 : 4;
-                if (ld_cc == 0) { xbase = p.X3; set_src(ctap, p.C3); }
-                else if (ld_cc * BK == p.C3) { xbase = p.X4; set_src(ctap, p.Csc - p.C3); }
+                if (ld_cc == 0) set_src(p.X3, ctap, p.C3);
+                else if (ld_cc * BK == p.C3) set_src(p.X4, ctap, p.Csc - p.C3);
                 if (++ld_cc == cpt_sc) { ld_cc = 0; ++ld_tap; }
                 return;
             }
         }
-        if (ld_cc == 0) { xbase = p.X; set_src(ld_tap, C1); }
-        else if (ld_cc * BK == C1) { xbase = p.X2; set_src(ld_tap, C2); }
+        if (ld_cc == 0) set_src(p.X, ld_tap, C1);
+        else if (ld_cc * BK == C1) set_src(p.X2, ld_tap, C2);
         if (++ld_cc == cpt) { ld_cc = 0; ++ld_tap; }
     };
-    auto load_piece = [&](int buf, int idx, int lchunk) __attribute__((always_inline)) {   // idx in [0, NL): W pieces, then X
+    auto load_piece = [&](int buf, int idx, int lchunk) __attribute__((always_inline)) {   // idx in [0, NL): W pieces, then X (lchunk: !LEAN_X only)
         char* wt = smem + buf * STAGE;
+        constexpr int KSTEP = BK * (int)sizeof(f16);                               // bytes a source advances per k step
         if (idx < WI) {
             lptr_t dst = (lptr_t)(wt + (wid + idx * NW) * 1024);
-            __builtin_amdgcn_global_load_lds((gptr_t)(p.Wp + (size_t)(woff + (unsigned)idx * wstride)), dst, 16, 0, 0);
-            if (idx == WI - 1) woff += BK;
+            __builtin_amdgcn_global_load_lds((gptr_t)(wbase + (size_t)idx * wstride + (size_t)wlane), dst, 16, 0, 0);
+            if (idx == WI - 1) wbase += KSTEP;
         } else {
             const int k = idx - WI;
             lptr_t dst = (lptr_t)(wt + WBYTES + (wid + k * NW) * 1024);
-            const f16* a = (xoff[k] >= 0) ? (xbase + (size_t)(unsigned)xoff[k]) : reinterpret_cast<const f16*>(p.zero_page) + lchunk;
-            __builtin_amdgcn_global_load_lds((gptr_t)a, dst, 16, 0, 0);
-            if (xoff[k] >= 0) xoff[k] += BK;
+            if constexpr (LEAN_X) {
+                __builtin_amdgcn_global_load_lds((gptr_t)xaddr[LEAN_X ? k : 0], dst, 16, 0, 0);
+                xaddr[LEAN_X ? k : 0] += KSTEP;
+            } else {
+                int& xo = xoff[LEAN_X ? 0 : k];
+                const f16* a = (xo >= 0) ? (xbase + (size_t)(unsigned)xo) : reinterpret_cast<const f16*>(p.zero_page) + lchunk;
+                __builtin_amdgcn_global_load_lds((gptr_t)a, dst, 16, 0, 0);
+                if (xo >= 0) xo += BK;
+            }
         }
     };
     // per-tile vectors -> LDS slot by LDS-DMA (lane-linear 1 KiB pieces; lanes past the vector read the zero page)
@@ -564,7 +591,7 @@ void igemm_pers_kernel(IGemmParams p, int ntiles, int cset) {
         const int a_row_off = (wc * 80 * CH + l15) * 128;
         const int b_row_off = (wp * 64 + l15) * 128;
         const int koff0 = ((lg ^ (l15 & 7)) << 4), koff1 = (((4 + lg) ^ (l15 & 7)) << 4);
-        const int lchunk = lds_chunk(ln);
+        const int lchunk = LEAN_X ? 0 : lds_chunk(ln);
         half8 b0[4], b1[4], a[5];
 #pragma unroll
         for (int j = 0; j < 4; ++j) b0[j] = *reinterpret_cast<const half8*>(xt + b_row_off + j * 2048 + koff0);
@@ -631,7 +658,7 @@ void igemm_pers_kernel(IGemmParams p, int ntiles, int cset) {
     load_aux(0);
     prepare();
     {
-        const int lchunk = lds_chunk(hw_lane());
+        const int lchunk = LEAN_X ? 0 : lds_chunk(hw_lane());
 #pragma unroll
         for (int i = 0; i < NL; ++i) load_piece(0, i, lchunk);
     }
@@ -732,6 +759,7 @@ std::atomic<unsigned> g_launch_no{0};      // round robin over g_tile_ctr's sets
 // `units` tiles (or split-K units) on one block per CU, with this translation unit's zero page and its next counter set
 inline hipError_t launch_pers(pers_kernel_t kernel, size_t lds, int units, const IGemmParams& p, hipStream_t s) {
     IGemmParams q = p;
+    if (2 * igemm_pers_src_row(p) > (long long)sizeof(g_zero_page_pers)) return hipErrorInvalidValue;      // a halo lane would walk off the zero page
     const hipError_t r = zero_page_addr(&q.zero_page);
     if (r != hipSuccess) return r;
     const int n_cu = device_cu_count();

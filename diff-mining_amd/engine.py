@@ -84,6 +84,7 @@ SIGNATURES = {
     "dm_get_option": (_i32, [_cp, _pi32]),
     "dm_op_igemm_tile": (_i32, [_i32] * 4),
     "dm_op_igemm_head_rows": (_i32, [_i32] * 5),
+    "dm_op_igemm_pers_max_source_channels": (_i32, []),
     "dm_op_attention": (_i32, [_vp] * 5 + [_i32] * 4 + [_i64] * 4 + [_vp] + [_i32] * 5 + [_f32]),
     "dm_op_attention_slots": (_i32, [_vp] * 5 + [_i32] * 4 + [_i64] * 4 + [_vp] + [_i32] * 8 + [_f32]),
     "dm_op_attention_route": (_i32, [_i32] * 6),

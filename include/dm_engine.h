@@ -675,6 +675,9 @@ int dm_op_igemm_tile(int M, int Cin, int Cout, int mode);
 /* rows [0, r) of such a launch run on the persistent 256x320 tile (whole rounds over the CUs), rows [r, M) on the
  * 128-row tile ("igemm_tail"; r = 0 / M: one kernel for all rows).  `spatial` = OH*OW of one sample (ignored for mode 0). */
 int dm_op_igemm_head_rows(int M, int spatial, int Cin, int Cout, int mode);
+/* channels of the longest row of ONE k-loop source (C1, C2, C3 or C4) the persistent 256x320 tile takes: its zero page, which halo
+ * lanes walk at the pace of the tensor's lanes, is twice as many bytes; longer rows run on the 128-row tile */
+int dm_op_igemm_pers_max_source_channels(void);
 /* flash attention, head_dim 40 / 80 / 160: O[b] = softmax(scale Q[b] K[s]^T) V[s] per head, s = kv_slot[b] if kv_slot, else b */
 int dm_op_attention(void* stream, const void* Q, const void* K, const void* V, void* O, int ldq, int ldk, int ldv,
                     int ldo, int64_t bsq, int64_t bsk, int64_t bsv, int64_t bso, const int32_t* kv_slot,
