@@ -1,4 +1,8 @@
 // engine_ops.hip — operator-level entry points (dm_op_*): single launches for the parity tests, none of which takes an engine handle.
+// The matrix kernels first (igemm tiles, attention routes, norms, conv_out), then the glue kernels around them, one entry per launch_*:
+// dm_op_time_gather, dm_op_silu, dm_op_im2col_in, dm_op_nhwc_to_nchw, dm_op_ensemble_mean (misc.hip), dm_op_im2col_rgb, dm_op_posterior
+// (vae.hip), dm_op_clip_embed, dm_op_clip_attention, dm_op_quick_gelu, dm_op_f16_to_f32 (clip.hip).  Their fp32 counterparts are the
+// dm_f32_op_* of unet_f32.hip.
 #include "../../include/dm_engine.h"
 #include "dm_kernels.h"
 
@@ -192,6 +196,69 @@ int dm_op_groupnorm_conv1x1(void* stream, const void* X, int N, int HW, int C, i
 int dm_op_layernorm(void* stream, const void* X, int rows, int C, const float* gamma, const float* beta, float eps,
                     void* Y) {
     return launch_layernorm((const f16*)X, rows, C, gamma, beta, eps, (f16*)Y, (hipStream_t)stream) == hipSuccess ? 0 : 1;
+}
+
+// ---- the glue kernels one by one (tests/test_gpu_glue.py): each entry wraps ONE launch_* and adds no arithmetic.  A null required pointer, a
+// non-positive extent or a violated precondition of the kernel returns 1 before anything is launched.
+int dm_op_time_gather(void* stream, const void* table, const int64_t* t, int B, int dim, void* out) {
+    if (!table || !t || !out || B <= 0 || dim <= 0 || (long long)B * dim > 0x7fffffffLL - 255) return 1;
+    return launch_time_gather((const f16*)table, t, B, dim, (f16*)out, (hipStream_t)stream) == hipSuccess ? 0 : 1;
+}
+
+int dm_op_silu(void* stream, const void* in, void* out, int64_t n) {
+    if (!in || !out || n <= 0) return 1;
+    return launch_silu((const f16*)in, (f16*)out, (long long)n, (hipStream_t)stream) == hipSuccess ? 0 : 1;
+}
+
+int dm_op_im2col_in(void* stream, const void* x, const int32_t* x_index, const void* eps, const int64_t* t, const void* sa, const void* sb,
+                    int latent_f32, int B, int H, int W, void* out) {
+    if (!x || !out || B <= 0 || H <= 0 || W <= 0 || (long long)H * W > 0x7fffffffLL) return 1;
+    if ((sa == nullptr) != (sb == nullptr)) return 1;
+    if (sa && (!eps || !t)) return 1;
+    return launch_im2col_in(x, x_index, eps, t, sa, sb, latent_f32 ? 1 : 0, B, H, W, (f16*)out, (hipStream_t)stream) == hipSuccess ? 0 : 1;
+}
+
+int dm_op_nhwc_to_nchw(void* stream, const void* X, int N, int HW, int C, void* Y) {
+    if (!X || !Y || N <= 0 || HW <= 0 || C <= 0 || N > 65535 || (C + 31) / 32 > 65535) return 1;
+    return launch_nhwc_to_nchw((const f16*)X, N, HW, C, (f16*)Y, (hipStream_t)stream) == hipSuccess ? 0 : 1;
+}
+
+int dm_op_ensemble_mean(void* stream, const void* X, int groups, int ens, int HW, int C, float* Y) {
+    if (!X || !Y || groups <= 0 || ens < 1 || HW <= 0 || C <= 0 || groups > 65535 || (C + 31) / 32 > 65535) return 1;
+    return launch_ensemble_mean((const f16*)X, groups, ens, HW, C, Y, (hipStream_t)stream) == hipSuccess ? 0 : 1;
+}
+
+int dm_op_im2col_rgb(void* stream, const void* x, int B, int H, int W, void* out) {
+    if (!x || !out || B <= 0 || H <= 0 || W <= 0 || (long long)H * W > 0x7fffffffLL) return 1;
+    return launch_im2col_rgb((const f16*)x, B, H, W, (f16*)out, (hipStream_t)stream) == hipSuccess ? 0 : 1;
+}
+
+int dm_op_posterior(void* stream, const void* Hm, int ldh, const void* qw, const void* qb, const void* noise, int B, int draws, int HW,
+                    float scaling, void* latent16, float* latent32, float* moments) {
+    if (!Hm || !qw || !qb || B <= 0 || HW <= 0 || draws < 1 || ldh < 8 || ldh % 8) return 1;
+    if (!latent16 && !latent32 && !moments) return 1;
+    return launch_posterior((const f16*)Hm, ldh, (const f16*)qw, (const f16*)qb, (const f16*)noise, B, draws, HW, scaling, (f16*)latent16,
+                            latent32, moments, (hipStream_t)stream) == hipSuccess ? 0 : 1;
+}
+
+int dm_op_clip_embed(void* stream, const int32_t* ids, const void* tok, const void* pos, int rows, int T, int C, int vocab, void* out) {
+    if (!ids || !tok || !pos || !out || rows <= 0 || T < 1 || C <= 0 || C % 8 || vocab < 1) return 1;
+    return launch_clip_embed(ids, (const f16*)tok, (const f16*)pos, rows, T, C, vocab, (f16*)out, (hipStream_t)stream) == hipSuccess ? 0 : 1;
+}
+
+int dm_op_clip_attention(void* stream, const void* qkv, int n, int T, int heads, void* out) {
+    if (!qkv || !out || n <= 0 || n > 65535 || T <= 0 || heads < 1) return 1;
+    return launch_clip_attention((const f16*)qkv, n, T, heads, (f16*)out, (hipStream_t)stream) == hipSuccess ? 0 : 1;      // T > 80: refused there
+}
+
+int dm_op_quick_gelu(void* stream, void* x, int64_t n) {
+    if (!x || n <= 0) return 1;
+    return launch_quick_gelu((f16*)x, (long long)n, (hipStream_t)stream) == hipSuccess ? 0 : 1;                            // n % 8: refused there
+}
+
+int dm_op_f16_to_f32(void* stream, const void* x, float* y, int64_t n) {
+    if (!x || !y || n <= 0) return 1;
+    return launch_f16_to_f32((const f16*)x, y, (long long)n, (hipStream_t)stream) == hipSuccess ? 0 : 1;
 }
 
 }  // extern "C"

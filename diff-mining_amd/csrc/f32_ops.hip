@@ -324,18 +324,40 @@ __global__ __launch_bounds__(clip_attn_threads(T)) void clip32_attn_kernel(const
     for (int d = 0; d < CLD; ++d) dst[d] = o[d];
 }
 
-__global__ void quick_gelu32_kernel(float* x, long long n) {          // y * sigmoid(1.702 y)
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        const float y = x[i];
-        x[i] = y / (1.0f + expf(-1.702f * y));
+// y * sigmoid(1.702 y) = y / (1 + exp(-1.702 y)) to a few fp32 roundings over the whole range.  The fp32 product a = 1.702f * y is off by up to
+// 2^-24 |a| (and 1.702f is not 1.702), and exp() turns that into a RELATIVE error of the same size: 50 roundings at a = -50, where the result is
+// y e^a.  lo = what the product's rounding and the constant dropped; exp(-(a + lo)) = exp(-a) (1 - lo), lo^2 < 1e-10.  Below a = -80 exp(-a)
+// heads for its overflow at 88.7 although the result stays a normal number down to a = -91: there 1 + e^a == 1 and the result is y e^a, with
+// e^a as a square so that no factor is denormal.
+__device__ __forceinline__ float quick_gelu32(float y) {
+    constexpr float C = 1.702f, C_LO = (float)(1.702 - (double)1.702f);
+    const float a = C * y;
+    float lo = fmaf(C, y, -a) + C_LO * y;
+    lo = fabsf(a) < 3.0e38f ? lo : 0.f;                  // y = +-inf: inf - inf above
+    if (a < -80.f) {
+        const float h = expf(0.5f * a);
+        const float t = y * h * h;
+        return fmaf(lo, t, t);
     }
+    const float e = expf(-a);
+    return y / (1.0f + fmaf(-lo, e, e));
+}
+
+// v / (1 + exp(-v)); below -80 as v e^v (1 + e^v == 1), e^v as a square: exp(-v) overflows at v = -88.7, where v e^v = -2.6e-37 is still a normal number
+__device__ __forceinline__ float silu32(float v) {
+    if (v < -80.f) {
+        const float h = expf(0.5f * v);
+        return v * h * h;
+    }
+    return v / (1.0f + expf(-v));
+}
+
+__global__ void quick_gelu32_kernel(float* x, long long n) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) x[i] = quick_gelu32(x[i]);
 }
 
 __global__ void silu32_kernel(const float* in, float* out, long long n) {
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        const float v = in[i];
-        out[i] = v / (1.0f + expf(-v));
-    }
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) out[i] = silu32(in[i]);
 }
 
 __global__ void temb32_kernel(const int64_t* t, int B, int dim, float* out) {

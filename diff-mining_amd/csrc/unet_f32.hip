@@ -1735,4 +1735,64 @@ int dm_f32_op_clip_patch_ln(void* stream, const void* X, int n, int T, int C, co
     return launch_clip_tower_patch_ln((const float*)X, n, T, C, gamma, beta, eps, (float*)Y, (hipStream_t)stream) == hipSuccess ? 0 : 1;
 }
 
+/* the glue kernels of f32_ops.hip one by one (tests/test_gpu_glue.py): one launch each, no arithmetic of their own; a null required pointer, a
+ * non-positive extent or a violated precondition of the kernel returns 1 before anything is launched */
+int dm_f32_op_clip_embed(void* stream, const int32_t* ids, const void* tok, const void* pos, int rows, int T, int C, int vocab, void* out) {
+    if (!ids || !tok || !pos || !out || rows <= 0 || T < 1 || C <= 0 || vocab < 1) return 1;
+    return launch_clip_embed(ids, (const float*)tok, (const float*)pos, rows, T, C, vocab, (float*)out, (hipStream_t)stream) == hipSuccess ? 0 : 1;
+}
+
+int dm_f32_op_clip_attention(void* stream, const void* qkv, int n, int T, int heads, int causal, void* out) {
+    if (!qkv || !out || n <= 0 || heads < 1 || heads > 65535) return 1;
+    return launch_clip_attention((const float*)qkv, n, T, heads, causal != 0, (float*)out, (hipStream_t)stream) == hipSuccess ? 0 : 1;   // (T, causal): refused there
+}
+
+int dm_f32_op_quick_gelu(void* stream, void* x, int64_t n) {
+    if (!x || n <= 0) return 1;
+    return launch_quick_gelu((float*)x, (long long)n, (hipStream_t)stream) == hipSuccess ? 0 : 1;
+}
+
+int dm_f32_op_silu(void* stream, const void* in, void* out, int64_t n) {
+    if (!in || !out || n <= 0) return 1;
+    return launch_silu((const float*)in, (float*)out, (long long)n, (hipStream_t)stream) == hipSuccess ? 0 : 1;
+}
+
+int dm_f32_op_timestep_embed(void* stream, const int64_t* t, int B, int dim, void* out) {
+    if (!t || !out || B <= 0 || dim < 2 || dim % 2 || (long long)B * (dim / 2) > 0x7fffffffLL - 255) return 1;
+    return launch_timestep_embed(t, B, dim, (float*)out, (hipStream_t)stream) == hipSuccess ? 0 : 1;
+}
+
+int dm_f32_op_conv_in(void* stream, const void* x, const void* w, const float* bias, int B, int Cin, int H, int W, int Cout, void* y) {
+    if (!x || !w || !bias || !y || B <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0) return 1;
+    return launch_conv_in((const float*)x, (const float*)w, bias, B, Cin, H, W, Cout, (float*)y, (hipStream_t)stream) == hipSuccess ? 0 : 1;
+}
+
+int dm_f32_op_add_noise(void* stream, const void* x, const int32_t* x_index, const void* eps, const int64_t* t, const float* sa, const float* sb, int B,
+                        int64_t per, void* out) {
+    if (!x || !eps || !t || !sa || !sb || !out || B <= 0 || per <= 0) return 1;
+    return launch_add_noise((const float*)x, x_index, (const float*)eps, t, sa, sb, B, (long long)per, (float*)out, (hipStream_t)stream) == hipSuccess ? 0 : 1;
+}
+
+int dm_f32_op_sqerr(void* stream, const void* pred, const void* eps, int64_t n, void* out) {
+    if (!pred || !eps || !out || n <= 0) return 1;
+    return launch_sqerr((const float*)pred, (const float*)eps, (long long)n, (float*)out, (hipStream_t)stream) == hipSuccess ? 0 : 1;
+}
+
+int dm_f32_op_nhwc_to_nchw(void* stream, const void* X, int N, int HW, int C, void* Y) {
+    if (!X || !Y || N <= 0 || HW <= 0 || C <= 0) return 1;
+    return launch_nhwc_to_nchw((const float*)X, N, HW, C, (float*)Y, (hipStream_t)stream) == hipSuccess ? 0 : 1;
+}
+
+int dm_f32_op_ensemble_mean(void* stream, const void* X, int groups, int ens, int HW, int C, void* Y) {
+    if (!X || !Y || groups <= 0 || ens < 1 || HW <= 0 || C <= 0) return 1;
+    return launch_ensemble_mean((const float*)X, groups, ens, HW, C, (float*)Y, (hipStream_t)stream) == hipSuccess ? 0 : 1;
+}
+
+int dm_f32_op_posterior(void* stream, const void* Hm, const void* qw, const void* qb, const void* noise, int B, int draws, int HW, float scaling,
+                        void* latent, void* moments) {
+    if (!Hm || !qw || !qb || B <= 0 || draws < 1 || HW <= 0 || (!latent && !moments)) return 1;
+    return launch_posterior((const float*)Hm, (const float*)qw, (const float*)qb, (const float*)noise, B, draws, HW, scaling, (float*)latent,
+                            (float*)moments, (hipStream_t)stream) == hipSuccess ? 0 : 1;
+}
+
 }  // extern "C"

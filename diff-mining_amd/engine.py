@@ -102,6 +102,17 @@ SIGNATURES = {
     "dm_op_fold_upconv_weights": (_i32, [_vp, _i32, _i32, _vp]),
     "dm_op_upconv_folded": (_i32, [_vp] * 5 + [_i32] * 5),
     "dm_op_groupnorm_conv1x1": (_i32, [_vp, _vp] + [_i32] * 4 + [_f32] + [_vp] * 4 + [_i32, _vp]),
+    "dm_op_time_gather": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp]),
+    "dm_op_silu": (_i32, [_vp, _vp, _vp, _i64]),
+    "dm_op_im2col_in": (_i32, [_vp] * 7 + [_i32] * 4 + [_vp]),
+    "dm_op_nhwc_to_nchw": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp]),
+    "dm_op_ensemble_mean": (_i32, [_vp, _vp] + [_i32] * 4 + [_vp]),
+    "dm_op_im2col_rgb": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp]),
+    "dm_op_posterior": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp]),
+    "dm_op_clip_embed": (_i32, [_vp] * 4 + [_i32] * 4 + [_vp]),
+    "dm_op_clip_attention": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp]),
+    "dm_op_quick_gelu": (_i32, [_vp, _vp, _i64]),
+    "dm_op_f16_to_f32": (_i32, [_vp, _vp, _vp, _i64]),
     "dm_f32_create": (_i32, [_i32, _pvp]),
     "dm_f32_destroy": (None, [_vp]),
     "dm_f32_last_error": (_cp, [_vp]),
@@ -148,6 +159,17 @@ SIGNATURES = {
     "dm_f32_op_bcast_add": (_i32, [_vp, _vp, _vp, _i32, _i64, _vp]),
     "dm_f32_op_decoder_tail": (_i32, [_vp] * 7 + [_i32] * 5 + [_vp, _vp]),
     "dm_f32_op_conv_out": (_i32, [_vp] * 4 + [_i32] * 5 + [_vp]),
+    "dm_f32_op_clip_embed": (_i32, [_vp] * 4 + [_i32] * 4 + [_vp]),
+    "dm_f32_op_clip_attention": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "dm_f32_op_quick_gelu": (_i32, [_vp, _vp, _i64]),
+    "dm_f32_op_silu": (_i32, [_vp, _vp, _vp, _i64]),
+    "dm_f32_op_timestep_embed": (_i32, [_vp, _vp, _i32, _i32, _vp]),
+    "dm_f32_op_conv_in": (_i32, [_vp] * 4 + [_i32] * 5 + [_vp]),
+    "dm_f32_op_add_noise": (_i32, [_vp] * 7 + [_i32, _i64, _vp]),
+    "dm_f32_op_sqerr": (_i32, [_vp, _vp, _vp, _i64, _vp]),
+    "dm_f32_op_nhwc_to_nchw": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp]),
+    "dm_f32_op_ensemble_mean": (_i32, [_vp, _vp] + [_i32] * 4 + [_vp]),
+    "dm_f32_op_posterior": (_i32, [_vp] * 5 + [_i32] * 3 + [_f32, _vp, _vp]),
 }
 SYMBOLS = list(SIGNATURES)
 

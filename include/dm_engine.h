@@ -744,6 +744,38 @@ int dm_op_upconv_folded(void* stream, const void* X, const void* W4, const void*
  * the raw X — Y [N][HW][Cout] fp16.  HW must be a multiple of 128, C of 64, Cout of 160. */
 int dm_op_groupnorm_conv1x1(void* stream, const void* X, int N, int HW, int C, int G, float eps, const float* gamma,
                             const float* beta, const void* W, const void* bias, int Cout, void* Y);
+/* The glue kernels around the matrix kernels, one launch each (fp16 tensors unless a float pointer says otherwise).  Every entry returns 1
+ * WITHOUT launching for a null required pointer, a non-positive extent or the precondition named with it.
+ *   time_gather    out [B][dim] = table [1000][dim] rows clamp(t[b], 0, 999), t int64
+ *   silu           out[i] = x / (1 + exp(-x)), n elements
+ *   im2col_in      scheduler.add_noise fused into conv_in's im2col: out [B*H*W][64], column c*9 + ky*3 + kx (< 36) = the zero-padded 3x3
+ *                  patch of noisy = sa[t[b]] * x[x_index ? x_index[b] : b] + sb[t[b]] * eps[b] (x, eps NCHW [.,4,H,W], t clamped to
+ *                  [0, 999]), columns 36..63 zero.  latent_f32 = 1: x / eps / sa / sb fp32, three fp32 roundings, then fp16 once; 0: all fp16,
+ *                  every operation rounded to fp16.  sa = sb = NULL: the plain sample (eps, t unused).  Refused: exactly one of sa / sb
+ *                  NULL; tables without eps or t
+ *   nhwc_to_nchw   X [N][HW][C] -> Y [N][C][HW]; N <= 65535
+ *   ensemble_mean  X [groups*ens][HW][C] fp16 -> Y [groups][C][HW] fp32, the mean over `ens` consecutive samples; ens >= 1, groups <= 65535
+ *   im2col_rgb     x NCHW [B,3,H,W] -> out [B*H*W][64], column c*9 + ky*3 + kx (< 27), columns 27..63 zero
+ *   posterior      quant_conv (qw [8][8], qb [8]) on the first 8 of the ldh channels of Hm [B*HW][ldh], rounded to fp16 = moments [B,8,HW]
+ *                  (fp32 values, optional); latent32 / latent16 [B*draws,4,HW] = (mean + exp(0.5 clamp(logvar, -30, 20)) * noise) * scaling
+ *                  with sample b*draws + d on image b's moments (noise NULL: the mode); ldh % 8 == 0, ldh >= 8, draws >= 1, an output
+ *   clip_embed     out [rows][C] = tok [vocab][C] row clamp(ids[r], 0, vocab - 1) + pos [T][C] row r % T (one fp16 add); C % 8 == 0
+ *   clip_attention causal self-attention on qkv [n*T][3*heads*64] (q pre-scaled) -> out [n*T][heads*64]; 1 <= T <= 80, heads >= 1
+ *   quick_gelu     x * sigmoid(1.702 x) in place; n % 8 == 0
+ *   f16_to_f32     y[i] = (float)x[i] */
+int dm_op_time_gather(void* stream, const void* table, const int64_t* t, int B, int dim, void* out);
+int dm_op_silu(void* stream, const void* in, void* out, int64_t n);
+int dm_op_im2col_in(void* stream, const void* x, const int32_t* x_index, const void* eps, const int64_t* t, const void* sa, const void* sb,
+                    int latent_f32, int B, int H, int W, void* out);
+int dm_op_nhwc_to_nchw(void* stream, const void* X, int N, int HW, int C, void* Y);
+int dm_op_ensemble_mean(void* stream, const void* X, int groups, int ens, int HW, int C, float* Y);
+int dm_op_im2col_rgb(void* stream, const void* x, int B, int H, int W, void* out);
+int dm_op_posterior(void* stream, const void* Hm, int ldh, const void* qw, const void* qb, const void* noise, int B, int draws, int HW,
+                    float scaling, void* latent16, float* latent32, float* moments);
+int dm_op_clip_embed(void* stream, const int32_t* ids, const void* tok, const void* pos, int rows, int T, int C, int vocab, void* out);
+int dm_op_clip_attention(void* stream, const void* qkv, int n, int T, int heads, void* out);
+int dm_op_quick_gelu(void* stream, void* x, int64_t n);
+int dm_op_f16_to_f32(void* stream, const void* x, float* y, int64_t n);
 
 /* ---- fp32 U-Net: the arithmetic of the reference's DIFT featuriser ------------------------------------------------------
  * `SDFeaturizer.__init__` (diffmining/typicality/dift.py:197-199) loads the pipeline WITHOUT torch_dtype and `forward`
@@ -921,6 +953,27 @@ int dm_f32_op_decoder_tail(void* stream, const void* X, const void* stats, const
                            int B, int H, int W, int C, int raw, void* out_f32, void* out_u8);
 /* the two-kernel tail's convolution: X NHWC [B,H,W,C] (already normalised), Wp [Cout <= 8][9 C], Y NCHW [B,Cout,H,W] */
 int dm_f32_op_conv_out(void* stream, const void* X, const void* Wp, const float* bias, int B, int H, int W, int C, int Cout, void* Y);
+/* The fp32 net's glue kernels, one launch each, all tensors fp32; refusals as for the dm_op_* glue entries above.
+ *   clip_embed / quick_gelu (in place) / silu / nhwc_to_nchw / ensemble_mean: as their fp16 namesakes (no C % 8 or n % 8 condition)
+ *   clip_attention  heads of 64 on qkv [n*T][3*heads*64], q scaled by 1/8 inside: (T, causal) = (77, 1) or (50, 0), nothing else
+ *   timestep_embed  out [B][dim] = [cos(t f_j) | sin(t f_j)], f_j = exp(-ln(10000) j / (dim/2)); dim even
+ *   conv_in         x NCHW [B,Cin,H,W] (x) 3x3 pad 1 -> y NHWC [B,H,W,Cout]; w [(ci*3+dy)*3+dx][Cout], bias [Cout]
+ *   add_noise       out[b] = sa[t[b]] * x[x_index ? x_index[b] : b] + sb[t[b]] * eps[b], `per` elements per sample, t clamped to [0, 999]
+ *   sqerr           out = (pred - eps)^2
+ *   posterior       Hm [B*HW][8]: moments [B,8,HW] and / or latent [B*draws,4,HW], as dm_op_posterior without the fp16 rounding */
+int dm_f32_op_clip_embed(void* stream, const int32_t* ids, const void* tok, const void* pos, int rows, int T, int C, int vocab, void* out);
+int dm_f32_op_clip_attention(void* stream, const void* qkv, int n, int T, int heads, int causal, void* out);
+int dm_f32_op_quick_gelu(void* stream, void* x, int64_t n);
+int dm_f32_op_silu(void* stream, const void* in, void* out, int64_t n);
+int dm_f32_op_timestep_embed(void* stream, const int64_t* t, int B, int dim, void* out);
+int dm_f32_op_conv_in(void* stream, const void* x, const void* w, const float* bias, int B, int Cin, int H, int W, int Cout, void* y);
+int dm_f32_op_add_noise(void* stream, const void* x, const int32_t* x_index, const void* eps, const int64_t* t, const float* sa, const float* sb,
+                        int B, int64_t per, void* out);
+int dm_f32_op_sqerr(void* stream, const void* pred, const void* eps, int64_t n, void* out);
+int dm_f32_op_nhwc_to_nchw(void* stream, const void* X, int N, int HW, int C, void* Y);
+int dm_f32_op_ensemble_mean(void* stream, const void* X, int groups, int ens, int HW, int C, void* Y);
+int dm_f32_op_posterior(void* stream, const void* Hm, const void* qw, const void* qb, const void* noise, int B, int draws, int HW, float scaling,
+                        void* latent, void* moments);
 
 #ifdef __cplusplus
 }
