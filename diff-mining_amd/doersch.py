@@ -64,7 +64,32 @@ dozen steps, 6 - 35 % (rel-L2) short of the optimum.  The rules, which `svm_fit_
             than 128 detectors; a feature count below 8, above 8192 (the score pass stages w in 64 KB of LDS) or not a multiple of 8;
             n >= 2^24.
 
-Not here: `accept_patch_neighbor`, `filter_by_contrast`, the plots.
+Before the first SVM round the baseline initialises its detectors (`initialize_classifier`, doersch/doersch.py:387-400): it samples
+25 000 candidate patches (`init_patches`, :248-276; here `sample_patches`), turns every candidate into a detector and searches the
+whole data set with all of them (`init_detectors`, :317-369; here `CandidateSearch`, `init_detectors`, `init_detectors_images`), and
+greedily keeps the 1000 best whose neighbour lists do not overlap an accepted one's (`rank_init_detectors` / `accept_patch_neighbor`,
+:371-385 and :46-64; here `rank_init_detectors`).  Kernels: csrc/dense_search_wide.hip; C ABI: dm_dense_wide_workspace_bytes /
+_winners / _topk, dm_detector_rank_workspace_bytes / dm_detector_rank.  The wide search obeys the search rules above
+with 1 <= K <= 32768, and its tables are bit-equal to the narrow search's over blocks of 128 detectors.  The ranking's rules, which
+`rank_init_detectors_host` (plain Python) and the kernel share:
+
+  order     candidates are taken by descending key (the discriminative-20 count; any int32), among equal keys by ascending index:
+            Python's stable `sorted(..., reverse=True)` over a dict filled in index order.
+  test      candidate k against accepted detector d: count = the number of pairs (entry i of k, entry j of d) with the same image and
+            IoU > 0.3 of the boxes (x, y, x + box, y + box); k is rejected when count > max_pairs (5) for SOME d.  The count starts
+            from zero for every d: pairs from different accepted detectors never add up.
+  IoU       in integers: with inter = max(0, dx) max(0, dy) and A = box^2, the reference's float64 `inter / (2 A - inter) > 0.3` is
+            the same predicate as 13 inter > 6 A for box <= 2048: a ratio of exactly 3 / 10 rounds to the very double the literal
+            0.3 denotes (correct rounding of one rational), and any other ratio p / q, q <= 2 A, differs from 3 / 10 by at least
+            1 / (10 * 2 A) >= 2^-27, far more than the rounding of the division (2^-53 relative), so it stays on its side.
+  accept    append k; stop at num_detectors accepted or when the candidates run out.  accepted[0 ... n) are candidate indices in
+            acceptance order; slots past n hold -1.
+  contract  of the device entry: within one candidate's list every image occurs at most once (what a top-k over per-image winners
+            yields); `detector_rank` checks it when the lists come from the host.  The host restatement counts all pairs and so
+            covers the general case.
+  limits    1 <= N <= 32768 candidates, 1 <= L <= 128 entries, 1 <= num_detectors <= 4096, 1 <= box <= 2048.
+
+Not here: `filter_by_contrast` (skimage's `is_low_contrast`; `sample_patches` takes the caller's `accept`), the plots.
 """
 from __future__ import annotations
 
@@ -1165,3 +1190,440 @@ def sample_negatives(chunks, num_samples: int, fold=None, rng=None):
         return np.concatenate(out)
     import torch
     return torch.cat(out)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# detector initialisation (csrc/dense_search_wide.hip): `init_patches`, `init_detectors`, `rank_init_detectors` and
+# `accept_patch_neighbor` of doersch/doersch.py:46-64, 248-276, 317-400
+# ------------------------------------------------------------------------------------------------------------------------------
+DENSE_WIDE_MAX_DETECTORS = 32768     # DM_DENSE_WIDE_MAX_DETECTORS
+RANK_MAX_N = 32768                   # DM_DETECTOR_RANK_MAX_N
+RANK_MAX_L = 128                     # DM_DETECTOR_RANK_MAX_L
+RANK_MAX_DETECTORS = 4096            # DM_DETECTOR_RANK_MAX_DETECTORS
+RANK_MAX_BOX = 2048                  # DM_DETECTOR_RANK_MAX_BOX
+# DM_RANK_E_* (include/dm_engine.h)
+RANK_ERRORS = {1: "null argument", 2: f"N outside [1, {RANK_MAX_N}]", 3: f"L outside [1, {RANK_MAX_L}]",
+               4: f"num_detectors outside [1, {RANK_MAX_DETECTORS}]", 5: f"box outside [1, {RANK_MAX_BOX}]", 6: "max_pairs < 0",
+               7: "workspace too small", 8: "misaligned pointer", 9: "HIP error"}
+
+
+def _check_rank(rc: int, what: str):
+    if rc:
+        raise EngineError(f"{what}: {RANK_ERRORS.get(rc, 'error')} (code {rc})")
+
+
+def _check_wide_shape(B, cells, C_, K, top_k=1):
+    _check_shape(B, cells, C_, 1, top_k)
+    if not 1 <= K <= DENSE_WIDE_MAX_DETECTORS:
+        raise ValueError(f"wide search: {K} detectors, need 1 ... {DENSE_WIDE_MAX_DETECTORS}")
+
+
+def wide_workspace_bytes(B: int, cells: int, K: int) -> int:
+    need = _lib().dm_dense_wide_workspace_bytes(int(B), int(cells), int(K))
+    if not need:
+        raise ValueError(f"wide search: no workspace for {B} images of {cells} cells and {K} detectors")
+    return need
+
+
+def wide_winners(data, w, score, cell, image_offset: int = 0, mask=None, work=None):
+    """dm_dense_wide_winners on the current stream: `winners` for 1 <= K <= 32768 detectors, bit-equal to it over blocks of 128."""
+    import torch
+    B, cells, C_ = data.shape
+    K, ld = score.shape
+    dev = data.device
+    need = wide_workspace_bytes(B, cells, K)
+    if work is None:
+        work = torch.empty(need, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib().dm_dense_wide_winners(_stream(torch, dev), _p(data), _p(w), _p(mask), B, cells, C_, K, int(image_offset), ld,
+                                          _p(work), work.numel() * work.element_size(), _p(score), _p(cell))
+    _check(rc, "dm_dense_wide_winners")
+    return work
+
+
+def wide_topk(score, cell, n_images: int, top_k: int, image_h, positive=None, only_pos: bool = False):
+    """dm_dense_wide_topk on the current stream over columns [0, n_images) of the tables; image_h int32 [n_images] (the H of every
+    image's [W, H] block grid) and positive uint8 [n_images] or None on the device -> device tensors (top_score fp32 [K, top_k],
+    top_image int32, top_x int32, top_y int32, count int32 [K], d20 int32 [K] or None)."""
+    import torch
+    K, ld = score.shape
+    dev = score.device
+    top_score = torch.empty((K, top_k), dtype=torch.float32, device=dev)
+    top_image, top_x, top_y = (torch.empty((K, top_k), dtype=torch.int32, device=dev) for _ in range(3))
+    count = torch.empty(K, dtype=torch.int32, device=dev)
+    d20 = None if positive is None else torch.empty(K, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib().dm_dense_wide_topk(_stream(torch, dev), _p(score), _p(cell), K, int(n_images), ld, int(top_k), int(bool(only_pos)),
+                                       _p(positive), _p(image_h), _p(top_score), _p(top_image), _p(top_x), _p(top_y), _p(count), _p(d20))
+    _check(rc, "dm_dense_wide_topk")
+    return top_score, top_image, top_x, top_y, count, d20
+
+
+def iou_above_03(inter: int, box: int) -> bool:
+    """`iou(a, b) > 0.3` of two box x box squares that share `inter` pixels, in integers (the module docstring says why it is the
+    reference's float64 predicate for box <= 2048)."""
+    return 13 * int(inter) > 6 * int(box) * int(box)
+
+
+def _overlap(a, b, box):
+    return max(0, box - abs(int(a[0]) - int(b[0]))) * max(0, box - abs(int(a[1]) - int(b[1])))
+
+
+def rank_init_detectors_host(num_detectors: int, stats, patches, box: int = 64, max_pairs: int = 5):
+    """`rank_init_detectors` (doersch/doersch.py:371-385) with `accept_patch_neighbor` (:46-64) in plain Python, by the rules at the
+    top of this module.  stats: {'discriminative-20': {index: key}, 'neighbors': {index: [((x, y), path), ...]}, 'w': {index: row}}
+    -> [(index, patches[index], stats['w'][index]), ...] in acceptance order.  Counts all pairs: a path may occur more than once in
+    a list."""
+    if not 1 <= box <= RANK_MAX_BOX:
+        raise ValueError(f"rank: box {box}, need 1 ... {RANK_MAX_BOX}")
+    out, lists = [], {}
+    for k, _ in sorted(stats["discriminative-20"].items(), key=lambda x: x[1], reverse=True):
+        if len(out) == num_detectors:
+            break
+        mine = {}
+        for bbox, path in stats["neighbors"][k]:
+            mine.setdefault(path, []).append(bbox)
+        ok = True
+        for d, _, _ in out:
+            count = 0
+            for path, theirs in lists[d].items():
+                for bbox in mine.get(path, ()):
+                    for other in theirs:
+                        count += iou_above_03(_overlap(bbox, other, box), box)
+            if count > max_pairs:
+                ok = False
+                break
+        if ok:
+            out.append((k, patches[k], stats["w"][k]))
+            lists[k] = mine
+    return out
+
+
+def detector_rank_workspace_bytes(N: int, L: int, num_detectors: int) -> int:
+    need = _lib().dm_detector_rank_workspace_bytes(int(N), int(L), int(num_detectors))
+    if not need:
+        raise ValueError(f"rank: no workspace for {N} candidates of {L} entries and {num_detectors} detectors")
+    return need
+
+
+def detector_rank(key, nb_image, nb_x, nb_y, nb_count, num_detectors: int, box: int = 64, max_pairs: int = 5, device=None):
+    """dm_detector_rank on the current stream: key int32 [N], nb_image / nb_x / nb_y int32 [N, L], nb_count int32 [N] ->
+    (accepted int32 [num_detectors] on the device, -1 past the end; n_accepted int32 [1] on the device).  Device tensors are taken as
+    they are (the contract — an image at most once per list — is the caller's: a top-k over per-image winners keeps it).  numpy
+    arrays are checked against the contract and copied to `device`."""
+    import torch
+    if isinstance(key, np.ndarray):
+        if device is None:
+            raise ValueError("rank: numpy lists need the device to run on")
+        key, nb_image, nb_x, nb_y, nb_count = (np.ascontiguousarray(a, dtype=np.int32) for a in (key, nb_image, nb_x, nb_y, nb_count))
+        for k in range(len(key)):
+            row = nb_image[k, :max(0, min(int(nb_count[k]), nb_image.shape[1]))]
+            row = row[row >= 0]
+            if len(np.unique(row)) != len(row):
+                raise ValueError(f"rank: candidate {k} lists an image twice; the device entry needs every image at most once per list")
+        key, nb_image, nb_x, nb_y, nb_count = (torch.from_numpy(a).to(device) for a in (key, nb_image, nb_x, nb_y, nb_count))
+    tensors = (key, nb_image, nb_x, nb_y, nb_count)
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 for t in tensors):
+        raise EngineError("rank: the lists must be int32 torch tensors on the GPU, or numpy arrays")
+    key, nb_image, nb_x, nb_y, nb_count = (t.contiguous() for t in tensors)
+    if nb_image.ndim != 2 or not (nb_image.shape == nb_x.shape == nb_y.shape) or key.shape != (nb_image.shape[0],) or nb_count.shape != key.shape:
+        raise ValueError(f"rank: key {tuple(key.shape)}, lists {tuple(nb_image.shape)}, counts {tuple(nb_count.shape)}")
+    N, L = nb_image.shape
+    dev = key.device
+    work = torch.empty(detector_rank_workspace_bytes(N, L, num_detectors), dtype=torch.uint8, device=dev)
+    accepted = torch.empty(int(num_detectors), dtype=torch.int32, device=dev)
+    n = torch.empty(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib().dm_detector_rank(_stream(torch, dev), _p(key), _p(nb_image), _p(nb_x), _p(nb_y), _p(nb_count), N, L, int(box),
+                                     int(max_pairs), int(num_detectors), _p(work), work.numel(), _p(accepted), _p(n))
+    _check_rank(rc, "dm_detector_rank")
+    return accepted, n
+
+
+def rank_init_detectors(num_detectors: int, stats, patches, box: int = 64, max_pairs: int = 5):
+    """`rank_init_detectors(num_detectors, c, stats, patches)` of doersch/doersch.py:371-385 -> [(index, patch, w), ...].  stats: what
+    `CandidateSearch.result` returns.  Where stats['arrays'] holds device tensors (a search that ran on the GPU) the greedy loop runs
+    there by `detector_rank`, on the lists as the search left them; otherwise it is `rank_init_detectors_host`."""
+    arrays = stats.get("arrays")
+    if arrays is None or isinstance(arrays["key"], np.ndarray):
+        return rank_init_detectors_host(num_detectors, stats, patches, box, max_pairs)
+    accepted, n = detector_rank(arrays["key"], arrays["nb_image"], arrays["nb_x"], arrays["nb_y"], arrays["nb_count"], num_detectors, box,
+                                max_pairs)
+    accepted = accepted.cpu().numpy()[:int(n.cpu()[0])]
+    return [(int(k), patches[int(k)], stats["w"][int(k)]) for k in accepted]
+
+
+class CandidateSearch:
+    """The search of `init_detectors` (doersch/doersch.py:317-369): the wide twin of `DenseSearch` for any K <= 32768 candidates.
+
+        cs = CandidateSearch(w, positive_paths, top_k=50)
+        for paths, data in chunks: cs.add(paths, data)          # data: fp16 [B, W, H, C], on the GPU or numpy
+        stats = cs.result()
+
+    The two [K][n_images] tables and the path list grow as `DenseSearch`'s do; chunks may differ in (W, H).  `result()` gives the
+    reference's metadata {'discriminative-20': {index: d20}, 'neighbors': {index: [((x, y), path), ...]}, 'w': {index: fp16 row}}
+    plus 'arrays': key (the d20 counts) int32 [K], nb_image / nb_x / nb_y int32 [K, top_k], nb_count int32 [K] — device tensors after
+    a search on the GPU (`rank_init_detectors` takes them where they are), numpy arrays after the host restatement
+    (`winners_host` over blocks of 128 detectors, `topk_host`, `discriminative_20`)."""
+
+    def __init__(self, w, positive_paths, top_k: int = 50):
+        w = w.detach().cpu().numpy() if hasattr(w, "detach") else np.asarray(w)
+        if w.ndim != 2:
+            raise ValueError(f"wide search: w must be [K, C], got {w.shape}")
+        self.w = np.ascontiguousarray(w.astype(np.float16))
+        self.K, self.C = self.w.shape
+        self.top_k = int(top_k)
+        _check_wide_shape(1, 1, self.C, self.K, self.top_k)
+        self.positive = set(positive_paths)
+        self.paths, self.dims = [], []
+        self.n = 0
+        self._host = None
+        self._score = self._cell = self._w_dev = self._work = None
+
+    def add(self, paths, data, mask=None):
+        """One chunk: `paths` of its B images, data fp16 [B, W, H, C], mask [B, W H] (0 = the cell scores 0) or None."""
+        if data.ndim != 4 or data.shape[0] != len(paths) or data.shape[3] != self.C:
+            raise ValueError(f"wide search: chunk {tuple(data.shape)} for {len(paths)} paths and {self.C} channels")
+        B, W, H, _ = data.shape
+        _check_wide_shape(B, W * H, self.C, self.K, self.top_k)
+        if mask is not None and tuple(mask.shape) != (B, W * H):
+            raise ValueError(f"wide search: mask {tuple(mask.shape)}, need {(B, W * H)}")
+        host = isinstance(data, np.ndarray)
+        if self._host is None:
+            self._host = host
+        elif self._host != host:
+            raise ValueError("wide search: numpy and device chunks in one search")
+        (self._add_host if host else self._add_device)(data, mask, B, W * H)
+        self.paths += list(paths)
+        self.dims += [(W, H)] * B
+        self.n += B
+
+    _grow = DenseSearch._grow
+
+    def _add_host(self, data, mask, B, cells):
+        if data.dtype != np.float16:
+            raise ValueError("wide search: data must be float16")
+
+        def copy(dst, src):
+            dst[:, :self.n] = src[:, :self.n]
+        self._grow(B, lambda s, dt: np.empty(s, dtype=dt), copy)
+        data = data.reshape(B, cells, self.C)
+        mask = None if mask is None else np.asarray(mask)
+        for k0 in range(0, self.K, DENSE_MAX_DETECTORS):
+            s, c = winners_host(data, self.w[k0:k0 + DENSE_MAX_DETECTORS], mask)
+            self._score[k0:k0 + len(s), self.n:self.n + B], self._cell[k0:k0 + len(s), self.n:self.n + B] = s, c
+
+    def _add_device(self, data, mask, B, cells):
+        import torch
+        if not (isinstance(data, torch.Tensor) and data.is_cuda):
+            raise EngineError("CandidateSearch.add: data must be a torch tensor on the GPU, or numpy for the host restatement")
+        if data.dtype != torch.float16:
+            raise ValueError("wide search: data must be float16")
+        dev = data.device
+        if self._w_dev is None:
+            self._w_dev = torch.from_numpy(self.w).to(dev)
+        elif self._w_dev.device != dev:
+            raise ValueError(f"wide search: a chunk on {dev}, earlier ones on {self._w_dev.device}")
+        data = data.contiguous().view(B, cells, self.C)
+        if mask is not None:
+            mask = mask.to(device=dev, dtype=torch.uint8).contiguous()
+
+        def copy(dst, src):
+            dst[:, :self.n].copy_(src[:, :self.n])
+        self._grow(B, lambda s, dt: torch.empty(s, dtype=getattr(torch, dt), device=dev), copy)
+        need = wide_workspace_bytes(B, cells, self.K)
+        if self._work is None or self._work.numel() < need:
+            self._work = torch.empty(need, dtype=torch.uint8, device=dev)
+        wide_winners(data, self._w_dev, self._score, self._cell, self.n, mask, self._work)
+
+    def tables(self):
+        """(score float32 [K, n_images], cell int32 [K, n_images]) as numpy arrays."""
+        if not self.n:
+            raise ValueError("wide search: no chunk yet")
+        if self._host:
+            return self._score[:, :self.n].copy(), self._cell[:, :self.n].copy()
+        return self._score[:, :self.n].cpu().numpy(), self._cell[:, :self.n].cpu().numpy()
+
+    def result(self):
+        """The reference's `metadata` plus 'arrays' (the class docstring).  A candidate without an admissible image has an empty
+        neighbour list and d20 0."""
+        if not self.n:
+            raise ValueError("wide search: no chunk yet")
+        image_h = np.array([H for _, H in self.dims], dtype=np.int32)
+        positive = np.array([p in self.positive for p in self.paths], dtype=np.uint8)
+        if self._host:
+            _, img, cell, count = topk_host(self._score[:, :self.n], self._cell[:, :self.n], self.top_k)
+            h = image_h[np.maximum(img, 0)]
+            x, y = np.where(img >= 0, (cell // h) * 8, -1).astype(np.int32), np.where(img >= 0, (cell % h) * 8, -1).astype(np.int32)
+            lists = [[(None, (int(x[k, j]), int(y[k, j])), self.paths[img[k, j]]) for j in range(int(count[k]))] for k in range(self.K)]
+            d20 = np.array(discriminative_20(lists, self.positive), dtype=np.int32)
+            arrays = dict(key=d20, nb_image=img, nb_x=x, nb_y=y, nb_count=count)
+        else:
+            import torch
+            dev = self._score.device
+            _, img_d, x_d, y_d, count_d, d20_d = wide_topk(self._score, self._cell, self.n, self.top_k, torch.from_numpy(image_h).to(dev),
+                                                           torch.from_numpy(positive).to(dev))
+            arrays = dict(key=d20_d, nb_image=img_d, nb_x=x_d, nb_y=y_d, nb_count=count_d)
+            img, x, y, count, d20 = (t.cpu().numpy() for t in (img_d, x_d, y_d, count_d, d20_d))
+        neighbors = {k: [((int(x[k, j]), int(y[k, j])), self.paths[img[k, j]]) for j in range(int(count[k]))] for k in range(self.K)}
+        return {"discriminative-20": {k: int(d20[k]) for k in range(self.K)}, "neighbors": neighbors,
+                "w": {k: self.w[k] for k in range(self.K)}, "arrays": arrays}
+
+
+def sample_patches(image_sizes, how_many: int, num_trials: int = 100, accept=None, rng=None):
+    """The loop of `init_patches` (doersch/doersch.py:248-276).  image_sizes: {path: (width, height)} of the seed images (PIL's
+    `Image.size`) in the reference's insertion order -> [((x, y, x + 64, y + 64), path), ...], how_many of them.  Every image keeps
+    a grid [width // 8 - 8, height // 8 - 8] of positions; the paths are shuffled once and visited round-robin; a visit permutes the
+    free positions (`rng.permutation`), tries the first num_trials and takes the first that `accept(path, bbox)` admits (None: the
+    first); every trial marks position (X[0], Y[1]) of the permuted lists — the reference's line as written, which marks neither the
+    tried nor the taken position (with one free position left, where the reference's Y[1] fails, Y[0]).  The reference's accept is
+    skimage's `is_low_contrast` on the crop, which is not restated here.  rng: anything with `shuffle(list)` and `permutation(n)` — a
+    numpy Generator or RandomState; None draws as the reference does, from Python's `random.shuffle` and `numpy.random.permutation`."""
+    import random
+    shuffle = random.shuffle if rng is None else rng.shuffle
+    permutation = np.random.permutation if rng is None else rng.permutation
+    elems = {}
+    for path, (width, height) in image_sizes.items():
+        if width // 8 - 8 < 1 or height // 8 - 8 < 1:
+            raise ValueError(f"sample_patches: {path} of {width} x {height} pixels has no patch position")
+        elems[path] = np.zeros((width // 8 - 8, height // 8 - 8))
+    if not elems or how_many < 0:
+        raise ValueError("sample_patches: no seed image, or how_many < 0")
+    keys = list(elems.keys())
+    key_id, patches, idle = 0, [], 0
+    shuffle(keys)
+    while len(patches) < how_many:
+        path = keys[key_id]
+        X, Y = np.where(elems[path] == 0)
+        idx = permutation(len(X))
+        X, Y = X[idx][:num_trials], Y[idx][:num_trials]
+        before = len(patches)
+        for j in range(len(X)):
+            elems[path][X[0], Y[min(1, len(Y) - 1)]] = 1
+            bbox = (int(X[j]) * 8, int(Y[j]) * 8, int(X[j]) * 8 + 64, int(Y[j]) * 8 + 64)
+            if accept is None or accept(path, bbox):
+                patches.append((bbox, path))
+                break
+        idle = 0 if len(patches) > before or len(X) else idle + 1
+        if idle >= len(keys):
+            raise ValueError(f"sample_patches: no free position left after {len(patches)} of {how_many} patches")
+        key_id = (key_id + 1) % len(keys)
+    return patches
+
+
+def _patch_rows(data, picks):
+    """The detectors of one chunk's patches: data fp16 [B, W, H, C]; picks [(image in the chunk, bbox), ...] -> fp16 numpy [n, C],
+    row (bbox[0] // 8, bbox[1] // 8) of each image's features (`detector_from_patch`, one gather for the chunk)."""
+    B, W, H, C_ = data.shape
+    pairs = []
+    for b, bbox in picks:
+        a, c = int(bbox[0]) // 8, int(bbox[1]) // 8
+        if not (0 <= a < W and 0 <= c < H):
+            raise ValueError(f"init_detectors: bbox {tuple(bbox)} outside {W} x {H} blocks")
+        pairs.append((b, a * H + c))
+    pairs = np.array(pairs, dtype=np.int32)
+    if isinstance(data, np.ndarray):
+        return data.reshape(B, W * H, C_)[pairs[:, 0], pairs[:, 1]].copy()
+    import torch
+    return gather(data.contiguous().view(B, W * H, C_), torch.from_numpy(pairs).to(data.device)).cpu().numpy()
+
+
+def _init_from_chunks(patches, positive_paths, top_k, chunks_from, cache_bytes):
+    """chunks_from(start) yields (paths, data fp16 [B, W, H, C]) from chunk `start` on.  Pass one takes every candidate's own row
+    and keeps the chunks themselves while they fit `cache_bytes`; pass two searches the kept chunks and produces only the rest again."""
+    want = {}
+    for index, (bbox, path) in enumerate(patches):
+        want.setdefault(path, []).append((index, bbox))
+    rows, kept, held, full = [None] * len(patches), [], 0, False
+    for names, data in chunks_from(0):
+        picks = [(b, index, bbox) for b, name in enumerate(names) for index, bbox in want.get(name, ())]
+        if picks:
+            for (_, index, _), row in zip(picks, _patch_rows(data, [(b, bbox) for b, _, bbox in picks])):
+                rows[index] = row
+        size = int(np.prod(data.shape)) * 2
+        if not full and held + size <= cache_bytes:
+            kept.append((names, data))
+            held += size
+        else:
+            full = True
+    missing = [patches[i][1] for i, r in enumerate(rows) if r is None]
+    if missing:
+        raise ValueError(f"init_detectors: {len(missing)} patches of images outside the data set, e.g. {missing[0]}")
+    cs = CandidateSearch(np.stack(rows), positive_paths, top_k=top_k)
+    for names, data in kept:
+        cs.add(names, data)
+    if full:
+        for names, data in chunks_from(len(kept)):
+            cs.add(names, data)
+    return cs.result()
+
+
+def init_detectors(patches, sft_paths, positive_paths, top_k: int = 50, device_id: str = "cuda", cache_bytes: int = 8 << 30):
+    """`init_detectors(c, patches)` of doersch/doersch.py:317-369 on the reference's safetensors shards (each key `';;'.join(paths)`
+    with a tensor [B, W, H, C] of normalised features, as `dense_search` reads them): candidate `index` of patches = [(bbox, path),
+    ...] becomes the detector `features(path)[bbox[0] // 8, bbox[1] // 8]` (:337) and all of them search every key of every shard.
+    The shards are read once where all of them fit `cache_bytes` of device (or host) memory, twice otherwise.  device_id "cpu" takes
+    the numpy restatements.  Returns what `CandidateSearch.result` returns."""
+    import torch
+    from safetensors import safe_open
+    host = device_id == "cpu"
+    device = torch.device(device_id)
+
+    def chunks_from(start):
+        at = 0
+        for sft_path in sft_paths:
+            with safe_open(sft_path, framework="pt", device=device_id if device_id in ("cuda", "cpu") else device.index) as f:
+                for key in f.keys():
+                    at += 1
+                    if at <= start:
+                        continue
+                    data = f.get_tensor(key).to(device).half()
+                    yield key.split(";;"), (data.numpy() if host else data)
+    return _init_from_chunks(patches, positive_paths, top_k, chunks_from, cache_bytes)
+
+
+def init_detectors_images(patches, image_paths, positive_paths, batch: int = 16, top_k: int = 50, device_id: str = "cuda",
+                          cache_bytes: int = 8 << 30):
+    """`init_detectors`, fed from image files: per batch of `batch` paths the images are read (`read_images`) and their features
+    computed (`hoglab`), size group by size group as in `dense_search_images`.  The candidates' own rows are gathered from the same
+    features, so a data set whose features fit `cache_bytes` is read once for both purposes; past that the remaining batches are
+    read and computed a second time for the search.  Returns what `CandidateSearch.result` returns."""
+    import torch
+    if batch < 1:
+        raise ValueError(f"init_detectors: batch {batch}")
+    host = device_id == "cpu"
+    device = torch.device(device_id)
+    image_paths = list(image_paths)
+
+    group_counts = []                                # size groups per batch, known once the batch has been read
+
+    def chunks_from(start):
+        n = 0
+        for bi, at in enumerate(range(0, len(image_paths), batch)):
+            names = image_paths[at:at + batch]
+            if bi < len(group_counts) and n + group_counts[bi] <= start:
+                n += group_counts[bi]
+                continue
+            groups = read_images(names)
+            if bi == len(group_counts):
+                group_counts.append(len(groups))
+            for g, (idx, images) in enumerate(groups):
+                if n + g >= start:
+                    data = hoglab(images) if host else hoglab(torch.from_numpy(images).to(device))
+                    yield [names[j] for j in idx], data
+            n += len(groups)
+    return _init_from_chunks(patches, positive_paths, top_k, chunks_from, cache_bytes)
+
+
+def initialize_classifier(seed_paths, image_paths, positive_paths, how_many: int = 25000, num_detectors: int = 1000,
+                          num_trials: int = 100, accept=None, rng=None, batch: int = 16, top_k: int = 50, device_id: str = "cuda"):
+    """`initialize_classifier` (doersch/doersch.py:387-400) without its cache files: `sample_patches` over the seed images' sizes,
+    `init_detectors_images` over the data set, `rank_init_detectors` -> (patches, [(index, patch, w), ...])."""
+    from PIL import Image
+    sizes = {}
+    for path in seed_paths:
+        with Image.open(path) as im:
+            sizes[path] = im.size
+    patches = sample_patches(sizes, how_many, num_trials=num_trials, accept=accept, rng=rng)
+    stats = init_detectors_images(patches, image_paths, positive_paths, batch=batch, top_k=top_k, device_id=device_id)
+    return patches, rank_init_detectors(num_detectors, stats, patches)

@@ -58,6 +58,11 @@ SIGNATURES = {
     "dm_dense_search_winners": (_i32, [_vp] * 4 + [_i32] * 6 + [_vp, _sz, _vp, _vp]),
     "dm_dense_search_topk": (_i32, [_vp] * 3 + [_i32] * 5 + [_vp] * 4),
     "dm_dense_search_gather": (_i32, [_vp, _vp] + [_i32] * 3 + [_vp, _i32, _vp]),
+    "dm_dense_wide_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "dm_dense_wide_winners": (_i32, [_vp] * 4 + [_i32] * 6 + [_vp, _sz, _vp, _vp]),
+    "dm_dense_wide_topk": (_i32, [_vp] * 3 + [_i32] * 5 + [_vp] * 8),
+    "dm_detector_rank_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "dm_detector_rank": (_i32, [_vp] * 6 + [_i32] * 5 + [_vp, _sz, _vp, _vp]),
     "dm_hoglab_bin_table": (_i32, [_vp]),
     "dm_hoglab_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "dm_hoglab_cells": (_i32, [_vp, _vp] + [_i32] * 3 + [_vp] * 3),

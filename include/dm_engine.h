@@ -415,6 +415,60 @@ int dm_dense_search_topk(void* stream, const float* score_f32, const int32_t* ce
                          int only_pos, float* top_score_f32, int32_t* top_image_i32, int32_t* top_cell_i32, int32_t* count_i32);
 int dm_dense_search_gather(void* stream, const void* data_f16, int B, int cells, int C, const int32_t* pairs_i32, int n, void* out_f16);
 
+/* ---- Doersch baseline: detector initialisation, wide search and greedy ranking (csrc/dense_search_wide.hip) ------------
+ * `init_detectors` and `rank_init_detectors` of doersch/doersch.py:317-385: every one of thousands of candidate detectors against
+ * every cell of every image, then the greedy choice of the candidates whose neighbour lists do not overlap an accepted one's.
+ *
+ * dm_dense_wide_winners: the contract of dm_dense_search_winners — the same operands, tables [K][ld], mask / NaN / -0 / lowest-cell
+ * rules and refusals — for 1 <= K <= DM_DENSE_WIDE_MAX_DETECTORS.  For every (k, image) the result is BIT-EQUAL to what
+ * dm_dense_search_winners writes when the same detectors are given to it in blocks of DM_DENSE_MAX_DETECTORS: a score's chain of
+ * MFMAs is the same (ascending blocks of 64 channels, two v_mfma_f32_16x16x32_f16 per block, the same channels in the same lane
+ * groups, zero chunks past C).  A workgroup stages 256 cells x 256 detectors through LDS per 64-channel step.  work:
+ * dm_dense_wide_workspace_bytes(B, cells, K) bytes (0 = bad arguments), 8-byte aligned, contents free: a [B][K] table of packed
+ * (ordered score bits, inverted cell) keys that the call zeroes and merges into by a 64-bit unsigned integer atomic max (a vector
+ * memory atomic; the order of arrival cannot matter).  No floating-point atomics: the same input gives the same bits on every run.
+ *
+ * dm_dense_wide_topk: dm_dense_search_topk's admission and order for K up to the wide limit.  Per listed entry it gives the
+ * reference's box corner top_x = (cell / H) 8, top_y = (cell % H) 8 with H = image_h_i32[image] (images of one search may differ in
+ * size) instead of the cell.  d20_i32_or_null [K]: the number of positive_u8_or_null[image] != 0 among the first min(20, count[k])
+ * entries (`search_batch`, doersch.py:95); it needs positive_u8_or_null [n_images].  Slots from count on hold NaN / -1 / -1 / -1.
+ *
+ * dm_detector_rank: key_i32 [N] (the d20 count; any int32), the candidates' lists nb_image_i32 / nb_x_i32 / nb_y_i32 [N][L] of which
+ * the first min(max(nb_count_i32[k], 0), L) entries count (an entry with a negative image is none).  Candidates are visited by
+ * descending key, ascending index among equal keys.  Candidate k is rejected when for SOME accepted detector d the number of pairs
+ * (entry of k, entry of d) with the same image and 13 inter > 6 box^2 (= IoU > 0.3 of the boxes (x, y, x + box, y + box), exactly)
+ * exceeds max_pairs; the count starts from zero for every d.  Otherwise k is accepted.  The visit stops at num_detectors accepted
+ * or after the last candidate: accepted_i32 [num_detectors] = candidate indices in acceptance order, -1 from n on;
+ * n_accepted_i32 [1] = n.  Contract: within one candidate's list an image occurs at most once (what a top-k over per-image winners
+ * yields).  work: dm_detector_rank_workspace_bytes(N, L, num_detectors) bytes (0 = bad arguments), 4-byte aligned, contents free
+ * (the visiting order and the accepted detectors' lists).  Integer arithmetic throughout; one persistent workgroup.
+ * Refused without a launch (DM_RANK_E_*): a null pointer; N, L, num_detectors or box outside [1, DM_DETECTOR_RANK_MAX_*];
+ * max_pairs < 0; a workspace that is too small; a misaligned workspace. */
+#define DM_DENSE_WIDE_MAX_DETECTORS 32768
+#define DM_DETECTOR_RANK_MAX_N 32768
+#define DM_DETECTOR_RANK_MAX_L 128
+#define DM_DETECTOR_RANK_MAX_DETECTORS 4096
+#define DM_DETECTOR_RANK_MAX_BOX 2048
+#define DM_RANK_E_NULL 1
+#define DM_RANK_E_N 2
+#define DM_RANK_E_L 3
+#define DM_RANK_E_DETECTORS 4
+#define DM_RANK_E_BOX 5
+#define DM_RANK_E_PAIRS 6
+#define DM_RANK_E_WORK 7
+#define DM_RANK_E_ALIGN 8
+#define DM_RANK_E_HIP 9
+size_t dm_dense_wide_workspace_bytes(int B, int cells, int K);
+int dm_dense_wide_winners(void* stream, const void* data_f16, const void* w_f16, const void* mask_u8_or_null, int B, int cells, int C,
+                          int K, int image_offset, int ld, void* work, size_t work_bytes, float* score_f32, int32_t* cell_i32);
+int dm_dense_wide_topk(void* stream, const float* score_f32, const int32_t* cell_i32, int K, int n_images, int ld, int top_k, int only_pos,
+                       const void* positive_u8_or_null, const int32_t* image_h_i32, float* top_score_f32, int32_t* top_image_i32,
+                       int32_t* top_x_i32, int32_t* top_y_i32, int32_t* count_i32, int32_t* d20_i32_or_null);
+size_t dm_detector_rank_workspace_bytes(int N, int L, int num_detectors);
+int dm_detector_rank(void* stream, const int32_t* key_i32, const int32_t* nb_image_i32, const int32_t* nb_x_i32, const int32_t* nb_y_i32,
+                     const int32_t* nb_count_i32, int N, int L, int box, int max_pairs, int num_detectors, void* work, size_t work_bytes,
+                     int32_t* accepted_i32, int32_t* n_accepted_i32);
+
 /* ---- Doersch baseline: HOG-LAB features from pixels (csrc/hoglab.hip) ------------------------------------------------
  * `get_hoglab_single` + `normalize` of doersch/hog.py:24-87 on the device: B RGB uint8 images [B][H][W][3] of one size -> per image
  * the [bc][br][2112] tensor the dense search reads (nr = H / 8, nc = W / 8 cells of 8 x 8 pixels, br = nr - 7, bc = nc - 7 blocks of
