@@ -16,8 +16,9 @@ max_iter=300, tol=1e-4), restated here in numpy (`kmeans_fit_host`) with the rul
             distance (each leaves its old cluster's sum and count); shift = sum_j |c_new - c_old|^2; stop strictly when the labels
             repeat, else when shift <= tol_abs; after a non-strict stop (or max_iter) one more assignment.
 
-UMAP stays with the caller (the reference's default is project=False): pass the reduced matrix as `features` and the originals as
-`rank_features`.  One call clusters one category; several categories are several calls (no batched entry yet).
+UMAP (umapfit.py, csrc/umap.hip; parity with umap-learn unpinned) is `cluster_patches(project=...)`: `project=5` is the main
+stage's project=True, `project=('groups', G, 32)` the parallel dataset's compress(); the default None is the reference's
+project=False.  One call clusters one category; several categories are several calls (no batched entry yet).
 """
 from __future__ import annotations
 
@@ -309,12 +310,32 @@ def rank_clusters(X, labels, centers, D, aggregate: str = "median", order_by: st
 
 
 def cluster_patches(features, D, num_clusters: int = 32, aggregate: str = "median", seed: int = 10, order_by: str = "centroid",
-                    rank_features=None, max_iter: int = 300, tol: float = 1e-4):
+                    rank_features=None, max_iter: int = 300, tol: float = 1e-4, *, project=None, project_seed: int = 42):
     """`cluster()` of the reference as arrays: fit, then rank.  On a GPU tensor both run on the device and only the small result
     comes back; a numpy array (or a CPU tensor) takes the numpy restatement.  Returns a dict: 'clusters' = a list, best first, of
     {'cluster': id, 'rows': row ids in order (int32), 'aggregate': float}, plus 'labels', 'centers', 'seed_index', 'inertia',
-    'n_iter'.  ids, paths and images stay the caller's, keyed by row."""
+    'n_iter'.  ids, paths and images stay the caller's, keyed by row.
+
+    project: None = no projection.  An int c = the main stage's project=True with `umap.UMAP(n_components=c)` (typicality/cluster.py:
+    314-317; the reference uses 5): k-means and the ranking both run on the embedding.  ('groups', G, c) = the parallel dataset's
+    cluster() (cluster.py:268-289): k-means on `umapfit.compress(features, G, c)`, members ranked with order_by='farthest' on the
+    original features.  project_seed seeds the projection (umap-learn is unseeded at both call sites).  With a projection the dict
+    also holds 'embedding'."""
     import torch
+    embedding = None
+    if project is not None:
+        from . import umapfit
+        if isinstance(project, (tuple, list)):
+            if len(project) != 3 or project[0] != "groups":
+                raise ValueError(f"cluster_patches: project {project!r} (None, an int, or ('groups', G, n_components))")
+            embedding = umapfit.compress(features, int(project[1]), int(project[2]), seed=project_seed)
+            features, rank_features, order_by = embedding, features if rank_features is None else rank_features, "farthest"
+        else:
+            on_dev = isinstance(features, torch.Tensor) and features.is_cuda
+            fit = umapfit.umap_fit if on_dev else umapfit.umap_fit_host
+            embedding = fit(features if on_dev else (features.numpy() if isinstance(features, torch.Tensor) else np.asarray(features)),
+                            int(project), seed=project_seed)["embedding"]
+            features = embedding
     on_gpu = isinstance(features, torch.Tensor) and features.is_cuda
     if on_gpu:
         labels, centers, seeds, inertia, n_iter = kmeans_fit(features, num_clusters, seed, max_iter, tol)
@@ -328,4 +349,7 @@ def cluster_patches(features, D, num_clusters: int = 32, aggregate: str = "media
         labels, centers, seeds, inertia, n_iter = kmeans_fit_host(f, num_clusters, seed, max_iter, tol)
         order, cor, off, agg, nn = rank_clusters_host(f, labels, centers, Dh, aggregate, order_by, r)
     clusters = [{"cluster": int(cor[r]), "rows": order[off[r]:off[r + 1]].copy(), "aggregate": float(agg[r])} for r in range(nn)]
-    return {"clusters": clusters, "labels": labels, "centers": centers, "seed_index": seeds, "inertia": inertia, "n_iter": n_iter}
+    out = {"clusters": clusters, "labels": labels, "centers": centers, "seed_index": seeds, "inertia": inertia, "n_iter": n_iter}
+    if embedding is not None:
+        out["embedding"] = embedding
+    return out

@@ -52,6 +52,10 @@ SIGNATURES = {
     "dm_kmeans_workspace_bytes": (_i32, [_i32, _i32, _i32, _psz]),
     "dm_kmeans_fit": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _f32, _vp, _sz] + [_vp] * 5),
     "dm_cluster_rank": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _sz] + [_vp] * 5),
+    "dm_umap_workspace_bytes": (_i32, [_i32] * 4 + [_psz]),
+    "dm_umap_knn": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp, _vp]),
+    "dm_umap_graph": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _sz] + [_vp] * 7),
+    "dm_umap_layout": (_i32, [_vp] * 4 + [_i32] * 3 + [_f32, _f32] + [_i32] * 4 + [_vp, _vp, _sz]),
     "dm_xray_eval_workspace_bytes": (_sz, [_i32, _i32, _i64]),
     "dm_xray_eval": (_i32, [_vp, _vp, _i32, _vp, _i32] + [_vp] * 6),
     "dm_dense_search_workspace_bytes": (_sz, [_i32, _i32, _i32]),
@@ -344,6 +348,13 @@ class _EngineBase:
         from . import clustering
         with self._torch.cuda.device(self.device):
             return clustering.rank_clusters(X, labels, centers, D, aggregate, order_by, rank_features, work)
+
+    def umap_fit(self, X, n_components: int, n_neighbors: int = 15, seed: int = 42, n_epochs=None, work=None):
+        """The UMAP projection of the clustering stage on this engine's device and current stream (dm_umap_knn / dm_umap_graph /
+        dm_umap_layout; see `umapfit.umap_fit`; parity with umap-learn unpinned)."""
+        from . import umapfit
+        with self._torch.cuda.device(self.device):
+            return umapfit.umap_fit(X, n_components, n_neighbors, seed, n_epochs, work)
 
     def xray_eval(self, maps, boxes, thresholds=None, work=None):
         """The counts of the X-ray application's AUC-PR and the box sums for a batch of heat-maps on this engine's device and

@@ -1,0 +1,463 @@
+"""UMAP projection for the clustering stage: `umap.UMAP(n_components=c, n_neighbors=k).fit_transform(X)` as the reference calls it
+(typicality/cluster.py:312-317 with c = 5; applications/parallel-dataset/cluster.py:253-270 with c = 32, k = 15, once per country's
+block of the features).  Kernels: csrc/umap.hip; C ABI: dm_umap_workspace_bytes / dm_umap_knn / dm_umap_graph / dm_umap_layout.
+
+PARITY UNPINNED.  The rules below restate umap-learn 0.5.6 (the reference's environment.yaml) at the two call sites' settings from
+the paper and from memory: umap-learn was not at hand to record its outputs.  tests/make_golden_umap.py records them wherever it is
+installed; until tests/golden/umap_ref.npz is committed, nothing here is checked against umap-learn itself.  The layout departs from
+umap-learn on purpose (below), so the embedding is never bit-comparable; kNN, rho, sigma, the graph, a and b are meant to be.
+
+Settings: euclidean, min_dist 0.1, spread 1, n_epochs None -> 500 (n <= 10 000), learning_rate 1, init 'spectral',
+negative_sample_rate 5, set_op_mix_ratio 1, local_connectivity 1, repulsion_strength 1.  Each rule is written once in numpy here
+(`*_host`) and once in the kernels:
+
+  a, b      scipy curve_fit of 1 / (1 + a x^(2b)) to y = 1 (x < min_dist), exp(-(x - min_dist) / spread) on linspace(0, 3 spread,
+            300): 1.5769, 0.8951 at the defaults.  Host only.
+  kNN       exact (umap-learn's own path below 4096 rows; n >= 4096 is refused).  Squared distance = the sum over ascending
+            feature index of (double(x_i) - double(x_k))^2 in fp64, multiply and add separate; distance = fp64 sqrt rounded to
+            fp32; the n_neighbors smallest per row, self included, ties to the lower index.  Host and device agree bit for bit.
+  smooth    rho_i = the smallest non-zero neighbour distance (0 if none).  sigma_i: 64 bisection steps at most (lo 0, hi inf, mid
+            1, doubling while hi is inf) on sum_{j >= 1} (d_ij - rho_i > 0 ? exp(-(d_ij - rho_i) / sigma) : 1) = log2(n_neighbors),
+            stopping at |diff| < 1e-5; then the floor 1e-3 x the row's mean distance (rho_i > 0) or 1e-3 x the global mean.  The
+            sum runs over j in ascending order in fp64 (umap-learn's numba loop is fp64 too); rho, sigma are stored as fp32.
+  graph     membership 0 for self (by index), 1 where d - rho <= 0 or sigma = 0, else exp(-(d - rho) / sigma) rounded to fp32;
+            P = (A + A^T) - A o A^T in fp32; entries below max(P) / n_epochs become 0.  Edges = the non-zeros of P in row-major
+            order, ascending column; that order is the edge id.
+  schedule  fp32: eps_e = max(P) / P_e, epn_e = eps_e / 5, next_e = eps_e, next_neg_e = epn_e.
+  init      (host; runs once, the graph is dense below 4096 rows) eigenvectors 1..dim of I - D^-1/2 P D^-1/2 (numpy eigh), sign
+            fixed so the largest-magnitude entry is positive, scaled to 10 / max|.|, plus seeded N(0, 1e-4) noise.  A disconnected
+            graph or dim + 1 >= n: umap-learn's init='random', seeded uniform(-10, 10) (its multi-component spectral layout is out
+            of scope).  Either way each coordinate is then rescaled to [0, 10], as umap-learn does for every init.
+  layout    SYNCHRONOUS within an epoch -- the departure.  umap-learn's numba loop updates coordinates in place from parallel
+            threads, which is not reproducible even on the CPU.  Here, in epoch ep (alpha = 1 - ep / n_epochs, fp32): every read
+            is of the epoch's input coordinates; vertex i walks its edges (i, j) in edge order, and for each with next_e <= ep
+              1. adds 2 clip(g (y_i - y_j), +-4) alpha, g = -2ab d^(2(b-1)) / (a d^(2b) + 1), g = 0 at d^2 = 0.  The 2 is exact:
+                 the graph is symmetric, (j, i) has the same weight and schedule, and umap-learn's move_other update of (j, i)
+                 moves i by the same amount;
+              2. n_neg = int((ep - next_neg_e) / epn_e) repulsive moves clip(g (y_i - y_k), +-4) alpha, g = 2b / ((0.001 + d^2)
+                 (a d^(2b) + 1)), k = hash(seed, ep, e, p) mod n, nothing at d^2 = 0;
+              3. next_e += eps_e, next_neg_e += n_neg epn_e;
+            all into one accumulator per coordinate in that order, then y_new = y + acc into the second buffer.  No atomics: the
+            result is bit-reproducible.  d^2 is summed by the 64-lane halving tree the kernel's wave reduction uses.  The schedule
+            and alpha are fp32 everywhere; `layout_host(dtype=)` sets the precision of coordinates, gradients and accumulator.
+
+A GPU tensor takes the device path and a numpy array the restatement; there is no quiet fall-back between them.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import time
+
+import numpy as np
+
+from .engine import EngineError, _p, load_library as _lib
+
+UMAP_MAX_N = 4096            # DM_UMAP_MAX_N: n >= this is refused (umap-learn switches to approximate neighbours there)
+UMAP_MAX_NEIGHBORS = 64      # DM_UMAP_MAX_NEIGHBORS
+UMAP_MAX_COMPONENTS = 64     # DM_UMAP_MAX_COMPONENTS
+NEG_RATE = 5
+SMOOTH_STEPS = 64
+SMOOTH_TOL = 1e-5
+MIN_K_DIST_SCALE = 1e-3
+# dm_umap_* return codes (include/dm_engine.h)
+ERRORS = {1: "null argument", 2: f"n >= {UMAP_MAX_N}", 3: "n_neighbors >= n", 4: f"n_neighbors outside [2, {UMAP_MAX_NEIGHBORS}]",
+          5: f"n_components outside [1, {UMAP_MAX_COMPONENTS}]", 6: "d < 1", 7: "bad epoch range", 8: "workspace too small",
+          9: "bad edge count", 10: "HIP error"}
+
+
+def default_epochs(n: int) -> int:
+    return 500 if n <= 10000 else 200
+
+
+def _check(n, d, k, dim=1):
+    if n >= UMAP_MAX_N:
+        raise ValueError(f"umap: n {n} >= {UMAP_MAX_N} (exact neighbours only)")
+    if k < 2 or k > UMAP_MAX_NEIGHBORS:
+        raise ValueError(f"umap: n_neighbors {k} outside [2, {UMAP_MAX_NEIGHBORS}]")
+    if k >= n:
+        raise ValueError(f"umap: n_neighbors {k} >= n {n}")
+    if dim < 1 or dim > UMAP_MAX_COMPONENTS:
+        raise ValueError(f"umap: n_components {dim} outside [1, {UMAP_MAX_COMPONENTS}]")
+    if d < 1:
+        raise ValueError("umap: d < 1")
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the numpy restatement: the CPU-tier yardstick, and what runs on a numpy array
+# ------------------------------------------------------------------------------------------------------------------------------
+def find_ab_params(spread: float = 1.0, min_dist: float = 0.1):
+    from scipy.optimize import curve_fit
+
+    def curve(x, a, b):
+        return 1.0 / (1.0 + a * x ** (2 * b))
+
+    xv = np.linspace(0, spread * 3, 300)
+    yv = np.zeros(xv.shape)
+    yv[xv < min_dist] = 1.0
+    yv[xv >= min_dist] = np.exp(-(xv[xv >= min_dist] - min_dist) / spread)
+    params, _ = curve_fit(curve, xv, yv)
+    return float(params[0]), float(params[1])
+
+
+def knn_host(X, n_neighbors: int = 15):
+    """(idx int32 [n, k], dist fp32 [n, k]) by the kNN rule at the top of this module."""
+    X = np.ascontiguousarray(X, dtype=np.float32)
+    n, d = X.shape
+    _check(n, d, n_neighbors)
+    Xd = X.astype(np.float64)
+    sq = np.zeros((n, n), dtype=np.float64)
+    t = np.empty((n, n), dtype=np.float64)
+    for e in range(d):                                   # ascending feature index, multiply and add separate
+        col = Xd[:, e]
+        np.subtract(col[:, None], col[None, :], out=t)
+        np.multiply(t, t, out=t)
+        sq += t
+    dist = np.sqrt(sq).astype(np.float32)
+    idx = np.argsort(dist, axis=1, kind="stable")[:, :n_neighbors].astype(np.int32)
+    return idx, np.take_along_axis(dist, idx, axis=1)
+
+
+def _smooth_host(dist, dtype):
+    """rho, sigma (fp32 [n]) and the flag of rows where the floor or the step cap decided sigma."""
+    n, k = dist.shape
+    f = np.dtype(dtype).type
+    target = f(np.log2(k))
+    big = np.where(dist > 0, dist, np.float32(np.inf)).min(axis=1)
+    rho = np.where(np.isfinite(big), big, np.float32(0)).astype(np.float32)
+    x = dist.astype(dtype) - rho.astype(dtype)[:, None]
+    lo = np.zeros(n, dtype)
+    hi = np.full(n, np.inf, dtype)
+    mid = np.ones(n, dtype)
+    live = np.ones(n, bool)
+    with np.errstate(over="ignore", divide="ignore", invalid="ignore"):
+        for _ in range(SMOOTH_STEPS):
+            psum = np.zeros(n, dtype)
+            for j in range(1, k):
+                psum = psum + np.where(x[:, j] > 0, np.exp(-(x[:, j] / mid)), f(1))
+            live &= ~(np.abs(psum - target) < f(SMOOTH_TOL))
+            if not live.any():
+                break
+            over = psum > target
+            new_hi = np.where(over, mid, hi)
+            new_lo = np.where(over, lo, mid)
+            new_mid = np.where(over, (lo + mid) / f(2), np.where(np.isinf(hi), mid * f(2), (mid + hi) / f(2)))
+            hi, lo, mid = np.where(live, new_hi, hi), np.where(live, new_lo, lo), np.where(live, new_mid, mid)
+    d64 = dist.astype(np.float64)
+    row_sum = np.zeros(n, np.float64)
+    for j in range(k):
+        row_sum = row_sum + d64[:, j]
+    floor = np.where(rho > 0, MIN_K_DIST_SCALE * (row_sum / k), MIN_K_DIST_SCALE * (row_sum.sum() / (n * k)))
+    floored = mid.astype(np.float64) < floor
+    sigma = np.where(floored, floor, mid.astype(np.float64)).astype(np.float32)
+    return rho, sigma, floored | live
+
+
+def fuzzy_graph_host(idx, dist, n_epochs: int = 500, dtype=np.float64):
+    """The fuzzy simplicial set from the kNN arrays.  dtype: the precision of the bisection and of exp (float64 is the rule; float32
+    is there to measure what fp32 costs).  Returns a dict: rho, sigma (fp32 [n]), exempt (bool [n]: floor or step cap decided sigma),
+    P (fp32 [n, n], pruned), threshold, row_ptr (int32 [n + 1]), col (int32 [E]), weight (fp32 [E])."""
+    idx = np.asarray(idx)
+    dist = np.asarray(dist, dtype=np.float32)
+    n, k = dist.shape
+    rho, sigma, exempt = _smooth_host(dist, dtype)
+    x = dist.astype(dtype) - rho.astype(dtype)[:, None]
+    s = sigma.astype(dtype)[:, None]
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        val = np.where((x <= 0) | (s == 0), np.dtype(dtype).type(1), np.exp(-(x / s))).astype(np.float32)
+    val[idx == np.arange(n)[:, None]] = 0
+    A = np.zeros((n, n), np.float32)
+    np.put_along_axis(A, idx.astype(np.int64), val, axis=1)
+    P = (A + A.T) - A * A.T
+    thr = np.float32(P.max() / np.float32(n_epochs))
+    P[P < thr] = 0
+    rows, cols = np.nonzero(P)                                 # row-major, ascending column
+    row_ptr = np.zeros(n + 1, np.int32)
+    row_ptr[1:] = np.cumsum(np.bincount(rows, minlength=n))
+    return {"rho": rho, "sigma": sigma, "exempt": exempt, "P": P, "threshold": thr, "row_ptr": row_ptr, "col": cols.astype(np.int32),
+            "weight": P[rows, cols]}
+
+
+def schedule_host(weight):
+    """(eps, epn, next, next_neg), fp32 [E]"""
+    weight = np.asarray(weight, np.float32)
+    eps = (weight.max() if len(weight) else np.float32(1)) / weight
+    epn = eps / np.float32(NEG_RATE)
+    return eps, epn, eps.copy(), epn.copy()
+
+
+def _rescale(Y):
+    lo, hi = Y.min(axis=0), Y.max(axis=0)
+    return (10.0 * (Y - lo) / (hi - lo)).astype(np.float32)
+
+
+def spectral_init_host(P, dim: int, seed: int = 42):
+    """(Y0 fp32 [n, dim], 'spectral' | 'random') from the dense graph, by the init rule at the top of this module."""
+    from scipy.sparse.csgraph import connected_components
+    P = np.asarray(P, dtype=np.float64)
+    n = P.shape[0]
+    rs = np.random.RandomState(seed)
+    n_comp = connected_components(P > 0, directed=False)[0] if n else 0
+    if n_comp != 1 or dim + 1 >= n:
+        return _rescale(rs.uniform(low=-10.0, high=10.0, size=(n, dim))), "random"
+    isd = 1.0 / np.sqrt(P.sum(axis=1))
+    L = np.eye(n) - isd[:, None] * P * isd[None, :]
+    L = (L + L.T) * 0.5
+    _, vec = np.linalg.eigh(L)
+    Y = vec[:, 1:dim + 1].copy()
+    top = np.abs(Y).argmax(axis=0)
+    Y *= np.sign(Y[top, np.arange(dim)])[None, :]
+    Y = (Y * (10.0 / np.abs(Y).max())).astype(np.float32) + rs.normal(scale=0.0001, size=(n, dim)).astype(np.float32)
+    return _rescale(Y), "spectral"
+
+
+_M32 = np.uint64(0xFFFFFFFF)
+
+
+def _mix32(h):
+    h = h ^ (h >> np.uint64(16))
+    h = (h * np.uint64(0x7FEB352D)) & _M32
+    h = h ^ (h >> np.uint64(15))
+    h = (h * np.uint64(0x846CA68B)) & _M32
+    return h ^ (h >> np.uint64(16))
+
+
+def hash_host(seed, ep, e, p):
+    """The layout's counter-based 32-bit mix (umap_hash in csrc/umap.hip): uint64 arrays holding 32-bit values."""
+    e = np.asarray(e).astype(np.uint64)
+    h = _mix32(np.uint64(int(seed) & 0x7FFFFFFF) ^ ((np.uint64(ep) * np.uint64(0x9E3779B9)) & _M32))
+    h = _mix32(h ^ ((e * np.uint64(0x85EBCA6B)) & _M32))
+    return _mix32(h ^ ((np.uint64(p) * np.uint64(0xC2B2AE35)) & _M32))
+
+
+def _d2_tree(diff):
+    """sum of squares over the coordinates by the kernel's tree: 64 lanes, halved six times"""
+    m, dim = diff.shape
+    v = np.zeros((m, 64), diff.dtype)
+    v[:, :dim] = diff * diff
+    w = 32
+    while w:
+        v = v[:, :w] + v[:, w:2 * w]
+        w >>= 1
+    return v[:, 0]
+
+
+def layout_host(row_ptr, col, weight, Y0, a, b, n_epochs: int = 500, seed: int = 42, first_epoch: int = 0, last_epoch=None,
+                dtype=np.float32, schedule=None, counts=None):
+    """The synchronous layout.  Returns (Y, schedule): schedule = (eps, epn, next, next_neg) to pass back in when a later call goes
+    on from `last_epoch`.  counts: an int array [E] that receives each edge's number of activations."""
+    f = np.dtype(dtype).type
+    row_ptr = np.asarray(row_ptr, np.int64)
+    col = np.asarray(col, np.int64)
+    n = len(row_ptr) - 1
+    Y = np.asarray(Y0).astype(dtype).copy()
+    dim = Y.shape[1]
+    last_epoch = n_epochs if last_epoch is None else last_epoch
+    eps, epn, nxt, nneg = schedule if schedule is not None else schedule_host(weight)
+    nxt, nneg = nxt.copy(), nneg.copy()
+    a32, b32 = np.float32(a), np.float32(b)
+    fa, fb = f(a32), f(b32)
+    c_att = f(np.float32(np.float32(-2) * a32) * b32)
+    c_rep = f(np.float32(2) * b32)
+    bm1 = f(b32 - np.float32(1))
+    head = np.repeat(np.arange(n), np.diff(row_ptr))
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        for ep in range(first_epoch, last_epoch):
+            alpha = f(np.float32(1) - np.float32(ep) / np.float32(n_epochs))
+            fep = np.float32(ep)
+            es = np.flatnonzero(nxt <= fep)                        # ascending edge id: grouped by head, in each vertex's order
+            if not len(es):
+                continue
+            n_neg = ((fep - nneg[es]) / epn[es]).astype(np.int32)
+            # every move of the epoch at once (all read the epoch's input), then added per vertex in order
+            per = 1 + np.maximum(n_neg, 0)
+            me = np.repeat(es, per)                                # the move's edge
+            mp = np.arange(len(me)) - np.repeat(np.cumsum(per) - per, per)       # 0 = attractive, p + 1 = the p-th repulsive
+            att = mp == 0
+            i = head[me]
+            other = np.where(att, col[me], (hash_host(seed, ep, me, np.maximum(mp - 1, 0).astype(np.uint64)) % np.uint64(n)).astype(np.int64))
+            diff = Y[i] - Y[other]
+            d2 = _d2_tree(diff)
+            den = fa * np.power(d2, fb) + f(1)
+            g = np.where(att, c_att * np.power(d2, bm1) / den, c_rep / ((f(0.001) + d2) * den))
+            g = np.where(d2 > 0, g, f(0))
+            t = np.clip(g[:, None] * diff, f(-4), f(4))
+            move = np.where(att[:, None], f(2) * t, t) * alpha
+            rank = np.arange(len(me)) - np.searchsorted(i, i, side="left")          # i is sorted: place within the vertex
+            order = np.argsort(rank, kind="stable")
+            cuts = np.searchsorted(rank[order], np.arange(int(rank.max()) + 2))
+            acc = np.zeros((n, dim), dtype)
+            for r in range(len(cuts) - 1):
+                sel = order[cuts[r]:cuts[r + 1]]                   # distinct vertices
+                acc[i[sel]] += move[sel]
+            nxt[es] = nxt[es] + eps[es]
+            nneg[es] = nneg[es] + n_neg.astype(np.float32) * epn[es]
+            if counts is not None:
+                counts[es] += 1
+            Y = Y + acc
+    return Y, (eps, epn, nxt, nneg)
+
+
+def umap_fit_host(X, n_components: int, n_neighbors: int = 15, seed: int = 42, n_epochs=None, dtype=np.float32, times=None):
+    """The whole restatement on a numpy array: {'embedding' fp32 [n, c], 'init_used', 'a', 'b', 'n_edges'}.  times: a dict that
+    receives seconds per step."""
+    X = np.ascontiguousarray(X, dtype=np.float32)
+    n, d = X.shape
+    _check(n, d, n_neighbors, n_components)
+    n_epochs = default_epochs(n) if n_epochs is None else int(n_epochs)
+    t = [time.perf_counter()]
+    a, b = find_ab_params()
+    idx, dist = knn_host(X, n_neighbors)
+    t.append(time.perf_counter())
+    G = fuzzy_graph_host(idx, dist, n_epochs)
+    t.append(time.perf_counter())
+    Y0, used = spectral_init_host(G["P"], n_components, seed)
+    t.append(time.perf_counter())
+    Y, _ = layout_host(G["row_ptr"], G["col"], G["weight"], Y0, a, b, n_epochs, seed, dtype=dtype)
+    t.append(time.perf_counter())
+    if times is not None:
+        times.update(zip(("knn", "graph", "init", "layout"), np.diff(t)))
+    return {"embedding": Y.astype(np.float32), "init_used": used, "a": a, "b": b, "n_edges": int(len(G["col"])), "init": Y0}
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the device path
+# ------------------------------------------------------------------------------------------------------------------------------
+def _fail(what, rc):
+    raise EngineError(f"{what}: {ERRORS.get(rc, 'error')} (code {rc})")
+
+
+def workspace_bytes(n: int, d: int, n_neighbors: int, n_components: int) -> int:
+    out = C.c_size_t(0)
+    rc = _lib().dm_umap_workspace_bytes(int(n), int(d), int(n_neighbors), int(n_components), C.byref(out))
+    if rc:
+        _fail("dm_umap_workspace_bytes", rc)
+    return out.value
+
+
+def _gpu_f32(X, what):
+    import torch
+    if not (isinstance(X, torch.Tensor) and X.is_cuda):
+        raise EngineError(f"{what}: a torch tensor on the GPU is required (the *_host functions are the numpy restatement)")
+    return X.to(torch.float32).contiguous()
+
+
+def _stream(dev):
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _work(work, need, dev):
+    import torch
+    return torch.empty(need, dtype=torch.uint8, device=dev) if work is None else work
+
+
+def knn(X, n_neighbors: int = 15, work=None):
+    """dm_umap_knn: (idx int32 [n, k], dist fp32 [n, k]) device tensors, bit-equal to `knn_host`."""
+    import torch
+    X = _gpu_f32(X, "umapfit.knn")
+    n, d = X.shape
+    dev = X.device
+    idx = torch.empty((n, n_neighbors), dtype=torch.int32, device=dev)
+    dist = torch.empty((n, n_neighbors), dtype=torch.float32, device=dev)
+    work = _work(work, workspace_bytes(n, d, n_neighbors, 1), dev)
+    with torch.cuda.device(dev):
+        rc = _lib().dm_umap_knn(_stream(dev), _p(X), n, d, int(n_neighbors), _p(work), work.numel(), _p(idx), _p(dist))
+    if rc:
+        _fail("dm_umap_knn", rc)
+    return idx, dist
+
+
+def fuzzy_graph(idx, dist, n_epochs: int = 500, work=None):
+    """dm_umap_graph: a dict of device tensors: rho, sigma [n], P [n, n], row_ptr [n + 1], col, weight (2 n k slots; the first
+    n_edges hold the edges), n_edges (int32 [])."""
+    import torch
+    dist = _gpu_f32(dist, "umapfit.fuzzy_graph")
+    dev = dist.device
+    idx = idx.to(device=dev, dtype=torch.int32).contiguous()
+    n, k = dist.shape
+    if idx.shape != dist.shape:
+        raise EngineError("umapfit.fuzzy_graph: idx and dist must both be [n, k]")
+    out = {"rho": torch.empty(n, dtype=torch.float32, device=dev), "sigma": torch.empty(n, dtype=torch.float32, device=dev),
+           "P": torch.empty((n, n), dtype=torch.float32, device=dev), "row_ptr": torch.empty(n + 1, dtype=torch.int32, device=dev),
+           "col": torch.empty(2 * n * k, dtype=torch.int32, device=dev), "weight": torch.empty(2 * n * k, dtype=torch.float32, device=dev),
+           "n_edges": torch.empty((), dtype=torch.int32, device=dev)}
+    work = _work(work, workspace_bytes(n, 1, k, 1), dev)
+    with torch.cuda.device(dev):
+        rc = _lib().dm_umap_graph(_stream(dev), _p(idx), _p(dist), n, k, int(n_epochs), _p(work), work.numel(), _p(out["rho"]),
+                                  _p(out["sigma"]), _p(out["P"]), _p(out["row_ptr"]), _p(out["col"]), _p(out["weight"]), _p(out["n_edges"]))
+    if rc:
+        _fail("dm_umap_graph", rc)
+    return out
+
+
+def layout(row_ptr, col, weight, n_edges: int, Y0, a: float, b: float, n_epochs: int = 500, seed: int = 42, first_epoch: int = 0,
+           last_epoch=None, work=None, n_neighbors: int = UMAP_MAX_NEIGHBORS):
+    """dm_umap_layout: epochs [first_epoch, last_epoch) enqueued back to back on the current stream; returns the new coordinates
+    (Y0 is left alone).  The schedule lives in `work`: first_epoch = 0 starts it, a later first_epoch goes on from the same `work`."""
+    import torch
+    Y = _gpu_f32(Y0, "umapfit.layout").clone()
+    dev = Y.device
+    n, dim = Y.shape
+    last_epoch = n_epochs if last_epoch is None else last_epoch
+    work = _work(work, workspace_bytes(n, 1, min(n_neighbors, max(n - 1, 2)), dim), dev)
+    with torch.cuda.device(dev):
+        rc = _lib().dm_umap_layout(_stream(dev), _p(row_ptr), _p(col), _p(weight), n, int(n_edges), dim, float(a), float(b),
+                                   int(n_epochs), int(seed) & 0x7FFFFFFF, int(first_epoch), int(last_epoch), _p(Y), _p(work), work.numel())
+    if rc:
+        _fail("dm_umap_layout", rc)
+    return Y
+
+
+def umap_fit(X, n_components: int, n_neighbors: int = 15, seed: int = 42, n_epochs=None, work=None, times=None):
+    """`umap.UMAP(n_components, n_neighbors).fit_transform(X)` by the rules of this module, on the device X lives on: {'embedding'
+    (device fp32 [n, c]), 'init_used', 'a', 'b', 'n_edges'}.  The graph comes to the host once for the spectral initialisation; the
+    epochs run without a host round trip.  Bit-reproducible.  times: a dict that receives seconds per step (it synchronises)."""
+    import torch
+    X = _gpu_f32(X, "umapfit.umap_fit")
+    if X.dim() != 2:
+        raise EngineError(f"umapfit.umap_fit: X must be [n, d], got {tuple(X.shape)}")
+    n, d = X.shape
+    dev = X.device
+    n_epochs = default_epochs(n) if n_epochs is None else int(n_epochs)
+    work = _work(work, workspace_bytes(n, d, n_neighbors, n_components), dev)
+
+    def mark():
+        if times is not None:
+            torch.cuda.synchronize(dev)
+        return time.perf_counter()
+
+    a, b = find_ab_params()
+    t = [mark()]
+    idx, dist = knn(X, n_neighbors, work)
+    t.append(mark())
+    G = fuzzy_graph(idx, dist, n_epochs, work)
+    n_edges = int(G["n_edges"])
+    t.append(mark())
+    Y0, used = spectral_init_host(G["P"].cpu().numpy(), n_components, seed)
+    Y0 = torch.from_numpy(Y0).to(dev)
+    t.append(mark())
+    Y = layout(G["row_ptr"], G["col"], G["weight"], n_edges, Y0, a, b, n_epochs, seed, work=work, n_neighbors=n_neighbors)
+    t.append(mark())
+    if times is not None:
+        times.update(zip(("knn", "graph", "init", "layout"), np.diff(t)))
+    return {"embedding": Y, "init_used": used, "a": a, "b": b, "n_edges": n_edges}
+
+
+def compress(X, n_groups: int, num_components: int = 32, n_neighbors: int = 15, seed: int = 42, n_epochs=None):
+    """`compress` of the parallel dataset (cluster.py:253-266): one fit per group of d // n_groups consecutive features (a country's
+    block), the embeddings side by side.  A GPU tensor stays on the device; a numpy array takes the restatement."""
+    import torch
+    on_gpu = isinstance(X, torch.Tensor) and X.is_cuda
+    if isinstance(X, torch.Tensor) and not on_gpu:
+        X = X.numpy()
+    d = X.shape[1]
+    group = d // int(n_groups)
+    if group < 1:
+        raise ValueError(f"compress: {n_groups} groups of {d} features")
+    parts = []
+    for i in range(0, d, group):
+        if on_gpu:
+            parts.append(umap_fit(X[:, i:i + group], num_components, n_neighbors, seed, n_epochs)["embedding"])
+        else:
+            parts.append(umap_fit_host(X[:, i:i + group], num_components, n_neighbors, seed, n_epochs)["embedding"])
+    return torch.cat(parts, dim=1) if on_gpu else np.hstack(parts)

@@ -336,6 +336,51 @@ int dm_cluster_rank(void* stream, const void* X, const void* X_rank_or_null, int
                     const float* centers, int k, const float* D_f32, int mode, int aggregate, void* work, size_t work_bytes,
                     int32_t* order, int32_t* cluster_of_rank, int32_t* offsets, float* aggregate_out, int32_t* n_nonempty);
 
+/* ---- UMAP projection for the clustering stage: exact kNN, fuzzy graph, synchronous layout (csrc/umap.hip) ----------
+ * Stream-plus-workspace functions (no engine handle), as the clustering ones.  The rules are stated in numpy in umapfit.py (a
+ * restatement of umap-learn 0.5.6 at the reference's settings; PARITY UNPINNED: not yet checked against umap-learn itself).
+ * `work`: device memory of at least dm_umap_workspace_bytes(n, d, n_neighbors, n_components) bytes; its contents do not matter,
+ * except that dm_umap_layout keeps the edge schedule there between a call with first_epoch = 0 and later calls that go on.
+ *
+ * dm_umap_knn: X fp32 [n][d] -> idx_out int32 [n][n_neighbors], dist_out fp32 [n][n_neighbors]: the n_neighbors nearest rows of every
+ * row, self included, ascending distance, ties to the lower index.  Squared distances are fp64 sums over ascending feature index
+ * with separate multiply and add; the distance is the fp64 sqrt rounded to fp32: bit-equal to the numpy restatement.
+ *
+ * dm_umap_graph: rho_out, sigma_out fp32 [n] (smooth_knn_dist: 64-step bisection in fp64, local_connectivity 1); dense_P_out fp32
+ * [n][n] = (A + A^T) - A o A^T of the memberships with entries below max(P) / n_epochs set to 0; the edge list = its non-zeros in
+ * row-major order: row_ptr_out int32 [n + 1], col_out int32 and weight_out fp32 with room for 2 n n_neighbors entries,
+ * n_edges_out int32 [1] (device).
+ *
+ * dm_umap_layout: epochs [first_epoch, last_epoch) of the synchronous layout on Y_inout fp32 [n][n_components], one launch per epoch,
+ * back to back on `stream`, no host synchronisation.  a, b: the curve parameters; seed: of the counter-based draw of the repulsive
+ * samples.  first_epoch = 0 starts the schedule (eps = max w / w, 5 negative samples per positive one); a later first_epoch goes on
+ * from the schedule the same `work` holds.  No atomics: bit-reproducible.
+ * Refused without a launch: a NULL pointer, n >= DM_UMAP_MAX_N, n_neighbors >= n, n_neighbors outside [2, DM_UMAP_MAX_NEIGHBORS],
+ * n_components outside [1, DM_UMAP_MAX_COMPONENTS], d < 1, n_epochs < 1 or an epoch range outside 0 <= first <= last <= n_epochs,
+ * a small workspace, n_edges outside [0, 2 n DM_UMAP_MAX_NEIGHBORS]. */
+#define DM_UMAP_MAX_N 4096
+#define DM_UMAP_MAX_NEIGHBORS 64
+#define DM_UMAP_MAX_COMPONENTS 64
+#define DM_UMAP_E_NULL 1
+#define DM_UMAP_E_N_LARGE 2
+#define DM_UMAP_E_NEIGHBORS_GE_N 3
+#define DM_UMAP_E_NEIGHBORS 4
+#define DM_UMAP_E_COMPONENTS 5
+#define DM_UMAP_E_D 6
+#define DM_UMAP_E_EPOCHS 7
+#define DM_UMAP_E_WORK 8
+#define DM_UMAP_E_EDGES 9
+#define DM_UMAP_E_HIP 10
+int dm_umap_workspace_bytes(int n, int d, int n_neighbors, int n_components, size_t* bytes_out);
+int dm_umap_knn(void* stream, const void* X, int n, int d, int n_neighbors, void* work, size_t work_bytes, int32_t* idx_out,
+                float* dist_out);
+int dm_umap_graph(void* stream, const int32_t* idx, const float* dist, int n, int n_neighbors, int n_epochs, void* work,
+                  size_t work_bytes, float* rho_out, float* sigma_out, float* dense_P_out, int32_t* row_ptr_out, int32_t* col_out,
+                  float* weight_out, int32_t* n_edges_out);
+int dm_umap_layout(void* stream, const int32_t* row_ptr, const int32_t* col, const float* weight, int n, int n_edges, int n_components,
+                   float a, float b, int n_epochs, int seed, int first_epoch, int last_epoch, float* Y_inout, void* work,
+                   size_t work_bytes);
+
 /* ---- X-ray evaluation: threshold counts of a heat-map against a ground-truth box (csrc/xray_eval.hip) -------------
  * The device half of `aucpr` and `mean_typicallity` (applications/xray/compute.py:263-284).  A stream-plus-workspace function
  * (no engine handle).  Row r of the descriptor table names a map [H][W] fp32 at maps_dev + map_offset (floats, any value; two
