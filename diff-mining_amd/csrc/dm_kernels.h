@@ -361,4 +361,23 @@ hipError_t launch_clip_attention(const f16* qkv, int n, int T, int heads, f16* o
 hipError_t launch_quick_gelu(f16* x, long long n, hipStream_t s);
 hipError_t launch_f16_to_f32(const f16* x, float* y, long long n, hipStream_t s);
 
+// ---- text-to-image sampling (sample.hip) ---------------------------------------------------------
+// out = one guided DDIM step of x [n] fp32 with eps [2n] fp16 (unconditional rows first) and a row (c0, c1, c2, c3) of the host's
+// coefficient table on the device, in torch's type promotion of the pipeline (the kernel's comment); in place when out == x
+hipError_t launch_cfg_ddim_step(const float* x, const f16* eps, float g, const float* coef, long long n, float* out, hipStream_t s);
+// latent NCHW fp32 [B,4,HW] -> post_quant_conv(rn16(latent / sf)) as NHWC rows [B*HW][ldc]: channels 0..3, zeros after; ldc % 8 == 0
+hipError_t launch_latent_prologue(const float* lat, const f16* w, const f16* b, int B, int HW, float sf, f16* out, int ldc, hipStream_t s);
+// block size of launch_gn_apply for (C, G): the slices its prologue cuts the partial sums into (norm.hip)
+int gn_apply_threads(int C, int G);
+// ab [N][2][C] fp32 = the per-channel affine (a, b) gn_apply_kernel forms from the partial sums of launch_gn_stats, bit for bit
+hipError_t launch_gn_affine(const double* partial, int N, int HW, int C, int G, float eps, const float* gamma, const float* beta, float* ab,
+                            hipStream_t s);
+// channels and GroupNorm groups of the decoder tail's input (`decoder.conv_norm_out` of the SDv1.5 VAE): the one definition the kernel
+// and the workspace formula of dm_op_decoder_tail share
+constexpr int DEC_TAIL_C = 128, DEC_TAIL_G = 32;
+// the VAE decoder's tail: conv_out (3x3, 128 -> 3; Wp [3][9*128] k = (tap, c), bias [3]) on silu(x * a + b) of X [B,H,W,128], never
+// written normalised -> raw [B,3,H,W] fp16 and / or img [B,H,W,3] uint8 (`VaeImageProcessor.postprocess`); C must be 128
+hipError_t launch_decoder_tail(const f16* X, const float* ab, const f16* Wp, const f16* bias, int B, int H, int W, int C, f16* raw, uint8_t* img,
+                               hipStream_t s);
+
 }  // namespace dm

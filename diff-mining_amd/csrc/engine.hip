@@ -167,8 +167,9 @@ void dm_engine_destroy(dm_engine* e) {
     if (!e) return;
     (void)hipSetDevice(e->device);
     (void)hipDeviceSynchronize();
-    for (f16* slab : {e->w_unet.slab, e->w_vae.slab, e->w_clip.slab}) if (slab) (void)hipFree(slab);
+    for (f16* slab : {e->w_unet.slab, e->w_vae.slab, e->w_vaed.slab, e->w_clip.slab}) if (slab) (void)hipFree(slab);
     if (e->arena_base) (void)hipFree(e->arena_base);
+    if (e->loop_buf) (void)hipFree(e->loop_buf);
     if (e->tile_ctr) (void)hipFree(e->tile_ctr);
     if (e->slot_scratch) (void)hipFree(e->slot_scratch);
     if (e->sin_table) (void)hipFree(e->sin_table);
@@ -209,6 +210,91 @@ int dm_vae_encode(dm_engine* e, const void* image_dev, const void* noise_dev, in
         A.moments = moments_f32_dev ? (float*)moments_f32_dev + (size_t)b0 * 8 * lpx : nullptr;
         DM_TRY(ensure_arena_for(e, s, {1, A.B, A.H, A.W, A.draws}, [&]() { return run_vae(e, A, s, true); }));
         DM_TRY(run_vae(e, A, s, false));
+    }
+    return 0;
+}
+
+/* `vae.decode(latents / scaling_factor).sample` under autocast and `VaeImageProcessor.postprocess` (finetuning/cars.py:235-255 through
+ * StableDiffusionPipeline.__call__): the batch in chunks by image area, nothing leaves the device in between */
+int dm_vae_decode(dm_engine* e, const void* latent_f32_dev, int batch, int h, int w, float scaling_factor, void* raw_f16_out_dev,
+                  void* image_u8_out_dev, void* stream) {
+    if (!e) return 1;
+    if (!e->w_vaed.ready) DM_FAIL(e, "dm_vae_decode: no VAE decoder weights (dm_engine_load_vae_decoder_weight / dm_engine_finalize_vae_decoder)");
+    if (!latent_f32_dev || (!raw_f16_out_dev && !image_u8_out_dev)) DM_FAIL(e, "dm_vae_decode: null argument (a latent and at least one output)");
+    if (batch <= 0 || h < 1 || w < 1 || h > 8192 || w > 8192) DM_FAIL(e, "dm_vae_decode: bad batch / latent size");
+    if (!(scaling_factor > 0.f)) DM_FAIL(e, "dm_vae_decode: scaling_factor must be positive");
+    DM_HIP(e, hipSetDevice(e->device));
+    hipStream_t s = (hipStream_t)stream;
+    const long long area = 64LL * h * w;
+    long long chunk = 4LL * 512 * 512 / area;                 // ~0.6 GB of fp16 activations per 512 x 512 image (a resnet at 512 x 512 x 256)
+    chunk = chunk < 1 ? 1 : chunk;
+    for (int b0 = 0; b0 < batch; b0 += (int)chunk) {
+        VaeDecArgs A{};
+        A.B = batch - b0 < chunk ? batch - b0 : (int)chunk; A.h = h; A.w = w; A.scaling = scaling_factor;
+        A.latent = (const float*)latent_f32_dev + (size_t)b0 * 4 * h * w;
+        A.raw = raw_f16_out_dev ? (f16*)raw_f16_out_dev + (size_t)b0 * 3 * area : nullptr;
+        A.image = image_u8_out_dev ? (uint8_t*)image_u8_out_dev + (size_t)b0 * 3 * area : nullptr;
+        DM_TRY(ensure_arena_for(e, s, {3, A.B, A.h, A.w}, [&]() { return run_vae_dec(e, A, s, true); }));
+        DM_TRY(run_vae_dec(e, A, s, false));
+    }
+    return 0;
+}
+
+/* n_steps guided DDIM updates on the device queue (StableDiffusionPipeline.__call__'s denoising loop with a DDIMScheduler, eta = 0):
+ * eps = UNet(cat([x, x]) rounded to fp16, t_i, prompt[slot]) at batch 2B — conv_in's fp32-latent path reads x through a row index, so
+ * the stacked copy is never made —, then x = cfg_ddim_step(x, eps, coef_i, g) in place.  Tables uploaded and the arena sized before the
+ * loop; no host synchronisation inside it. */
+int dm_sample_run(dm_engine* e, void* x_f32_dev, const int64_t* t_host, const float* coef_host, const int32_t* slot_dev, int B, int h, int w,
+                  int n_steps, float guidance_scale, void* stream) {
+    if (!e) return 1;
+    if (n_steps <= 0) DM_FAIL(e, "dm_sample_run: n_steps %d", n_steps);
+    if (!x_f32_dev || !t_host || !coef_host || !slot_dev) DM_FAIL(e, "dm_sample_run: null argument");
+    if (!e->finalized) DM_FAIL(e, "engine not finalized");
+    if (e->n_prompts <= 0) DM_FAIL(e, "dm_engine_set_prompts must be called first");
+    if (B <= 0 || h < 1 || w < 1) DM_FAIL(e, "dm_sample_run: bad batch / latent size");
+    if (2LL * B > max_chunk(h, w))
+        DM_FAIL(e, "dm_sample_run: 2 x %d samples over the %d of one U-Net run at %d x %d: a step's two halves share a run", B, max_chunk(h, w), h, w);
+    if ((long long)n_steps * 2 * B > (1LL << 24)) DM_FAIL(e, "dm_sample_run: n_steps %d", n_steps);
+    for (int i = 0; i < n_steps; ++i) if (t_host[i] < 0 || t_host[i] > 999) DM_FAIL(e, "dm_sample_run: timestep %lld out of range", (long long)t_host[i]);
+    DM_HIP(e, hipSetDevice(e->device));
+    hipStream_t s = (hipStream_t)stream;
+    const int N = 2 * B;
+    const size_t n = (size_t)B * 4 * h * w;
+    auto up256 = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t off_t = up256(2 * n * sizeof(f16)), off_c = off_t + up256((size_t)n_steps * N * sizeof(int64_t)),
+                 off_i = off_c + up256((size_t)n_steps * 4 * sizeof(float)), need = off_i + up256((size_t)N * sizeof(int32_t));
+    // the loop buffer is shared by every loop of this engine: an earlier loop queued on `s` may still read its tables, and the blocking
+    // copies run on the null stream, which a non-blocking `s` is not ordered with — so the queue drains first (once, before the loop)
+    DM_HIP(e, hipStreamSynchronize(s));
+    if (need > e->loop_cap) {
+        drop_graphs(e);
+        if (e->loop_buf) DM_HIP(e, hipFree(e->loop_buf));
+        e->loop_buf = nullptr; e->loop_cap = 0;
+        DM_MALLOC(e, &e->loop_buf, need);
+        e->loop_cap = need;
+    }
+    f16* eps = (f16*)e->loop_buf;
+    int64_t* t_dev = (int64_t*)(e->loop_buf + off_t);
+    float* coef = (float*)(e->loop_buf + off_c);
+    int32_t* xi = (int32_t*)(e->loop_buf + off_i);
+    {
+        std::vector<int64_t> tt((size_t)n_steps * N);
+        for (int i = 0; i < n_steps; ++i) for (int b = 0; b < N; ++b) tt[(size_t)i * N + b] = t_host[i];
+        std::vector<int32_t> idx((size_t)N);
+        for (int b = 0; b < N; ++b) idx[(size_t)b] = b % B;           // latent_model_input = cat([latents] * 2)
+        DM_HIP(e, hipMemcpy(t_dev, tt.data(), tt.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+        DM_HIP(e, hipMemcpy(coef, coef_host, (size_t)n_steps * 4 * sizeof(float), hipMemcpyHostToDevice));
+        DM_HIP(e, hipMemcpy(xi, idx.data(), idx.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
+    FwdArgs A{};
+    A.x = x_f32_dev; A.x_index = xi; A.t = t_dev; A.slots = slot_dev; A.latent_f32 = 1;
+    A.B = N; A.H = h; A.W = w; A.add_noise = false; A.up_ft_index = -1; A.pred = eps;
+    DM_TRY(ensure_arena(e, A, s));
+    for (int i = 0; i < n_steps; ++i) {
+        A.t = t_dev + (size_t)i * N;
+        DM_TRY(ensure_arena(e, A, s));              // a map lookup: the dry run and the allocation happened before the loop
+        DM_TRY(run_forward(e, A, s, false));
+        DM_HIP(e, launch_cfg_ddim_step((const float*)x_f32_dev, eps, guidance_scale, coef + 4 * i, (long long)n, (float*)x_f32_dev, s));
     }
     return 0;
 }
@@ -612,7 +698,7 @@ int dm_engine_reserve(dm_engine* e, int max_batch, int max_h, int max_w, int n_c
 
 int dm_engine_memory(dm_engine* e, size_t* weights_bytes, size_t* arena_bytes) {
     if (!e) return 1;
-    if (weights_bytes) *weights_bytes = e->w_unet.bytes + e->w_vae.bytes + e->w_clip.bytes;     // U-Net + optional VAE / CLIP slabs
+    if (weights_bytes) *weights_bytes = e->w_unet.bytes + e->w_vae.bytes + e->w_vaed.bytes + e->w_clip.bytes;     // U-Net + optional VAE / CLIP slabs
     if (arena_bytes) *arena_bytes = e->arena_cap;
     return 0;
 }

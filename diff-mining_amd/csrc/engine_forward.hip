@@ -1,5 +1,5 @@
-// engine_forward.hip — the fp16 engine's schedules: the op vocabulary (`Fwd`: arena tensors in, launches out) and the three
-// networks written in it, issued as hand-written gfx950 kernels on one HIP stream.
+// engine_forward.hip — the fp16 engine's schedules: the op vocabulary (`Fwd`: arena tensors in, launches out) and the four
+// networks written in it (U-Net, VAE encoder, VAE decoder, CLIP text tower), issued as hand-written gfx950 kernels on one HIP stream.
 //
 // Replaces, for diff-mining's hot path:  scheduler.add_noise + unet(...) + mse_loss at
 // diffmining/typicality/compute.py:99-101 and MyUNet2DConditionModel.forward at dift.py:24-169.
@@ -684,6 +684,71 @@ int dm::eng::run_vae(dm_engine* e, const VaeArgs& A, hipStream_t s, bool dry) {
     if (!dry) DM_HIP(e, launch_posterior(co.p, co.C, v.qw, v.qb, A.noise, A.B, A.draws, co.H * co.W, A.scaling, A.latent16, A.latent32,
                                          A.moments, s));
     F.free(co);
+    return 0;
+}
+
+// ---- VAE decoder: latent -> sample / image (`vae.decode(latents / scaling_factor)` + `VaeImageProcessor.postprocess` of the pipeline
+//      `Trainer.sample` runs under autocast, finetuning/cars.py:235-255) --------------------------------------------------------------
+int dm::eng::run_vae_dec(dm_engine* e, const VaeDecArgs& A, hipStream_t s, bool dry) {
+    Fwd F{e, s, dry};
+    F.res_eps = VAE_EPS;
+    const VaeDecW& v = e->vaed;
+    Tensor cur;
+    {
+        Tensor z;       // post_quant_conv's output at the head of 64-channel rows: conv_in is one 3x3 igemm with a single k step per tap
+        DM_TRY(F.alloc(&z, A.B, A.h, A.w, 64));
+        if (!dry) DM_HIP(e, launch_latent_prologue(A.latent, v.pqw, v.pqb, A.B, A.h * A.w, A.scaling, z.p, 64, s));
+        DM_TRY(F.igemm(v.conv_in, IG_CONV3, z, nullptr, A.h, A.w, nullptr, 0, nullptr, EPI_PLAIN, &cur));
+        F.free(z);
+    }
+    {
+        Tensor m0, n, qkv, a, m1, m2;
+        DM_TRY(F.resnet(v.mid[0], cur, nullptr, nullptr, &m0));
+        F.free(cur);
+        const int C = VBOC[VNB - 1], T = m0.H * m0.W;
+        DM_TRY(F.groupnorm(v.attn_gn, m0, nullptr, VAE_EPS, false, &n));
+        DM_TRY(F.dense(v.qkv, n, nullptr, nullptr, EPI_PLAIN, &qkv));
+        F.free(n);
+        DM_TRY(F.alloc(&a, m0.N, m0.H, m0.W, C));
+        if (!dry) {
+            DM_TRY(F.prof_begin(1, 4.0 * m0.N * (double)T * T * C));
+            DM_HIP(e, launch_attention512(qkv.p, qkv.p + C, qkv.p + 2 * C, a.p, m0.N, T, 3 * C, C, 1.0f / sqrtf((float)C), s));
+            DM_TRY(F.prof_end());
+        }
+        F.free(qkv);
+        DM_TRY(F.dense(v.o, a, nullptr, &m0, EPI_PLAIN, &m1));
+        F.free(a); F.free(m0);
+        DM_TRY(F.resnet(v.mid[1], m1, nullptr, nullptr, &m2));
+        F.free(m1);
+        cur = m2;
+    }
+    for (int i = 0; i < VNB; ++i) {
+        for (int j = 0; j < 3; ++j) {
+            Tensor r;
+            DM_TRY(F.resnet(v.up[i][j], cur, nullptr, nullptr, &r));
+            F.free(cur);
+            cur = r;
+        }
+        if (i != VNB - 1) {
+            Tensor up;      // Upsample2D: nearest 2x, then conv3x3 (the 64-channel-wave tiles: 512 / 256 output channels)
+            DM_TRY(F.igemm(v.us[i], IG_CONV3_UP, cur, nullptr, 2 * cur.H, 2 * cur.W, nullptr, 0, nullptr, EPI_PLAIN, &up));
+            F.free(cur);
+            cur = up;
+        }
+    }
+    // conv_norm_out + SiLU + conv_out + post-processing: the statistics pass as everywhere, then one kernel (sample.hip)
+    const int C = cur.C, HW = cur.H * cur.W;
+    if (C != v.norm_out.c) DM_FAIL(e, "vae decoder: channel mismatch %d vs %d", C, v.norm_out.c);
+    size_t poff, aoff; void *pp, *ap;
+    DM_TRY(F.alloc_raw((size_t)cur.N * gn_stats_chunks(HW) * GROUPS * 2 * sizeof(double), &poff, &pp));
+    DM_TRY(F.alloc_raw((size_t)cur.N * 2 * C * sizeof(float), &aoff, &ap));
+    if (!dry) {
+        DM_HIP(e, launch_gn_stats(cur.p, nullptr, cur.N, HW, C, C, GROUPS, (double*)pp, s));
+        DM_HIP(e, launch_gn_affine((const double*)pp, cur.N, HW, C, GROUPS, VAE_EPS, v.norm_out.g, v.norm_out.b, (float*)ap, s));
+        DM_HIP(e, launch_decoder_tail(cur.p, (const float*)ap, v.conv_out.w, v.conv_out.b, cur.N, cur.H, cur.W, C, A.raw, A.image, s));
+    }
+    F.free_raw(poff); F.free_raw(aoff);
+    F.free(cur);
     return 0;
 }
 

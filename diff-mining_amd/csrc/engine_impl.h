@@ -41,6 +41,16 @@ struct VaeW {
     const f16* qw = nullptr; const f16* qb = nullptr;    // quant_conv [8][8], [8]
 };
 
+// SDv1.5 VAE decoder (post_quant_conv, conv_in 4 -> 512, mid block, four up blocks of three resnets over 512/512/256/128)
+struct VaeDecW {
+    const f16* pqw = nullptr; const f16* pqb = nullptr;    // post_quant_conv [4][4], [4]
+    ConvW conv_in;                 // [512][9 * 64]: the four latent channels at the head of a 64-channel row, zeros after
+    ResW mid[2];
+    NormW attn_gn; ConvW qkv, o;
+    ResW up[sd15::VNB][3]; ConvW us[sd15::VNB - 1];
+    NormW norm_out; ConvW conv_out;  // conv_out [3][9 * 128], bias [3]
+};
+
 // CLIP ViT-L/14 text tower (12 pre-LN layers, hidden 768, 12 heads of 64, MLP 3072 quick_gelu)
 struct ClipLayerW { NormW ln1, ln2; ConvW qkv, o, fc1, fc2; };
 struct ClipW {
@@ -92,6 +102,13 @@ struct dm_engine {
     // optional VAE encoder (dm_engine_load_vae_weight / dm_engine_finalize_vae)
     dm::WeightSet<dm::f16> w_vae;
     dm::eng::VaeW vae;
+
+    // optional VAE decoder (dm_engine_load_vae_decoder_weight / dm_engine_finalize_vae_decoder): a weight set of its own
+    dm::WeightSet<dm::f16> w_vaed;
+    dm::eng::VaeDecW vaed;
+
+    // tables and the noise prediction of dm_sample_run (one loop at a time per engine: the buffer is shared by its loops)
+    char* loop_buf = nullptr; size_t loop_cap = 0;
 
     // prompt K/V cache
     int n_prompts = 0;
@@ -147,8 +164,14 @@ struct VaeArgs {
     f16* latent16; float* latent32; float* moments;
 };
 
+struct VaeDecArgs {
+    const float* latent; int B, h, w; float scaling;
+    f16* raw; uint8_t* image;     // [B,3,8h,8w] fp16 NCHW / [B,8h,8w,3] uint8 (either may be null)
+};
+
 int run_forward(dm_engine* e, const FwdArgs& A, hipStream_t s, bool dry);
 int run_vae(dm_engine* e, const VaeArgs& A, hipStream_t s, bool dry);
+int run_vae_dec(dm_engine* e, const VaeDecArgs& A, hipStream_t s, bool dry);
 int run_clip(dm_engine* e, const int32_t* ids, int n, f16* out16, float* out32, hipStream_t s, bool dry);
 
 }}  // namespace dm::eng

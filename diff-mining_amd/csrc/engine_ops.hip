@@ -1,8 +1,8 @@
 // engine_ops.hip — operator-level entry points (dm_op_*): single launches for the parity tests, none of which takes an engine handle.
 // The matrix kernels first (igemm tiles, attention routes, norms, conv_out), then the glue kernels around them, one entry per launch_*:
 // dm_op_time_gather, dm_op_silu, dm_op_im2col_in, dm_op_nhwc_to_nchw, dm_op_ensemble_mean (misc.hip), dm_op_im2col_rgb, dm_op_posterior
-// (vae.hip), dm_op_clip_embed, dm_op_clip_attention, dm_op_quick_gelu, dm_op_f16_to_f32 (clip.hip).  Their fp32 counterparts are the
-// dm_f32_op_* of unet_f32.hip.
+// (vae.hip), dm_op_clip_embed, dm_op_clip_attention, dm_op_quick_gelu, dm_op_f16_to_f32 (clip.hip), dm_op_cfg_ddim_step, dm_op_latent_prologue,
+// dm_op_decoder_tail (sample.hip).  Their fp32 counterparts are the dm_f32_op_* of unet_f32.hip.
 #include "../../include/dm_engine.h"
 #include "dm_kernels.h"
 
@@ -259,6 +259,44 @@ int dm_op_quick_gelu(void* stream, void* x, int64_t n) {
 int dm_op_f16_to_f32(void* stream, const void* x, float* y, int64_t n) {
     if (!x || !y || n <= 0) return 1;
     return launch_f16_to_f32((const f16*)x, y, (long long)n, (hipStream_t)stream) == hipSuccess ? 0 : 1;
+}
+
+// ---- the kernels of text-to-image sampling (sample.hip), one by one
+int dm_op_cfg_ddim_step(void* stream, const float* x_f32, const void* eps_f16, const float* coef4_dev, float g, int64_t n, float* out_f32) {
+    if (!x_f32 || !eps_f16 || !coef4_dev || !out_f32 || n <= 0) return 1;
+    return launch_cfg_ddim_step(x_f32, (const f16*)eps_f16, g, coef4_dev, (long long)n, out_f32, (hipStream_t)stream) == hipSuccess ? 0 : 1;
+}
+
+int dm_op_latent_prologue(void* stream, const float* latent_f32, const void* w_f16, const void* b_f16, int B, int HW, float scaling_factor,
+                          void* out_f16, int ldc) {
+    if (!latent_f32 || !w_f16 || !b_f16 || !out_f16 || B <= 0 || HW <= 0) return 1;
+    return launch_latent_prologue(latent_f32, (const f16*)w_f16, (const f16*)b_f16, B, HW, scaling_factor, (f16*)out_f16, ldc,
+                                  (hipStream_t)stream) == hipSuccess ? 0 : 1;
+}
+
+// bytes of the statistics' partial sums [B][chunks][G][2] fp64, which the affine [B][2][C] fp32 follows
+static size_t decoder_tail_partial_bytes(int B, int H, int W) {
+    return (size_t)B * gn_stats_chunks(H * W) * DEC_TAIL_G * 2 * sizeof(double);
+}
+
+size_t dm_op_decoder_tail_workspace_bytes(int B, int H, int W) {
+    if (B <= 0 || H <= 0 || W <= 0 || (long long)H * W > 0x7fffffffLL) return 0;
+    return decoder_tail_partial_bytes(B, H, W) + (size_t)B * 2 * DEC_TAIL_C * sizeof(float);
+}
+
+int dm_op_decoder_tail(void* stream, const void* X, const float* gamma, const float* beta, const void* Wp, const void* bias, int B, int H, int W,
+                       float eps, void* work, size_t work_bytes, void* raw_f16_out, void* image_u8_out) {
+    if (!X || !gamma || !beta || !Wp || !bias || !work || (!raw_f16_out && !image_u8_out)) return 1;
+    const size_t need = dm_op_decoder_tail_workspace_bytes(B, H, W);
+    if (need == 0 || work_bytes < need || ((uintptr_t)work & 7)) return 1;
+    hipStream_t s = (hipStream_t)stream;
+    double* partial = (double*)work;
+    float* ab = (float*)((char*)work + decoder_tail_partial_bytes(B, H, W));
+    hipError_t r = launch_gn_stats((const f16*)X, nullptr, B, H * W, DEC_TAIL_C, DEC_TAIL_C, DEC_TAIL_G, partial, s);
+    if (r == hipSuccess) r = launch_gn_affine(partial, B, H * W, DEC_TAIL_C, DEC_TAIL_G, eps, gamma, beta, ab, s);
+    if (r == hipSuccess) r = launch_decoder_tail((const f16*)X, ab, (const f16*)Wp, (const f16*)bias, B, H, W, DEC_TAIL_C, (f16*)raw_f16_out,
+                                                 (uint8_t*)image_u8_out, s);
+    return r == hipSuccess ? 0 : 1;
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // engine_pack.hip — weight intake of the fp16 engine: the staged state dicts (diffusers names) packed into the MFMA-friendly HBM
-// layout of one slab per network (U-Net, VAE encoder, CLIP text tower), and the scheduler / sinusoid tables.
+// layout of one slab per network (U-Net, VAE encoder, VAE decoder, CLIP text tower), and the scheduler / sinusoid tables.
 #include "engine_impl.h"
 
 #include <cmath>
@@ -593,6 +593,76 @@ int dm_engine_finalize_vae(dm_engine* e) {
         if (i != VNB - 1) rebase_conv(v.ds[i], base);
     }
     rebase_res(v.mid[0], base); rebase_res(v.mid[1], base);
+    return 0;
+}
+
+int dm_engine_load_vae_decoder_weight(dm_engine* e, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim) {
+    if (!e || !name || !host_ptr || !shape) return 1;
+    if (e->w_vaed.ready) DM_FAIL(e, "load_vae_decoder_weight after finalize_vae_decoder");
+    std::string nm(name);
+    if (nm.rfind("vae.", 0) == 0) nm = nm.substr(4);
+    if (nm.rfind("encoder.", 0) == 0 || nm.rfind("quant_conv.", 0) == 0) return 0;          // the encoder's half
+    // the encoder loader's name rules: pre-0.15 attention names, [C, C, 1, 1] projections staged as [C, C]
+    static const char* legacy[4][2] = {{".query.", ".to_q."}, {".key.", ".to_k."}, {".value.", ".to_v."}, {".proj_attn.", ".to_out.0."}};
+    for (auto& l : legacy) { const size_t at = nm.find(l[0]); if (at != std::string::npos) nm.replace(at, strlen(l[0]), l[1]); }
+    if (nm.find(".attentions.0.to_") != std::string::npos && ndim == 4 && shape[2] == 1 && shape[3] == 1) ndim = 2;
+    return dm::stage_tensor(e->w_vaed.host, nm, host_ptr, dtype, shape, ndim, e->err);
+}
+
+int dm_engine_finalize_vae_decoder(dm_engine* e) {
+    if (!e) return 1;
+    if (e->w_vaed.ready) return 0;
+    DM_HIP(e, hipSetDevice(e->device));
+    Packer P{e, e->w_vaed};
+    VaeDecW& v = e->vaed;
+    const int C = VBOC[VNB - 1];
+    {
+        HostTensor* qw = P.get("post_quant_conv.weight", {4, 4, 1, 1});
+        HostTensor* qb = P.get("post_quant_conv.bias", {4});
+        HostTensor* w = P.get("decoder.conv_in.weight", {C, 4, 3, 3});
+        if (!qw || !qb || !w) return 1;
+        v.pqw = as_ptr(P.put(qw->data.data(), 16 * 2));
+        v.pqb = as_ptr(P.put(qb->data.data(), 4 * 2));
+        // conv_in as a 3x3 igemm over 64-channel rows: [C][tap * 64 + c], c < 4 (the latent prologue writes zeros into the other 60)
+        std::vector<f16> pk((size_t)C * 9 * 64, (f16)0.f);
+        for (int co = 0; co < C; ++co)
+            for (int ci = 0; ci < 4; ++ci)
+                for (int tap = 0; tap < 9; ++tap) pk[((size_t)co * 9 + tap) * 64 + ci] = w->data[((size_t)co * 4 + ci) * 9 + tap];
+        v.conv_in.w = as_ptr(P.put(pk.data(), pk.size() * 2));
+        v.conv_in.cin = 64; v.conv_in.cout = C; v.conv_in.k = 3;
+        DM_TRY(pack_bias(P, "decoder.conv_in", C, &v.conv_in.b));
+    }
+    DM_TRY(pack_vae_resnet(P, "decoder.mid_block.resnets.0", C, C, &v.mid[0]));
+    {
+        const std::string a = "decoder.mid_block.attentions.0";
+        DM_TRY(pack_norm(P, a + ".group_norm", C, &v.attn_gn));
+        DM_TRY(pack_stack(P, {a + ".to_q", a + ".to_k", a + ".to_v"}, C, C, &v.qkv));
+        std::vector<f16> qb;
+        DM_TRY(stack_bias(P, {a + ".to_q", a + ".to_k", a + ".to_v"}, C, &qb));
+        v.qkv.b = as_ptr(P.put(qb.data(), qb.size() * 2));
+        DM_TRY(pack_dense(P, a + ".to_out.0", C, C, false, true, &v.o));
+    }
+    DM_TRY(pack_vae_resnet(P, "decoder.mid_block.resnets.1", C, C, &v.mid[1]));
+    int cin = C;
+    for (int i = 0; i < VNB; ++i) {
+        const int cout = VBOC[VNB - 1 - i];
+        const std::string bn = "decoder.up_blocks." + std::to_string(i);
+        for (int j = 0; j < 3; ++j) DM_TRY(pack_vae_resnet(P, bn + ".resnets." + std::to_string(j), j == 0 ? cin : cout, cout, &v.up[i][j]));
+        if (i != VNB - 1) DM_TRY(pack_conv3(P, bn + ".upsamplers.0.conv", cout, cout, &v.us[i]));
+        cin = cout;
+    }
+    DM_TRY(pack_norm(P, "decoder.conv_norm_out", VBOC[0], &v.norm_out));
+    DM_TRY(pack_conv3(P, "decoder.conv_out", 3, VBOC[0], &v.conv_out));         // [3][tap * 128 + c]: the tail's A operand rows
+    DM_TRY(P.finish("VAE decoder", 140));
+    char* base = (char*)e->w_vaed.slab;
+    rebase(v.pqw, base); rebase(v.pqb, base);
+    rebase_conv(v.conv_in, base); rebase_conv(v.qkv, base); rebase_conv(v.o, base); rebase_conv(v.conv_out, base);
+    rebase_norm(v.attn_gn, base); rebase_norm(v.norm_out, base);
+    rebase_res(v.mid[0], base); rebase_res(v.mid[1], base);
+    for (int i = 0; i < VNB; ++i) {
+        for (int j = 0; j < 3; ++j) rebase_res(v.up[i][j], base);
+        if (i != VNB - 1) rebase_conv(v.us[i], base);
+    }
     return 0;
 }
 

@@ -455,6 +455,11 @@ static void gn_geometry(int C, int* R, int* threads) {
     *R = r; *threads = ((cols * r + 63) / 64) * 64;
 }
 
+int gn_apply_threads(int C, int G) {
+    int R, threads; gn_geometry(C, &R, &threads);
+    return threads < G ? 64 : threads;
+}
+
 hipError_t launch_gn_stats(const f16* X, const f16* X2, int N, int HW, int C, int C1, int G, double* partial, hipStream_t s) {
     if (C % 8 || C % G || C1 % 8 || G > 64) return hipErrorInvalidValue;
     int R, threads; gn_geometry(C, &R, &threads);
@@ -489,7 +494,7 @@ hipError_t launch_gn_apply(const f16* X, const f16* X2, int N, int HW, int C, in
                            const float* beta, const double* partial, int silu, f16* Y, hipStream_t s, int chunks) {
     if (C % 8 || C % G || C1 % 8 || G > 64) return hipErrorInvalidValue;
     int R, threads; gn_geometry(C, &R, &threads);
-    if (threads < G) threads = 64;
+    threads = gn_apply_threads(C, G);
     // enough blocks to fill the chip, few enough that the per-block statistics prologue amortises
     int ppb = 256;
     while (ppb > 8 && (long long)N * ((HW + ppb - 1) / ppb) < 2048) ppb >>= 1;

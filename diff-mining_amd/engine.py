@@ -81,6 +81,10 @@ SIGNATURES = {
     "dm_engine_load_vae_weight": (_i32, _WEIGHT),
     "dm_engine_finalize_vae": (_i32, [_vp]),
     "dm_vae_encode": (_i32, [_vp, _vp, _vp] + [_i32] * 4 + [_f32] + [_vp] * 4),
+    "dm_engine_load_vae_decoder_weight": (_i32, _WEIGHT),
+    "dm_engine_finalize_vae_decoder": (_i32, [_vp]),
+    "dm_vae_decode": (_i32, [_vp, _vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp]),
+    "dm_sample_run": (_i32, [_vp] * 5 + [_i32] * 4 + [_f32, _vp]),
     "dm_engine_load_clip_weight": (_i32, _WEIGHT),
     "dm_engine_finalize_clip": (_i32, [_vp]),
     "dm_clip_encode": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp]),
@@ -122,6 +126,10 @@ SIGNATURES = {
     "dm_op_clip_attention": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp]),
     "dm_op_quick_gelu": (_i32, [_vp, _vp, _i64]),
     "dm_op_f16_to_f32": (_i32, [_vp, _vp, _vp, _i64]),
+    "dm_op_cfg_ddim_step": (_i32, [_vp] * 4 + [_f32, _i64, _vp]),
+    "dm_op_latent_prologue": (_i32, [_vp] * 4 + [_i32, _i32, _f32, _vp, _i32]),
+    "dm_op_decoder_tail_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "dm_op_decoder_tail": (_i32, [_vp] * 6 + [_i32] * 3 + [_f32, _vp, _sz, _vp, _vp]),
     "dm_f32_create": (_i32, [_i32, _pvp]),
     "dm_f32_destroy": (None, [_vp]),
     "dm_f32_last_error": (_cp, [_vp]),
@@ -561,6 +569,56 @@ class UNetEngine(_EngineBase):
                     "dm_vae_encode")
         return (lat, mom) if return_moments else lat
 
+    # -- text-to-image sampling (finetuning/cars.py:235-255; see diff_mining_amd.sample) ---------------------------------------------
+    def load_vae_decoder_state_dict(self, sd: Dict[str, "np.ndarray"]):
+        """sd: `AutoencoderKL.state_dict()`; only `post_quant_conv.*` and `decoder.*` are used (140 tensors, 49,490,199 parameters), the
+        encoder half is ignored.  A weight set of its own, beside `load_vae_state_dict`.  An incomplete set is refused here, by name,
+        before anything is staged."""
+        from .vae_spec import canonical_vae_decoder_name, vae_decoder_tensor_spec
+        have = {canonical_vae_decoder_name(k) for k in sd}
+        missing = [n for n, _ in vae_decoder_tensor_spec() if n not in have]
+        if missing:
+            raise EngineError(f"load_vae_decoder_state_dict: {len(missing)} of the 140 decoder tensors are missing (first: {missing[0]})")
+        self._load("_vae_decoder", sd)
+        self._vae_decoder_ready = True
+
+    def load_vae_decoder_safetensors(self, path: str):
+        """`vae/diffusion_pytorch_model.safetensors` of a diffusers pipeline directory: its decoder half."""
+        from safetensors.numpy import load_file
+        self.load_vae_decoder_state_dict(load_file(path))
+
+    def vae_decode(self, latent, raw: bool = False, want: str = "u8", scaling_factor: float = 0.18215):
+        """`vae.decode(latent / scaling_factor).sample` of the pipeline under autocast.  latent [B,4,h,w] (taken as fp32).  want "u8":
+        [B,8h,8w,3] uint8 = `VaeImageProcessor.postprocess` ((x / 2 + 0.5).clamp(0, 1) in fp16, * 255, rounded half to even); "f16":
+        [B,3,8h,8w] fp16, the sample itself; raw=True: the pair (sample, image).  On the device."""
+        torch = self._torch
+        assert want in ("u8", "f16"), want
+        latent = latent.to(self.device, torch.float32).contiguous()
+        B, c, h, w = latent.shape
+        assert c == 4, latent.shape
+        f = torch.empty(B, 3, 8 * h, 8 * w, dtype=torch.float16, device=self.device) if (raw or want == "f16") else None
+        u = torch.empty(B, 8 * h, 8 * w, 3, dtype=torch.uint8, device=self.device) if (raw or want == "u8") else None
+        self._check(self.lib.dm_vae_decode(self._h, _p(latent), B, h, w, float(np.float32(scaling_factor)), _p(f), _p(u), self._stream()),
+                    "dm_vae_decode")
+        return (f, u) if raw else (u if want == "u8" else f)
+
+    def sample_run(self, x, timesteps, coef, slots, guidance_scale: float = 7.5):
+        """`len(timesteps)` guided DDIM updates of x [B,4,h,w] fp32 on the device queue (dm_sample_run): per step eps = unet(cat([x, x]), t_i,
+        slots) at batch 2B, then the guided update with row i of `coef` (`sample.sample_coefficients`).  slots [2B]: the B unconditional
+        prompts, then the B conditional ones.  Returns the new x (fp32, a new tensor)."""
+        torch = self._torch
+        x = x.to(self.device, torch.float32).contiguous().clone()
+        B, c, h, w = x.shape
+        assert c == 4, x.shape
+        t = np.ascontiguousarray(np.asarray(timesteps, dtype=np.int64).reshape(-1))
+        cf = np.ascontiguousarray(np.asarray(coef, dtype=np.float32).reshape(-1, 4))
+        if cf.shape[0] != t.shape[0]:
+            raise ValueError(f"{t.shape[0]} timesteps but {cf.shape[0]} coefficient rows")
+        s = self._slots(slots, 2 * B)
+        self._check(self.lib.dm_sample_run(self._h, _p(x), t.ctypes.data_as(C.c_void_p), cf.ctypes.data_as(C.c_void_p), _p(s), B, h, w,
+                                           int(t.shape[0]), float(guidance_scale), self._stream()), "dm_sample_run")
+        return x
+
     def resize_lanczos(self, images, out_w: int, out_h: int, resample: bool = True):
         """`PIL.Image.resize((out_w, out_h), LANCZOS)` + `to_tensor(x) * 2 - 1` (D.rescale + D.load_image, compute.py:126-132,
         165-180) of uint8 HWC RGB arrays of any sizes in ONE launch of dm_resize_lanczos -> [n,3,out_h,out_w] fp32 on the
@@ -604,9 +662,10 @@ class UNetEngine(_EngineBase):
                 raise EngineError(f"{cfg}: {e}") from None
         self.load_state_dict(load_file(path))
 
-    def load_pipeline_dir(self, model_path: str, vae: bool = True, text_encoder: bool = True):
+    def load_pipeline_dir(self, model_path: str, vae: bool = True, text_encoder: bool = True, vae_decoder: bool = False):
         """`StableDiffusionPipeline.from_pretrained(model_path)` as far as the path needs it (compute.py:65-73): the
-        U-Net (config.json checked), and when present the VAE encoder and the CLIP text tower of the directory."""
+        U-Net (config.json checked), and when present the VAE encoder and the CLIP text tower of the directory; with
+        `vae_decoder=True` also the VAE's decoder half (`sample.sample`)."""
         unet = os.path.join(model_path, "unet", "diffusion_pytorch_model.safetensors")
         if not os.path.isfile(unet):
             raise EngineError(f"{unet} not found (a diffusers pipeline directory with safetensors weights is expected)")
@@ -614,6 +673,8 @@ class UNetEngine(_EngineBase):
         v = os.path.join(model_path, "vae", "diffusion_pytorch_model.safetensors")
         if vae and os.path.isfile(v):
             self.load_vae_safetensors(v)
+        if vae_decoder and os.path.isfile(v):
+            self.load_vae_decoder_safetensors(v)
         c = os.path.join(model_path, "text_encoder", "model.safetensors")
         if text_encoder and os.path.isfile(c):
             from safetensors.numpy import load_file

@@ -654,6 +654,39 @@ int dm_vae_encode(dm_engine* e, const void* image_dev, const void* noise_dev, in
                   int H, int W, float scaling_factor, void* latent_f16_dev, void* latent_f32_dev,
                   void* moments_f32_dev, void* stream);
 
+/* ---- Text-to-image sampling: guided DDIM loop and VAE decoder (csrc/sample.hip) ------------------------------------
+ * Replaces `Trainer.sample` (finetuning/cars.py:235-255; the same call in ftt/geo/places and xray/finetune.py:228):
+ * `StableDiffusionPipeline(prompt, negative_prompt, latents, num_inference_steps=50, eta=0.0, guidance_scale=7.5)` on a DDIMScheduler
+ * under `torch.autocast('cuda')` with fp32 latents (`--mixed_precision no`), from the initial latents to uint8 images with nothing
+ * leaving the device in between.  Optional: an engine without decoder weights still scores, and the loop needs only the U-Net.
+ * Not covered: the `ddim=False` arm (the trainer's DDPM scheduler), fp16 latents (`--mixed_precision fp16`), the fp32 net.
+ *
+ * dm_engine_load_vae_decoder_weight: one tensor of `AutoencoderKL.state_dict()` by its diffusers name (`post_quant_conv.*`,
+ *   `decoder.*`; the name rules of dm_engine_load_vae_weight: `vae.` prefix, pre-0.15 attention names and shapes; `encoder.*` and
+ *   `quant_conv.*` are accepted and ignored).  A weight set of its own beside the encoder's.  Host memory, DM_F16 or DM_F32.
+ * dm_engine_finalize_vae_decoder: checks the 140 decoder tensors (49,490,199 parameters), packs, uploads; an incomplete set is refused.
+ * dm_vae_decode: latent [batch,4,h,w] fp32 NCHW -> `vae.decode(latent / scaling_factor).sample` in the arithmetic of dm_vae_encode
+ *   (fp16 tensors, fp32 GroupNorm statistics): z = the correctly rounded fp32 quotient, rounded to fp16; post_quant_conv, conv_in, the mid
+ *   block, four up blocks of three resnets (512, 512, 256, 128 channels, nearest-2x up-samplers between them); conv_norm_out + SiLU +
+ *   conv_out + post-processing in one kernel that never writes the normalised [batch,8h,8w,128] tensor.  Outputs (each optional, at
+ *   least one): raw [batch,3,8h,8w] fp16 NCHW = the sample; image [batch,8h,8w,3] uint8 = `VaeImageProcessor.postprocess`:
+ *   (raw / 2 + 0.5).clamp(0, 1) in fp16, each operation rounded, widened to fp32, * 255, rounded half to even (NaN -> 0).  The batch is
+ *   cut into chunks by image area (4 images of 512 x 512); a sample's bits do not depend on the batch.
+ * dm_sample_run: n_steps guided DDIM updates of x [B,4,h,w] fp32 IN PLACE on the device queue.  t_host [n_steps] int64 (0..999) and
+ *   coef_host [n_steps][4] fp32 = (sqrt(a_prev), sqrt(1 - a_t), sqrt(a_t), sqrt(1 - a_prev)) per step are HOST tables (the scheduler's
+ *   0-dim fp32 tensors; the device computes no square root), uploaded once before the loop; slot_dev [2B] int32 on the device = the
+ *   registered prompts of the B unconditional rows, then of the B conditional rows (`torch.cat([negative, prompt])`).  Per step:
+ *   eps = UNet(cat([x, x]) rounded to fp16, t_i, slots) at batch 2B, then dm_op_cfg_ddim_step.  No host synchronisation inside the loop;
+ *   the call waits for work queued on `stream` before its blocking uploads, and an engine runs its loops on one stream at a time (they
+ *   share one table buffer).  Refused without a launch: n_steps <= 0, a timestep outside 0..999, 2B beyond one U-Net run (DM_CHUNK
+ *   samples of 64 x 64, scaled by area), no prompts registered.  A sample's bits do not depend on B.                                    */
+int dm_engine_load_vae_decoder_weight(dm_engine* e, const char* name, const void* host_ptr, int dtype, const int64_t* shape, int ndim);
+int dm_engine_finalize_vae_decoder(dm_engine* e);
+int dm_vae_decode(dm_engine* e, const void* latent_f32_dev, int batch, int h, int w, float scaling_factor, void* raw_f16_out_dev,
+                  void* image_u8_out_dev, void* stream);
+int dm_sample_run(dm_engine* e, void* x_f32_dev, const int64_t* t_host, const float* coef_host, const int32_t* slot_dev, int B, int h, int w,
+                  int n_steps, float guidance_scale, void* stream);
+
 /* ---- CLIP text tower ----------------------------------------------------------
  * Replaces `self.clip(tokens.to(self.device))[0]` of `CategoryFeatures.embed`
  * (diffmining/typicality/compute.py:51; the pipeline's `text_encoder`, compute.py:68): CLIP ViT-L/14 text
@@ -875,6 +908,26 @@ int dm_op_clip_embed(void* stream, const int32_t* ids, const void* tok, const vo
 int dm_op_clip_attention(void* stream, const void* qkv, int n, int T, int heads, void* out);
 int dm_op_quick_gelu(void* stream, void* x, int64_t n);
 int dm_op_f16_to_f32(void* stream, const void* x, float* y, int64_t n);
+
+/* The kernels of text-to-image sampling (csrc/sample.hip), one by one.  Each returns 1 WITHOUT launching for a null required pointer, a
+ * non-positive extent or the precondition named with it.
+ *   cfg_ddim_step    out [n] fp32 = one guided DDIM step of x [n] fp32 with eps [2n] fp16 (the n unconditional values first) and the row
+ *                    coef4_dev = (c0, c1, c2, c3) on the device, in torch's type promotion of StableDiffusionPipeline.__call__ +
+ *                    DDIMScheduler.step: e = rn16(u + rn16(g * rn16(c - u))); x0 = (x - rn16(c1 * e)) / c2; out = c0 * x0 + rn16(c3 * e) —
+ *                    every fp16-tensor op an fp32 operation rounded to fp16, the scalars at fp32 precision, no FMA.  out may be x
+ *   latent_prologue  latent NCHW fp32 [B,4,HW] -> out NHWC fp16 [B*HW][ldc]: channels 0..3 = post_quant_conv (w [4][4], b [4] fp16) of
+ *                    rn16(latent / scaling_factor), the four products added in fp32 in input-channel order, then the bias, one rounding;
+ *                    channels 4..ldc-1 zero.  ldc % 8 == 0, ldc >= 8, scaling_factor > 0
+ *   decoder_tail     X [B,H,W,128] fp16 NHWC -> conv_out (Wp [3][9*128] fp16, k = (tap, channel); bias [3] fp16) of
+ *                    silu(GroupNorm_32(X; gamma, beta fp32, eps)) with the normalised tensor never written: raw [B,3,H,W] fp16 NCHW and / or
+ *                    image [B,H,W,3] uint8 as dm_vae_decode writes them (at least one).  work: dm_op_decoder_tail_workspace_bytes(B, H, W)
+ *                    bytes on the device, 8-byte aligned (the statistics).  B <= 65535 */
+int dm_op_cfg_ddim_step(void* stream, const float* x_f32, const void* eps_f16, const float* coef4_dev, float g, int64_t n, float* out_f32);
+int dm_op_latent_prologue(void* stream, const float* latent_f32, const void* w_f16, const void* b_f16, int B, int HW, float scaling_factor,
+                          void* out_f16, int ldc);
+size_t dm_op_decoder_tail_workspace_bytes(int B, int H, int W);
+int dm_op_decoder_tail(void* stream, const void* X, const float* gamma, const float* beta, const void* Wp, const void* bias, int B, int H, int W,
+                       float eps, void* work, size_t work_bytes, void* raw_f16_out, void* image_u8_out);
 
 /* ---- fp32 U-Net: the arithmetic of the reference's DIFT featuriser ------------------------------------------------------
  * `SDFeaturizer.__init__` (diffmining/typicality/dift.py:197-199) loads the pipeline WITHOUT torch_dtype and `forward`
