@@ -310,7 +310,8 @@ def rank_clusters(X, labels, centers, D, aggregate: str = "median", order_by: st
 
 
 def cluster_patches(features, D, num_clusters: int = 32, aggregate: str = "median", seed: int = 10, order_by: str = "centroid",
-                    rank_features=None, max_iter: int = 300, tol: float = 1e-4, *, project=None, project_seed: int = 42):
+                    rank_features=None, max_iter: int = 300, tol: float = 1e-4, *, project=None, project_seed: int = 42,
+                    project_solver: str = "host"):
     """`cluster()` of the reference as arrays: fit, then rank.  On a GPU tensor both run on the device and only the small result
     comes back; a numpy array (or a CPU tensor) takes the numpy restatement.  Returns a dict: 'clusters' = a list, best first, of
     {'cluster': id, 'rows': row ids in order (int32), 'aggregate': float}, plus 'labels', 'centers', 'seed_index', 'inertia',
@@ -319,8 +320,8 @@ def cluster_patches(features, D, num_clusters: int = 32, aggregate: str = "media
     project: None = no projection.  An int c = the main stage's project=True with `umap.UMAP(n_components=c)` (typicality/cluster.py:
     314-317; the reference uses 5): k-means and the ranking both run on the embedding.  ('groups', G, c) = the parallel dataset's
     cluster() (cluster.py:268-289): k-means on `umapfit.compress(features, G, c)`, members ranked with order_by='farthest' on the
-    original features.  project_seed seeds the projection (umap-learn is unseeded at both call sites).  With a projection the dict
-    also holds 'embedding'."""
+    original features.  project_seed seeds the projection (umap-learn is unseeded at both call sites).  project_solver: 'host' or 'device', `umapfit.umap_fit`'s
+    init_solver (where the spectral initialisation runs; a numpy input ignores it).  With a projection the dict also holds 'embedding'."""
     import torch
     embedding = None
     if project is not None:
@@ -328,13 +329,15 @@ def cluster_patches(features, D, num_clusters: int = 32, aggregate: str = "media
         if isinstance(project, (tuple, list)):
             if len(project) != 3 or project[0] != "groups":
                 raise ValueError(f"cluster_patches: project {project!r} (None, an int, or ('groups', G, n_components))")
-            embedding = umapfit.compress(features, int(project[1]), int(project[2]), seed=project_seed)
+            embedding = umapfit.compress(features, int(project[1]), int(project[2]), seed=project_seed, init_solver=project_solver)
             features, rank_features, order_by = embedding, features if rank_features is None else rank_features, "farthest"
         else:
             on_dev = isinstance(features, torch.Tensor) and features.is_cuda
-            fit = umapfit.umap_fit if on_dev else umapfit.umap_fit_host
-            embedding = fit(features if on_dev else (features.numpy() if isinstance(features, torch.Tensor) else np.asarray(features)),
-                            int(project), seed=project_seed)["embedding"]
+            if on_dev:
+                embedding = umapfit.umap_fit(features, int(project), seed=project_seed, init_solver=project_solver)["embedding"]
+            else:
+                embedding = umapfit.umap_fit_host(features.numpy() if isinstance(features, torch.Tensor) else np.asarray(features),
+                                                  int(project), seed=project_seed)["embedding"]
             features = embedding
     on_gpu = isinstance(features, torch.Tensor) and features.is_cuda
     if on_gpu:

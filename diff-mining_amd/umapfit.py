@@ -1,6 +1,7 @@
 """UMAP projection for the clustering stage: `umap.UMAP(n_components=c, n_neighbors=k).fit_transform(X)` as the reference calls it
 (typicality/cluster.py:312-317 with c = 5; applications/parallel-dataset/cluster.py:253-270 with c = 32, k = 15, once per country's
-block of the features).  Kernels: csrc/umap.hip; C ABI: dm_umap_workspace_bytes / dm_umap_knn / dm_umap_graph / dm_umap_layout.
+block of the features).  Kernels: csrc/umap.hip, csrc/umap_spectral.hip; C ABI: dm_umap_workspace_bytes / dm_umap_knn / dm_umap_graph /
+dm_umap_layout, dm_umap_spectral_workspace_bytes / dm_umap_spectral.
 
 PARITY UNPINNED.  The rules below restate umap-learn 0.5.6 (the reference's environment.yaml) at the two call sites' settings from
 the paper and from memory: umap-learn was not at hand to record its outputs.  tests/make_golden_umap.py records them wherever it is
@@ -28,6 +29,8 @@ negative_sample_rate 5, set_op_mix_ratio 1, local_connectivity 1, repulsion_stre
             fixed so the largest-magnitude entry is positive, scaled to 10 / max|.|, plus seeded N(0, 1e-4) noise.  A disconnected
             graph or dim + 1 >= n: umap-learn's init='random', seeded uniform(-10, 10) (its multi-component spectral layout is out
             of scope).  Either way each coordinate is then rescaled to [0, 10], as umap-learn does for every init.
+            init_solver='device' finds the same eigenvectors from the edge list on the device instead (dm_umap_spectral; the rules
+            are above `spectral_init_iter_host`); the default is the host.
   layout    SYNCHRONOUS within an epoch -- the departure.  umap-learn's numba loop updates coordinates in place from parallel
             threads, which is not reproducible even on the CPU.  Here, in epoch ep (alpha = 1 - ep / n_epochs, fp32): every read
             is of the epoch's input coordinates; vertex i walks its edges (i, j) in edge order, and for each with next_e <= ep
@@ -203,11 +206,187 @@ def spectral_init_host(P, dim: int, seed: int = 42):
     L = np.eye(n) - isd[:, None] * P * isd[None, :]
     L = (L + L.T) * 0.5
     _, vec = np.linalg.eigh(L)
-    Y = vec[:, 1:dim + 1].copy()
+    return _spectral_tail(vec[:, 1:dim + 1], rs.normal(scale=0.0001, size=(n, dim)).astype(np.float32)), "spectral"
+
+
+def _spectral_tail(vec, noise):
+    """The end of the spectral initialisation, shared by both solvers: eigenvectors 1..dim (float64 [n, dim]) -> Y0 fp32 [n, dim].
+    Sign by the largest-magnitude entry, 10 / max|.|, the fp32 cast, the noise (fp32 [n, dim]), the rescale to [0, 10]."""
+    Y = np.array(vec, dtype=np.float64)
+    dim = Y.shape[1]
     top = np.abs(Y).argmax(axis=0)
     Y *= np.sign(Y[top, np.arange(dim)])[None, :]
-    Y = (Y * (10.0 / np.abs(Y).max())).astype(np.float32) + rs.normal(scale=0.0001, size=(n, dim)).astype(np.float32)
-    return _rescale(Y), "spectral"
+    Y = (Y * (10.0 / np.abs(Y).max())).astype(np.float32) + noise
+    return _rescale(Y)
+
+
+# ---- the iterative solver of the spectral initialisation: what csrc/umap_spectral.hip runs, stated in numpy --------------------------
+# The dim + 1 top eigenvectors of M = D^-1/2 P D^-1/2 (the bottom ones of the Laplacian above) from the edge list alone, by
+# Chebyshev-filtered subspace iteration on a block of b = min(n, m + max(8, m // 2)) columns, m = dim + 1:
+#   matrix   deg_i = the sum of row i's weights in edge order (fp64), isd = 1 / sqrt(deg); (M X)_i = isd_i sum_e (w_e isd_col_e) X_col_e,
+#            edges in edge order.
+#   start    column 0 = sqrt(deg) (the top eigenvector, eigenvalue 1), column c > 0 of row i = hash(seed, SPECTRAL_HASH_EP, i, c) / 2^32 - 1/2.
+#   filter   the Chebyshev polynomial that damps [-1, cut]: cut = 0 at first, then the smallest Ritz value of the iteration before
+#            (not below -0.99).  Degree 16, lowered until T_deg at eigenvalue 1 is <= SPECTRAL_GROWTH: the filtered block's condition number
+#            is about that value, and Cholesky-QR applied twice orthonormalises a block only while it stays well below u^-1/2 = 6.7e7
+#            (at degree 16 and cut = 0 it is T_16(3) = 9e11 on a graph whose spectrum is spread: the first Cholesky factorisation then
+#            fails on tests/umap_cases.py's n130, for one).
+#   ortho    Cholesky-QR twice: G = X^T X, R = chol(G)^T, X <- X R^-1.
+#   Ritz     H = Q^T (M Q), symmetrised; cyclic Jacobi in the round-robin order of `_jacobi_rounds` until a sweep rotates nothing;
+#            Ritz values in descending order (ties: the lower column first); Q and M Q are rotated.
+#   stop     every wanted pair has ||M v - theta v||_2 <= SPECTRAL_TOL; at most SPECTRAL_MAX_OUTER iterations.
+SPECTRAL_DEGREE = 16
+SPECTRAL_GROWTH = 1e6
+SPECTRAL_TOL = 1e-11
+SPECTRAL_MAX_OUTER = 40
+SPECTRAL_SWEEPS = 30
+SPECTRAL_MIN_CUT = -0.99
+SPECTRAL_HASH_EP = 0x5EED
+
+
+def spectral_block(n: int, dim: int) -> int:
+    m = dim + 1
+    return min(n, m + max(8, m // 2))
+
+
+def components_host(row_ptr, col, n: int) -> int:
+    """The number of connected components, by min-label propagation over the edge list."""
+    row_ptr = np.asarray(row_ptr, np.int64)
+    col = np.asarray(col, np.int64)
+    head = np.repeat(np.arange(n), np.diff(row_ptr))
+    label = np.arange(n)
+    while True:
+        new = label.copy()
+        np.minimum.at(new, head, label[col])
+        if np.array_equal(new, label):
+            return int(np.sum(label == np.arange(n)))
+        label = new
+
+
+def _csr_apply(row_ptr, coef, col, X):
+    """out_i = sum over row i's edges e, in edge order, of coef_e X[col_e] (float64)"""
+    n = len(row_ptr) - 1
+    cnt = np.diff(row_ptr)
+    out = np.zeros((n, X.shape[1]), np.float64)
+    for r in range(int(cnt.max()) if n else 0):
+        rows = np.flatnonzero(cnt > r)
+        e = row_ptr[rows] + r
+        out[rows] = out[rows] + coef[e, None] * X[col[e]]
+    return out
+
+
+def _cheb_degree(cut: float) -> int:
+    c, e = (cut - 1.0) / 2.0, (cut + 1.0) / 2.0
+    x = (1.0 - c) / e
+    t0, t1, deg = 1.0, x, 1
+    while deg < SPECTRAL_DEGREE:
+        t2 = 2.0 * x * t1 - t0
+        if not t2 <= SPECTRAL_GROWTH:
+            break
+        t0, t1, deg = t1, t2, deg + 1
+    return deg
+
+
+def _jacobi_rounds(b: int):
+    """The fixed sweep order: the round-robin tournament of b players (one dummy if b is odd), P - 1 rounds of disjoint pairs (p < q)."""
+    P = b + (b & 1)
+    rounds = []
+    for s in range(P - 1):
+        k = np.arange(1, P // 2)
+        x = np.concatenate([[P - 1], (s + k) % (P - 1)])
+        y = np.concatenate([[s], (s - k) % (P - 1)])
+        p, q = np.minimum(x, y), np.maximum(x, y)
+        keep = q < b
+        rounds.append((p[keep], q[keep]))
+    return rounds
+
+
+def _jacobi_host(H):
+    """(theta descending, W, sweeps): H W = W diag(theta) by cyclic Jacobi in the order of `_jacobi_rounds`."""
+    H = np.array(H, dtype=np.float64)
+    b = len(H)
+    W = np.eye(b)
+    rounds = _jacobi_rounds(b)
+    sweeps = 0
+    for sweeps in range(1, SPECTRAL_SWEEPS + 1):
+        rotated = False
+        for p, q in rounds:
+            hpp, hqq, hpq = H[p, p], H[q, q], H[p, q]
+            act = np.abs(hpq) > 1e-20 * (np.abs(hpp) + np.abs(hqq))
+            if not act.any():
+                continue
+            rotated = True
+            with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+                tau = (hqq - hpp) / (2.0 * hpq)
+                t = np.where(tau >= 0, 1.0, -1.0) / (np.abs(tau) + np.sqrt(1.0 + tau * tau))
+                c = 1.0 / np.sqrt(1.0 + t * t)
+                s = t * c
+            c, s = np.where(act, c, 1.0), np.where(act, s, 0.0)
+            for A in (H, W):                                   # columns: A <- A J
+                ap, aq = A[:, p].copy(), A[:, q].copy()
+                A[:, p], A[:, q] = c * ap - s * aq, s * ap + c * aq
+            hp, hq = H[p, :].copy(), H[q, :].copy()            # rows: H <- J^T H
+            H[p, :], H[q, :] = c[:, None] * hp - s[:, None] * hq, s[:, None] * hp + c[:, None] * hq
+        if not rotated:
+            break
+    theta = np.diag(H).copy()
+    order = np.argsort(-theta, kind="stable")
+    return theta[order], W[:, order], sweeps
+
+
+def spectral_init_iter_host(row_ptr, col, weight, n: int, dim: int, seed: int = 42):
+    """(Y0 fp32 [n, dim], 'spectral' | 'random', info) from the edge list, by the rules above.  info: 'status' ('converged',
+    'not_converged' -- the caller takes `spectral_init_host` -- or 'random'), 'n_comp', 'iters', 'max_residual', 'degrees' (the
+    filter's, per iteration), and after a solve 'eigvals' (float64 [dim + 1], of M, descending) and 'eigvecs' (float64 [n, dim + 1])."""
+    row_ptr = np.asarray(row_ptr, np.int64)
+    col = np.asarray(col, np.int64)[:row_ptr[-1]]
+    w = np.asarray(weight, np.float32)[:row_ptr[-1]].astype(np.float64)
+    rs = np.random.RandomState(seed)
+    n_comp = components_host(row_ptr, col, n) if n else 0
+    info = {"status": "random", "n_comp": n_comp, "iters": 0, "max_residual": float("nan"), "degrees": []}
+    if n_comp != 1 or dim + 1 >= n:
+        return _rescale(rs.uniform(low=-10.0, high=10.0, size=(n, dim))), "random", info
+    m, b = dim + 1, spectral_block(n, dim)
+    deg = _csr_apply(row_ptr, w, col, np.ones((n, 1)))[:, 0]
+    isd = 1.0 / np.sqrt(deg)
+    coef = w * isd[col]
+
+    def mul(X):
+        return isd[:, None] * _csr_apply(row_ptr, coef, col, X)
+
+    X = hash_host(seed, SPECTRAL_HASH_EP, np.arange(n)[:, None], np.arange(b, dtype=np.uint64)[None, :]).astype(np.float64) / 2.0 ** 32 - 0.5
+    X[:, 0] = np.sqrt(deg)
+    cut = 0.0
+    info["status"] = "not_converged"
+    with np.errstate(all="ignore"):
+        for it in range(1, SPECTRAL_MAX_OUTER + 1):
+            d = _cheb_degree(cut)
+            info["degrees"].append(d)
+            c, e = (cut - 1.0) / 2.0, (cut + 1.0) / 2.0
+            Y0, Y1 = X, (mul(X) - c * X) / e
+            for _ in range(2, d + 1):
+                Y0, Y1 = Y1, 2.0 * (mul(Y1) - c * Y1) / e - Y0
+            Q = Y1
+            try:
+                for _ in range(2):                              # Cholesky-QR, twice
+                    R = np.linalg.cholesky(Q.T @ Q).T
+                    Q = Q @ np.linalg.inv(R)
+            except np.linalg.LinAlgError:
+                break
+            MQ = mul(Q)
+            H = Q.T @ MQ
+            theta, W, _ = _jacobi_host(0.5 * (H + H.T))
+            X, MX = Q @ W, MQ @ W
+            res = np.sqrt(((MX[:, :m] - theta[None, :m] * X[:, :m]) ** 2).sum(axis=0))
+            info.update(iters=it, max_residual=float(res.max()), eigvals=theta[:m].copy(), eigvecs=X[:, :m].copy())
+            if res.max() <= SPECTRAL_TOL:
+                info["status"] = "converged"
+                break
+            cut = max(float(theta[-1]), SPECTRAL_MIN_CUT)
+    noise = rs.normal(scale=0.0001, size=(n, dim)).astype(np.float32)
+    if "eigvecs" not in info:
+        info.update(eigvals=np.full(m, np.nan), eigvecs=np.full((n, m), np.nan))
+    return _spectral_tail(info["eigvecs"][:, 1:], noise), "spectral", info
 
 
 _M32 = np.uint64(0xFFFFFFFF)
@@ -408,11 +587,68 @@ def layout(row_ptr, col, weight, n_edges: int, Y0, a: float, b: float, n_epochs:
     return Y
 
 
-def umap_fit(X, n_components: int, n_neighbors: int = 15, seed: int = 42, n_epochs=None, work=None, times=None):
-    """`umap.UMAP(n_components, n_neighbors).fit_transform(X)` by the rules of this module, on the device X lives on: {'embedding'
-    (device fp32 [n, c]), 'init_used', 'a', 'b', 'n_edges'}.  The graph comes to the host once for the spectral initialisation; the
-    epochs run without a host round trip.  Bit-reproducible.  times: a dict that receives seconds per step (it synchronises)."""
+def spectral_workspace_bytes(n: int, n_components: int) -> int:
+    out = C.c_size_t(0)
+    rc = _lib().dm_umap_spectral_workspace_bytes(int(n), int(n_components), C.byref(out))
+    if rc:
+        _fail("dm_umap_spectral_workspace_bytes", rc)
+    return out.value
+
+
+def spectral_host_arrays(n: int, dim: int, seed: int = 42):
+    """(noise, fallback) fp32 [n, dim]: what dm_umap_spectral takes from the host, drawn as `spectral_init_host` draws them (each from
+    a fresh RandomState(seed): a fit uses one or the other)."""
+    noise = np.random.RandomState(seed).normal(scale=0.0001, size=(n, dim)).astype(np.float32)
+    return noise, _rescale(np.random.RandomState(seed).uniform(low=-10.0, high=10.0, size=(n, dim)))
+
+
+def spectral_status(status):
+    """The status record of dm_umap_spectral (8 float64 values, on the host) as `spectral_init_iter_host` reports it."""
+    s = [float(v) for v in status]
+    used = "random" if s[0] else "spectral"
+    return {"init_used": used, "status": "random" if s[0] else "converged" if s[3] else "not_converged", "n_comp": int(s[1]), "iters": int(s[2]),
+            "max_residual": s[4], "cut": s[5], "degree": int(s[6]), "block": int(s[7])}
+
+
+def spectral_init(G, dim: int, seed: int = 42, work=None, return_vectors: bool = False):
+    """dm_umap_spectral on the edge list of `fuzzy_graph` (G: 'row_ptr', 'col', 'weight' on the device): a dict of device tensors,
+    'Y0' fp32 [n, dim], 'eigvals' float64 [dim + 1], 'eigvecs' float64 [n, dim + 1] (return_vectors) and 'status' float64 [8], read
+    with `spectral_status`.  Nothing here waits for the device."""
     import torch
+    row_ptr = G["row_ptr"]
+    if not (isinstance(row_ptr, torch.Tensor) and row_ptr.is_cuda):
+        raise EngineError("umapfit.spectral_init: the graph must be on the GPU (spectral_init_iter_host is the numpy restatement)")
+    dev = row_ptr.device
+    n = row_ptr.numel() - 1
+    if dim < 1 or dim > UMAP_MAX_COMPONENTS:
+        raise EngineError(f"umapfit.spectral_init: n_components {dim} outside [1, {UMAP_MAX_COMPONENTS}]")
+    noise, fallback = (torch.from_numpy(a).to(dev) for a in spectral_host_arrays(n, dim, seed))
+    out = {"Y0": torch.empty((n, dim), dtype=torch.float32, device=dev), "eigvals": torch.empty(dim + 1, dtype=torch.float64, device=dev),
+           "eigvecs": torch.empty((n, dim + 1), dtype=torch.float64, device=dev) if return_vectors else None,
+           "status": torch.empty(8, dtype=torch.float64, device=dev)}
+    work = _work(work, spectral_workspace_bytes(n, dim), dev)
+    with torch.cuda.device(dev):
+        rc = _lib().dm_umap_spectral(_stream(dev), _p(row_ptr), _p(G["col"]), _p(G["weight"]), n, int(dim), int(seed) & 0x7FFFFFFF, _p(noise),
+                                     _p(fallback), _p(work), work.numel(), _p(out["Y0"]), _p(out["eigvals"]),
+                                     _p(out["eigvecs"]) if return_vectors else None, _p(out["status"]))
+    if rc:
+        _fail("dm_umap_spectral", rc)
+    return out
+
+
+INIT_SOLVERS = ("host", "device")
+
+
+def umap_fit(X, n_components: int, n_neighbors: int = 15, seed: int = 42, n_epochs=None, work=None, times=None, init_solver: str = "host"):
+    """`umap.UMAP(n_components, n_neighbors).fit_transform(X)` by the rules of this module, on the device X lives on: {'embedding'
+    (device fp32 [n, c]), 'init_used', 'a', 'b', 'n_edges', 'init_solver', 'init_iters'}.  init_solver 'host': the graph comes to the
+    host once for the spectral initialisation (`spectral_init_host`).  'device': dm_umap_spectral; the only host read is its status
+    record, together with n_edges; a status of not converged takes the host's initialisation instead, and 'init_solver' says
+    'host (device not converged)'.  The epochs run without a host round trip.  Bit-reproducible.  times: a dict that receives
+    seconds per step (it synchronises)."""
+    import torch
+    if init_solver not in INIT_SOLVERS:
+        raise ValueError(f"umap_fit: init_solver {init_solver!r} is not one of {INIT_SOLVERS}")
     X = _gpu_f32(X, "umapfit.umap_fit")
     if X.dim() != 2:
         raise EngineError(f"umapfit.umap_fit: X must be [n, d], got {tuple(X.shape)}")
@@ -431,21 +667,38 @@ def umap_fit(X, n_components: int, n_neighbors: int = 15, seed: int = 42, n_epoc
     idx, dist = knn(X, n_neighbors, work)
     t.append(mark())
     G = fuzzy_graph(idx, dist, n_epochs, work)
-    n_edges = int(G["n_edges"])
-    t.append(mark())
-    Y0, used = spectral_init_host(G["P"].cpu().numpy(), n_components, seed)
-    Y0 = torch.from_numpy(Y0).to(dev)
+    solver, iters = "host", 0
+    if init_solver == "device":
+        if times is not None:                              # timed: the graph's step ends before the solve is enqueued
+            n_edges = int(G["n_edges"])
+        t.append(mark())
+        S = spectral_init(G, n_components, seed)           # its own workspace; enqueued before anything is read
+        if times is not None:
+            st = spectral_status(S["status"].cpu().numpy())
+        else:
+            both = torch.cat([G["n_edges"].to(torch.float64).reshape(1), S["status"]]).cpu().numpy()       # the fit's one host read
+            n_edges, st = int(both[0]), spectral_status(both[1:])
+        Y0, used, solver, iters = S["Y0"], st["init_used"], "device", st["iters"]
+        if st["status"] == "not_converged":
+            solver = "host (device not converged)"
+    else:
+        n_edges = int(G["n_edges"])
+        t.append(mark())
+    if solver != "device":
+        Y0, used = spectral_init_host(G["P"].cpu().numpy(), n_components, seed)
+        Y0 = torch.from_numpy(Y0).to(dev)
     t.append(mark())
     Y = layout(G["row_ptr"], G["col"], G["weight"], n_edges, Y0, a, b, n_epochs, seed, work=work, n_neighbors=n_neighbors)
     t.append(mark())
     if times is not None:
         times.update(zip(("knn", "graph", "init", "layout"), np.diff(t)))
-    return {"embedding": Y, "init_used": used, "a": a, "b": b, "n_edges": n_edges}
+    return {"embedding": Y, "init_used": used, "a": a, "b": b, "n_edges": n_edges, "init_solver": solver, "init_iters": iters}
 
 
-def compress(X, n_groups: int, num_components: int = 32, n_neighbors: int = 15, seed: int = 42, n_epochs=None):
+def compress(X, n_groups: int, num_components: int = 32, n_neighbors: int = 15, seed: int = 42, n_epochs=None, init_solver: str = "host"):
     """`compress` of the parallel dataset (cluster.py:253-266): one fit per group of d // n_groups consecutive features (a country's
-    block), the embeddings side by side.  A GPU tensor stays on the device; a numpy array takes the restatement."""
+    block), the embeddings side by side.  A GPU tensor stays on the device (init_solver: `umap_fit`'s); a numpy array takes the
+    restatement."""
     import torch
     on_gpu = isinstance(X, torch.Tensor) and X.is_cuda
     if isinstance(X, torch.Tensor) and not on_gpu:
@@ -457,7 +710,7 @@ def compress(X, n_groups: int, num_components: int = 32, n_neighbors: int = 15, 
     parts = []
     for i in range(0, d, group):
         if on_gpu:
-            parts.append(umap_fit(X[:, i:i + group], num_components, n_neighbors, seed, n_epochs)["embedding"])
+            parts.append(umap_fit(X[:, i:i + group], num_components, n_neighbors, seed, n_epochs, init_solver=init_solver)["embedding"])
         else:
             parts.append(umap_fit_host(X[:, i:i + group], num_components, n_neighbors, seed, n_epochs)["embedding"])
     return torch.cat(parts, dim=1) if on_gpu else np.hstack(parts)

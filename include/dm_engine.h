@@ -381,6 +381,27 @@ int dm_umap_layout(void* stream, const int32_t* row_ptr, const int32_t* col, con
                    float a, float b, int n_epochs, int seed, int first_epoch, int last_epoch, float* Y_inout, void* work,
                    size_t work_bytes);
 
+/* dm_umap_spectral: UMAP's spectral initialisation from the edge list of dm_umap_graph, without a host round trip (csrc/umap_spectral.hip;
+ * the rules: `spectral_init_iter_host` in umapfit.py).  The n_components + 1 top eigenvectors of D^-1/2 P D^-1/2 by Chebyshev-filtered
+ * subspace iteration in fp64 on a block of min(n, m + max(8, m / 2)) columns, m = n_components + 1; every outer iteration of the cap
+ * (40) is enqueued on `stream`, and a device-side flag turns the ones after convergence into empty launches.  No floating-point
+ * atomics: bit-reproducible.
+ *   noise, fallback   fp32 [n][n_components], device: the seeded N(0, 1e-4) noise and the rescaled uniform(-10, 10) initialisation,
+ *                     both drawn by the host (they do not depend on the graph)
+ *   work              at least dm_umap_spectral_workspace_bytes(n, n_components) bytes; its contents do not matter
+ *   Y0_out            fp32 [n][n_components]: eigenvectors 1 .. n_components, sign by the largest-magnitude entry, 10 / max|.|, + noise,
+ *                     each coordinate rescaled to [0, 10]; `fallback` if the graph has more than one component or n_components + 1 >= n
+ *   eigvals_out       fp64 [n_components + 1], descending (1 - these are the Laplacian's); eigvecs_out fp64 [n][n_components + 1] or NULL
+ *   status_out        fp64 [8]: 0 spectral / 1 random, component count, outer iterations, converged (0 / 1), the largest residual
+ *                     ||M v - theta v||_2 of the last iteration, the last filter's cut and degree, the block's columns.  A spectral
+ *                     status that is not converged (40 iterations without every residual <= 1e-11) means Y0_out is not to be used.
+ * Refused without a launch: a NULL pointer (eigvecs_out excepted), n >= DM_UMAP_MAX_N, n < 1 (DM_UMAP_E_NEIGHBORS_GE_N),
+ * n_components outside [1, DM_UMAP_MAX_COMPONENTS], a small workspace. */
+int dm_umap_spectral_workspace_bytes(int n, int n_components, size_t* bytes_out);
+int dm_umap_spectral(void* stream, const int32_t* row_ptr, const int32_t* col, const float* weight, int n, int n_components, int seed,
+                     const float* noise, const float* fallback, void* work, size_t work_bytes, float* Y0_out, double* eigvals_out,
+                     double* eigvecs_out, double* status_out);
+
 /* ---- X-ray evaluation: threshold counts of a heat-map against a ground-truth box (csrc/xray_eval.hip) -------------
  * The device half of `aucpr` and `mean_typicallity` (applications/xray/compute.py:263-284).  A stream-plus-workspace function
  * (no engine handle).  Row r of the descriptor table names a map [H][W] fp32 at maps_dev + map_offset (floats, any value; two
