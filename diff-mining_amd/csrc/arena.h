@@ -1,4 +1,4 @@
-// arena.h — the workspace allocator both schedules use (engine_forward.hip: fp16 U-Net / VAE / CLIP; unet_f32.hip: the fp32 U-Net).
+// arena.h — the workspace allocator both schedules use (engine_forward.hip: fp16 U-Net / VAE / CLIP; f32_forward.hip, f32_vae.hip, f32_clip_nets.hip: the fp32 net).
 // A first-fit free list over ONE device allocation, driven from the host: the schedule is run once "dry" (sizes only, no
 // launches) to learn its exact peak, the buffer is (re)allocated only when a call needs more than it holds, and the real run
 // then hands out the same offsets again (the allocator is deterministic).

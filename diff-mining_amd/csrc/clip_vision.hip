@@ -1,4 +1,4 @@
-// clip_vision.hip — the glue kernels of the fp32 CLIP ViT-B/32 image tower (dm_f32_clip_image_features, unet_f32.hip): the
+// clip_vision.hip — the glue kernels of the fp32 CLIP ViT-B/32 image tower (dm_f32_clip_image_features, f32_clip_nets.hip): the
 // processor's preprocessing, patch rows, token assembly, the CLS gather and the L2 normalisation (the attention over the 50
 // tokens is the text tower's kernel without the mask, f32_ops.hip).  Every GEMM of the tower (patch embedding, q|k|v, out_proj,
 // fc1, fc2, visual_projection) runs on gemm32.  Below them, with (size, patch) as launch parameters, the glue of the configurable

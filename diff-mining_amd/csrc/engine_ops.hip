@@ -2,7 +2,7 @@
 // The matrix kernels first (igemm tiles, attention routes, norms, conv_out), then the glue kernels around them, one entry per launch_*:
 // dm_op_time_gather, dm_op_silu, dm_op_im2col_in, dm_op_nhwc_to_nchw, dm_op_ensemble_mean (misc.hip), dm_op_im2col_rgb, dm_op_posterior
 // (vae.hip), dm_op_clip_embed, dm_op_clip_attention, dm_op_quick_gelu, dm_op_f16_to_f32 (clip.hip), dm_op_cfg_ddim_step, dm_op_latent_prologue,
-// dm_op_decoder_tail (sample.hip).  Their fp32 counterparts are the dm_f32_op_* of unet_f32.hip.
+// dm_op_decoder_tail (sample.hip).  Their fp32 counterparts are the dm_f32_op_* of f32_net.hip.
 #include "../../include/dm_engine.h"
 #include "dm_kernels.h"
 

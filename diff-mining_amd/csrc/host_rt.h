@@ -1,4 +1,4 @@
-// host_rt.h — error plumbing of the host-side runtimes (engine*.hip, unet_f32.hip).  `e` is a handle with a std::string `err`; each
+// host_rt.h — error plumbing of the host-side runtimes (engine*.hip, f32_*.hip).  `e` is a handle with a std::string `err`; each
 // macro returns from the enclosing int function: 1 after writing the message, or the failing callee's code.
 #pragma once
 #include <cstdio>

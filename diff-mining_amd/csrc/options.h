@@ -1,4 +1,4 @@
-// options.h — the process-wide runtime switches.  Stands alone (unet_f32.hip), and is what dm_kernels.h includes from inside its own
+// options.h — the process-wide runtime switches.  Stands alone (f32_impl.h), and is what dm_kernels.h includes from inside its own
 // `namespace dm` (DM_OPTIONS_IN_NAMESPACE_DM), so the kernels' translation units see these declarations where they always stood.
 #pragma once
 #ifndef DM_OPTIONS_IN_NAMESPACE_DM

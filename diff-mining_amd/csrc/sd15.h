@@ -1,5 +1,5 @@
 // sd15.h — architecture constants of the public SDv1.5 checkpoint (unet / vae / text_encoder config.json), once, for the fp16 engine
-// (engine*.hip) and the fp32 net (unet_f32.hip).
+// (engine*.hip) and the fp32 net (f32_*.hip).
 #pragma once
 
 namespace sd15 {

@@ -1,5 +1,5 @@
 // weights.h — staging and upload of one state dict: what the seven loaders / finalizers of the fp16 engine (engine_pack.hip, T = f16)
-// and of the fp32 net (unet_f32.hip, T = float) share.  A loader normalises the tensor's name and calls stage_tensor(); a finalizer
+// and of the fp32 net (f32_pack.hip, T = float) share.  A loader normalises the tensor's name and calls stage_tensor(); a finalizer
 // packs the staged tensors into a host blob (WeightSet::get marks what it consumed) and hands the blob to WeightSet::finish().
 #pragma once
 #include "../../include/dm_engine.h"

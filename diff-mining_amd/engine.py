@@ -197,7 +197,7 @@ MINE_DESC_DTYPE = np.dtype([("grid_offset", "<i8"), ("work_offset", "<i8"), ("ma
                             ("h", "<i4"), ("w", "<i4"), ("H", "<i4"), ("W", "<i4")])
 MINE_MAX_K = 64
 MINE_MAX_SETS = 16          # DM_MINE_MAX_SETS: the set counts median_maps_kernel is instantiated for
-CLIP_TOWER_CHUNK = 64       # CT_CHUNK (unet_f32.hip): images per run of the configurable CLIP image tower
+CLIP_TOWER_CHUNK = 64       # CT_CHUNK (f32_impl.h): images per run of the configurable CLIP image tower
 
 
 def get_options(names=("ln_fold", "gn_fold", "ff_fold", "sc_fold", "up_fold", "tap_reuse", "ln_inkernel", "igemm_splitk", "q_once", "gn_epi", "conv_out_rows", "gn_skip", "attn_pipe", "graph")) -> dict:

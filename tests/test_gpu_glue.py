@@ -1,4 +1,4 @@
-"""The engines' glue kernels one by one (dm_op_* of engine_ops.hip, dm_f32_op_* of unet_f32.hip) against the references of
+"""The engines' glue kernels one by one (dm_op_* of engine_ops.hip, dm_f32_op_* of f32_net.hip) against the references of
 tests/glue_cases.py, which tests/test_glue_refs.py proves on the CPU.
 
 Every operand of every call lives in a tests/gpu_util.py Guarded buffer: check() after the call catches a store outside a tensor and a
