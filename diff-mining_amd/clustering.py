@@ -16,7 +16,7 @@ max_iter=300, tol=1e-4), restated here in numpy (`kmeans_fit_host`) with the rul
             distance (each leaves its old cluster's sum and count); shift = sum_j |c_new - c_old|^2; stop strictly when the labels
             repeat, else when shift <= tol_abs; after a non-strict stop (or max_iter) one more assignment.
 
-UMAP (umapfit.py, csrc/umap.hip; parity with umap-learn unpinned) is `cluster_patches(project=...)`: `project=5` is the main
+UMAP (umapfit.py, csrc/umap.hip and, from 4096 rows up to 65535, csrc/umap_sparse.hip; parity with umap-learn unpinned) is `cluster_patches(project=...)`: `project=5` is the main
 stage's project=True, `project=('groups', G, 32)` the parallel dataset's compress(); the default None is the reference's
 project=False.  One call clusters one category; several categories are several calls (no batched entry yet).
 """
@@ -337,7 +337,8 @@ def cluster_patches(features, D, num_clusters: int = 32, aggregate: str = "media
                 embedding = umapfit.umap_fit(features, int(project), seed=project_seed, init_solver=project_solver)["embedding"]
             else:
                 embedding = umapfit.umap_fit_host(features.numpy() if isinstance(features, torch.Tensor) else np.asarray(features),
-                                                  int(project), seed=project_seed)["embedding"]
+                                                  int(project), seed=project_seed,
+                                                  route=umapfit.pick_route("auto", len(features)))["embedding"]
             features = embedding
     on_gpu = isinstance(features, torch.Tensor) and features.is_cuda
     if on_gpu:

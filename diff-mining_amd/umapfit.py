@@ -1,7 +1,16 @@
 """UMAP projection for the clustering stage: `umap.UMAP(n_components=c, n_neighbors=k).fit_transform(X)` as the reference calls it
 (typicality/cluster.py:312-317 with c = 5; applications/parallel-dataset/cluster.py:253-270 with c = 32, k = 15, once per country's
-block of the features).  Kernels: csrc/umap.hip, csrc/umap_spectral.hip; C ABI: dm_umap_workspace_bytes / dm_umap_knn / dm_umap_graph /
-dm_umap_layout, dm_umap_spectral_workspace_bytes / dm_umap_spectral.
+block of the features).  Kernels: csrc/umap.hip, csrc/umap_spectral.hip, csrc/umap_sparse.hip; C ABI: dm_umap_workspace_bytes /
+dm_umap_knn / dm_umap_graph / dm_umap_layout, dm_umap_spectral_workspace_bytes / dm_umap_spectral, and the same names after
+dm_umap_sparse_.
+
+Two routes, one set of rules.  `route='dense'` goes through the n x n graph and takes n < 4096 (UMAP_MAX_N).  `route='sparse'` works
+from the neighbour lists alone, takes n < 65536 (UMAP_SPARSE_MAX_N) and gives the same bits wherever both run; 'auto' (the device
+functions' default) is dense below 4096 rows and sparse from there.  The parallel dataset's default is 10 000 patches per fit
+(cluster.py:391), which is why the sparse route exists.  Above 4095 rows umap-learn itself switches to approximate NN-descent
+neighbours, unseeded; this module stays exact there, so nothing of umap-learn's is bit-comparable above the limit, and parity
+stays unpinned on both routes.  Not measured: real DIFT features at 10 000 rows, whether real graphs of that size are connected (a
+disconnected one takes the random initialisation, as below), and quality against umap-learn.
 
 PARITY UNPINNED.  The rules below restate umap-learn 0.5.6 (the reference's environment.yaml) at the two call sites' settings from
 the paper and from memory: umap-learn was not at hand to record its outputs.  tests/make_golden_umap.py records them wherever it is
@@ -14,7 +23,7 @@ negative_sample_rate 5, set_op_mix_ratio 1, local_connectivity 1, repulsion_stre
 
   a, b      scipy curve_fit of 1 / (1 + a x^(2b)) to y = 1 (x < min_dist), exp(-(x - min_dist) / spread) on linspace(0, 3 spread,
             300): 1.5769, 0.8951 at the defaults.  Host only.
-  kNN       exact (umap-learn's own path below 4096 rows; n >= 4096 is refused).  Squared distance = the sum over ascending
+  kNN       exact (umap-learn's own path below 4096 rows; the sparse route stays exact above).  Squared distance = the sum over ascending
             feature index of (double(x_i) - double(x_k))^2 in fp64, multiply and add separate; distance = fp64 sqrt rounded to
             fp32; the n_neighbors smallest per row, self included, ties to the lower index.  Host and device agree bit for bit.
   smooth    rho_i = the smallest non-zero neighbour distance (0 if none).  sigma_i: 64 bisection steps at most (lo 0, hi inf, mid
@@ -55,7 +64,9 @@ import numpy as np
 
 from .engine import EngineError, _p, load_library as _lib
 
-UMAP_MAX_N = 4096            # DM_UMAP_MAX_N: n >= this is refused (umap-learn switches to approximate neighbours there)
+UMAP_MAX_N = 4096            # DM_UMAP_MAX_N: the dense route refuses n >= this (umap-learn switches to approximate neighbours there)
+UMAP_SPARSE_MAX_N = 65536    # DM_UMAP_SPARSE_MAX_N: the sparse route refuses n >= this
+ROUTES = ("auto", "dense", "sparse")
 UMAP_MAX_NEIGHBORS = 64      # DM_UMAP_MAX_NEIGHBORS
 UMAP_MAX_COMPONENTS = 64     # DM_UMAP_MAX_COMPONENTS
 NEG_RATE = 5
@@ -63,7 +74,7 @@ SMOOTH_STEPS = 64
 SMOOTH_TOL = 1e-5
 MIN_K_DIST_SCALE = 1e-3
 # dm_umap_* return codes (include/dm_engine.h)
-ERRORS = {1: "null argument", 2: f"n >= {UMAP_MAX_N}", 3: "n_neighbors >= n", 4: f"n_neighbors outside [2, {UMAP_MAX_NEIGHBORS}]",
+ERRORS = {1: "null argument", 2: f"n >= {UMAP_MAX_N} (dense route) or {UMAP_SPARSE_MAX_N} (sparse route)", 3: "n_neighbors >= n", 4: f"n_neighbors outside [2, {UMAP_MAX_NEIGHBORS}]",
           5: f"n_components outside [1, {UMAP_MAX_COMPONENTS}]", 6: "d < 1", 7: "bad epoch range", 8: "workspace too small",
           9: "bad edge count", 10: "HIP error"}
 
@@ -72,9 +83,20 @@ def default_epochs(n: int) -> int:
     return 500 if n <= 10000 else 200
 
 
-def _check(n, d, k, dim=1):
-    if n >= UMAP_MAX_N:
+def pick_route(route: str, n: int) -> str:
+    """'dense' or 'sparse': 'auto' is dense below UMAP_MAX_N rows (the behaviour before the sparse route existed) and sparse from there"""
+    if route not in ROUTES:
+        raise ValueError(f"umap: route {route!r} is not one of {ROUTES}")
+    return ("dense" if n < UMAP_MAX_N else "sparse") if route == "auto" else route
+
+
+def _check(n, d, k, dim=1, route="dense"):
+    if route not in ("dense", "sparse"):
+        raise ValueError(f"umap: route {route!r} is not 'dense' or 'sparse'")
+    if route == "dense" and n >= UMAP_MAX_N:
         raise ValueError(f"umap: n {n} >= {UMAP_MAX_N} (exact neighbours only)")
+    if n >= UMAP_SPARSE_MAX_N:
+        raise ValueError(f"umap: n {n} >= {UMAP_SPARSE_MAX_N}")
     if k < 2 or k > UMAP_MAX_NEIGHBORS:
         raise ValueError(f"umap: n_neighbors {k} outside [2, {UMAP_MAX_NEIGHBORS}]")
     if k >= n:
@@ -102,12 +124,32 @@ def find_ab_params(spread: float = 1.0, min_dist: float = 0.1):
     return float(params[0]), float(params[1])
 
 
-def knn_host(X, n_neighbors: int = 15):
-    """(idx int32 [n, k], dist fp32 [n, k]) by the kNN rule at the top of this module."""
+KNN_HOST_BLOCK = 256         # rows per block of the sparse route's restatement
+
+
+def knn_host(X, n_neighbors: int = 15, route: str = "dense"):
+    """(idx int32 [n, k], dist fp32 [n, k]) by the kNN rule at the top of this module.  route 'sparse': the same per-feature fp64
+    passes on blocks of KNN_HOST_BLOCK rows, so n x n is never formed; the same bits."""
     X = np.ascontiguousarray(X, dtype=np.float32)
     n, d = X.shape
-    _check(n, d, n_neighbors)
+    _check(n, d, n_neighbors, route=route)
     Xd = X.astype(np.float64)
+    if route == "sparse":
+        idx = np.empty((n, n_neighbors), np.int32)
+        dist = np.empty((n, n_neighbors), np.float32)
+        for i0 in range(0, n, KNN_HOST_BLOCK):
+            rows = slice(i0, min(n, i0 + KNN_HOST_BLOCK))
+            sq = np.zeros((rows.stop - i0, n), dtype=np.float64)
+            t = np.empty_like(sq)
+            for e in range(d):
+                np.subtract(Xd[rows, e][:, None], Xd[None, :, e], out=t)
+                np.multiply(t, t, out=t)
+                sq += t
+            db = np.sqrt(sq).astype(np.float32)
+            ib = np.argsort(db, axis=1, kind="stable")[:, :n_neighbors]
+            idx[rows] = ib
+            dist[rows] = np.take_along_axis(db, ib, axis=1)
+        return idx, dist
     sq = np.zeros((n, n), dtype=np.float64)
     t = np.empty((n, n), dtype=np.float64)
     for e in range(d):                                   # ascending feature index, multiply and add separate
@@ -155,10 +197,14 @@ def _smooth_host(dist, dtype):
     return rho, sigma, floored | live
 
 
-def fuzzy_graph_host(idx, dist, n_epochs: int = 500, dtype=np.float64):
+def fuzzy_graph_host(idx, dist, n_epochs: int = 500, dtype=np.float64, route: str = "dense"):
     """The fuzzy simplicial set from the kNN arrays.  dtype: the precision of the bisection and of exp (float64 is the rule; float32
     is there to measure what fp32 costs).  Returns a dict: rho, sigma (fp32 [n]), exempt (bool [n]: floor or step cap decided sigma),
-    P (fp32 [n, n], pruned), threshold, row_ptr (int32 [n + 1]), col (int32 [E]), weight (fp32 [E])."""
+    P (fp32 [n, n], pruned; route 'dense' only), threshold, row_ptr (int32 [n + 1]), col (int32 [E]), weight (fp32 [E]).  route
+    'sparse' takes the union on the lists (an edge's two memberships are looked up by the key row n + column) and has no P; the
+    rest is the same bits."""
+    if route not in ("dense", "sparse"):
+        raise ValueError(f"umap: route {route!r} is not 'dense' or 'sparse'")
     idx = np.asarray(idx)
     dist = np.asarray(dist, dtype=np.float32)
     n, k = dist.shape
@@ -168,6 +214,25 @@ def fuzzy_graph_host(idx, dist, n_epochs: int = 500, dtype=np.float64):
     with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
         val = np.where((x <= 0) | (s == 0), np.dtype(dtype).type(1), np.exp(-(x / s))).astype(np.float32)
     val[idx == np.arange(n)[:, None]] = 0
+    if route == "sparse":
+        rows = np.repeat(np.arange(n, dtype=np.int64), k)
+        cols = idx.astype(np.int64).ravel()
+        ok = (cols >= 0) & (cols < n) & (cols != rows)
+        rows, cols, a = rows[ok], cols[ok], val.ravel()[ok]
+        out_key, in_key = rows * n + cols, cols * n + rows
+        keys = np.unique(np.concatenate([out_key, in_key]))            # ascending: row-major, ascending column
+        a_ij = np.zeros(len(keys), np.float32)
+        a_ji = np.zeros(len(keys), np.float32)
+        a_ij[np.searchsorted(keys, out_key)] = a
+        a_ji[np.searchsorted(keys, in_key)] = a
+        p = (a_ij + a_ji) - a_ij * a_ji
+        thr = np.float32(p.max(initial=np.float32(0)) / np.float32(n_epochs))
+        keep = ~(p < thr) & (p != 0)
+        keys, p = keys[keep], p[keep]
+        row_ptr = np.zeros(n + 1, np.int32)
+        row_ptr[1:] = np.cumsum(np.bincount(keys // n, minlength=n))
+        return {"rho": rho, "sigma": sigma, "exempt": exempt, "threshold": thr, "row_ptr": row_ptr, "col": (keys % n).astype(np.int32),
+                "weight": p}
     A = np.zeros((n, n), np.float32)
     np.put_along_axis(A, idx.astype(np.int64), val, axis=1)
     P = (A + A.T) - A * A.T
@@ -202,11 +267,49 @@ def spectral_init_host(P, dim: int, seed: int = 42):
     n_comp = connected_components(P > 0, directed=False)[0] if n else 0
     if n_comp != 1 or dim + 1 >= n:
         return _rescale(rs.uniform(low=-10.0, high=10.0, size=(n, dim))), "random"
+    _, vec = _laplacian_eigh(P)
+    return _spectral_tail(vec[:, 1:dim + 1], rs.normal(scale=0.0001, size=(n, dim)).astype(np.float32)), "spectral"
+
+
+def _laplacian_eigh(P):
+    """numpy's eigh of I - D^-1/2 P D^-1/2, P dense float64: (eigenvalues ascending, eigenvectors)"""
+    n = P.shape[0]
     isd = 1.0 / np.sqrt(P.sum(axis=1))
     L = np.eye(n) - isd[:, None] * P * isd[None, :]
     L = (L + L.T) * 0.5
-    _, vec = np.linalg.eigh(L)
-    return _spectral_tail(vec[:, 1:dim + 1], rs.normal(scale=0.0001, size=(n, dim)).astype(np.float32)), "spectral"
+    return np.linalg.eigh(L)
+
+
+def spectral_init_sparse_host(row_ptr, col, weight, n: int, dim: int, seed: int = 42, dense_below: int = UMAP_MAX_N):
+    """(Y0 fp32 [n, dim], 'spectral' | 'random', info) from the edge list, by the init rule at the top of this module.  Below
+    `dense_below` rows the rule's own solver still fits -- numpy's eigh of the dense Laplacian, `spectral_init_host`'s, the same bits --
+    and from there the dense matrix is never formed: scipy's `eigsh` (ARPACK, largest algebraic, started from the all-ones vector so
+    that it is reproducible) on the sparse M = D^-1/2 P D^-1/2, whose top eigenvectors are the Laplacian's bottom ones.  Then
+    `_spectral_tail`.  dense_below = 0 takes eigsh at any size.  info: 'n_comp', 'solver' ('eigh' | 'eigsh'), and after a solve
+    'eigvals' (float64 [dim + 1], of M, descending) and 'eigvecs' (float64 [n, dim + 1])."""
+    from scipy import sparse
+    from scipy.sparse.csgraph import connected_components
+    row_ptr = np.asarray(row_ptr, np.int64)
+    col = np.asarray(col, np.int64)[:row_ptr[-1]]
+    w = np.asarray(weight, np.float32)[:row_ptr[-1]].astype(np.float64)
+    rs = np.random.RandomState(seed)
+    P = sparse.csr_matrix((w, col, row_ptr), shape=(n, n))
+    n_comp = connected_components(P, directed=False)[0] if n else 0
+    info = {"n_comp": int(n_comp), "solver": None}
+    if n_comp != 1 or dim + 1 >= n:
+        return _rescale(rs.uniform(low=-10.0, high=10.0, size=(n, dim))), "random", info
+    m = dim + 1
+    if n < dense_below or m + 1 >= n:                       # ARPACK takes fewer than n - 1 pairs
+        val, vec = _laplacian_eigh(P.toarray())
+        info.update(solver="eigh", eigvals=1.0 - val[:m], eigvecs=vec[:, :m].copy())
+    else:
+        from scipy.sparse.linalg import eigsh
+        isd = 1.0 / np.sqrt(np.asarray(P.sum(axis=1)).ravel())
+        M = sparse.diags(isd) @ P @ sparse.diags(isd)
+        val, vec = eigsh(((M + M.T) * 0.5).tocsr(), k=m, which="LA", v0=np.ones(n), tol=0, ncv=min(n, max(2 * m + 1, 40)))
+        order = np.argsort(-val, kind="stable")
+        info.update(solver="eigsh", eigvals=val[order].copy(), eigvecs=vec[:, order].copy())
+    return _spectral_tail(info["eigvecs"][:, 1:], rs.normal(scale=0.0001, size=(n, dim)).astype(np.float32)), "spectral", info
 
 
 def _spectral_tail(vec, noise):
@@ -476,26 +579,31 @@ def layout_host(row_ptr, col, weight, Y0, a, b, n_epochs: int = 500, seed: int =
     return Y, (eps, epn, nxt, nneg)
 
 
-def umap_fit_host(X, n_components: int, n_neighbors: int = 15, seed: int = 42, n_epochs=None, dtype=np.float32, times=None):
-    """The whole restatement on a numpy array: {'embedding' fp32 [n, c], 'init_used', 'a', 'b', 'n_edges'}.  times: a dict that
-    receives seconds per step."""
+def umap_fit_host(X, n_components: int, n_neighbors: int = 15, seed: int = 42, n_epochs=None, dtype=np.float32, times=None,
+                  route: str = "dense"):
+    """The whole restatement on a numpy array: {'embedding' fp32 [n, c], 'init_used', 'a', 'b', 'n_edges', 'route'}.  times: a dict
+    that receives seconds per step.  route: 'dense' (the default: n < 4096) or 'sparse' (n < 65536, no n x n array; the initialisation
+    is `spectral_init_sparse_host`) -- the restatement does not choose by itself."""
     X = np.ascontiguousarray(X, dtype=np.float32)
     n, d = X.shape
-    _check(n, d, n_neighbors, n_components)
+    _check(n, d, n_neighbors, n_components, route)
     n_epochs = default_epochs(n) if n_epochs is None else int(n_epochs)
     t = [time.perf_counter()]
     a, b = find_ab_params()
-    idx, dist = knn_host(X, n_neighbors)
+    idx, dist = knn_host(X, n_neighbors, route)
     t.append(time.perf_counter())
-    G = fuzzy_graph_host(idx, dist, n_epochs)
+    G = fuzzy_graph_host(idx, dist, n_epochs, route=route)
     t.append(time.perf_counter())
-    Y0, used = spectral_init_host(G["P"], n_components, seed)
+    if route == "sparse":
+        Y0, used, _ = spectral_init_sparse_host(G["row_ptr"], G["col"], G["weight"], n, n_components, seed)
+    else:
+        Y0, used = spectral_init_host(G["P"], n_components, seed)
     t.append(time.perf_counter())
     Y, _ = layout_host(G["row_ptr"], G["col"], G["weight"], Y0, a, b, n_epochs, seed, dtype=dtype)
     t.append(time.perf_counter())
     if times is not None:
         times.update(zip(("knn", "graph", "init", "layout"), np.diff(t)))
-    return {"embedding": Y.astype(np.float32), "init_used": used, "a": a, "b": b, "n_edges": int(len(G["col"])), "init": Y0}
+    return {"embedding": Y.astype(np.float32), "init_used": used, "a": a, "b": b, "n_edges": int(len(G["col"])), "init": Y0, "route": route}
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -505,11 +613,17 @@ def _fail(what, rc):
     raise EngineError(f"{what}: {ERRORS.get(rc, 'error')} (code {rc})")
 
 
-def workspace_bytes(n: int, d: int, n_neighbors: int, n_components: int) -> int:
+def _entry(name: str, route: str) -> str:
+    """the C function of a step on a route: dm_umap_<name> or dm_umap_sparse_<name>"""
+    return ("dm_umap_sparse_" if route == "sparse" else "dm_umap_") + name
+
+
+def workspace_bytes(n: int, d: int, n_neighbors: int, n_components: int, route: str = "dense") -> int:
     out = C.c_size_t(0)
-    rc = _lib().dm_umap_workspace_bytes(int(n), int(d), int(n_neighbors), int(n_components), C.byref(out))
+    name = _entry("workspace_bytes", pick_route(route, n))
+    rc = getattr(_lib(), name)(int(n), int(d), int(n_neighbors), int(n_components), C.byref(out))
     if rc:
-        _fail("dm_umap_workspace_bytes", rc)
+        _fail(name, rc)
     return out.value
 
 
@@ -530,25 +644,27 @@ def _work(work, need, dev):
     return torch.empty(need, dtype=torch.uint8, device=dev) if work is None else work
 
 
-def knn(X, n_neighbors: int = 15, work=None):
-    """dm_umap_knn: (idx int32 [n, k], dist fp32 [n, k]) device tensors, bit-equal to `knn_host`."""
+def knn(X, n_neighbors: int = 15, work=None, route: str = "auto"):
+    """dm_umap_knn / dm_umap_sparse_knn: (idx int32 [n, k], dist fp32 [n, k]) device tensors, bit-equal to `knn_host` on either route."""
     import torch
     X = _gpu_f32(X, "umapfit.knn")
     n, d = X.shape
     dev = X.device
+    route = pick_route(route, n)
+    name = _entry("knn", route)
     idx = torch.empty((n, n_neighbors), dtype=torch.int32, device=dev)
     dist = torch.empty((n, n_neighbors), dtype=torch.float32, device=dev)
-    work = _work(work, workspace_bytes(n, d, n_neighbors, 1), dev)
+    work = _work(work, workspace_bytes(n, d, n_neighbors, 1, route), dev)
     with torch.cuda.device(dev):
-        rc = _lib().dm_umap_knn(_stream(dev), _p(X), n, d, int(n_neighbors), _p(work), work.numel(), _p(idx), _p(dist))
+        rc = getattr(_lib(), name)(_stream(dev), _p(X), n, d, int(n_neighbors), _p(work), work.numel(), _p(idx), _p(dist))
     if rc:
-        _fail("dm_umap_knn", rc)
+        _fail(name, rc)
     return idx, dist
 
 
-def fuzzy_graph(idx, dist, n_epochs: int = 500, work=None):
-    """dm_umap_graph: a dict of device tensors: rho, sigma [n], P [n, n], row_ptr [n + 1], col, weight (2 n k slots; the first
-    n_edges hold the edges), n_edges (int32 [])."""
+def fuzzy_graph(idx, dist, n_epochs: int = 500, work=None, route: str = "auto"):
+    """dm_umap_graph / dm_umap_sparse_graph: a dict of device tensors: rho, sigma [n], P [n, n] (the dense route only), row_ptr [n + 1],
+    col, weight (2 n k slots; the first n_edges hold the edges), n_edges (int32 [])."""
     import torch
     dist = _gpu_f32(dist, "umapfit.fuzzy_graph")
     dev = dist.device
@@ -556,42 +672,52 @@ def fuzzy_graph(idx, dist, n_epochs: int = 500, work=None):
     n, k = dist.shape
     if idx.shape != dist.shape:
         raise EngineError("umapfit.fuzzy_graph: idx and dist must both be [n, k]")
+    route = pick_route(route, n)
     out = {"rho": torch.empty(n, dtype=torch.float32, device=dev), "sigma": torch.empty(n, dtype=torch.float32, device=dev),
-           "P": torch.empty((n, n), dtype=torch.float32, device=dev), "row_ptr": torch.empty(n + 1, dtype=torch.int32, device=dev),
+           "row_ptr": torch.empty(n + 1, dtype=torch.int32, device=dev),
            "col": torch.empty(2 * n * k, dtype=torch.int32, device=dev), "weight": torch.empty(2 * n * k, dtype=torch.float32, device=dev),
            "n_edges": torch.empty((), dtype=torch.int32, device=dev)}
-    work = _work(work, workspace_bytes(n, 1, k, 1), dev)
+    if route == "dense":
+        if n >= UMAP_MAX_N:                                # before the n x n allocation
+            _fail("dm_umap_graph", 2)
+        out["P"] = torch.empty((n, n), dtype=torch.float32, device=dev)
+    work = _work(work, workspace_bytes(n, 1, k, 1, route), dev)
+    dense = (_p(out["P"]),) if route == "dense" else ()
+    name = _entry("graph", route)
     with torch.cuda.device(dev):
-        rc = _lib().dm_umap_graph(_stream(dev), _p(idx), _p(dist), n, k, int(n_epochs), _p(work), work.numel(), _p(out["rho"]),
-                                  _p(out["sigma"]), _p(out["P"]), _p(out["row_ptr"]), _p(out["col"]), _p(out["weight"]), _p(out["n_edges"]))
+        rc = getattr(_lib(), name)(_stream(dev), _p(idx), _p(dist), n, k, int(n_epochs), _p(work), work.numel(), _p(out["rho"]),
+                                   _p(out["sigma"]), *dense, _p(out["row_ptr"]), _p(out["col"]), _p(out["weight"]), _p(out["n_edges"]))
     if rc:
-        _fail("dm_umap_graph", rc)
+        _fail(name, rc)
     return out
 
 
 def layout(row_ptr, col, weight, n_edges: int, Y0, a: float, b: float, n_epochs: int = 500, seed: int = 42, first_epoch: int = 0,
-           last_epoch=None, work=None, n_neighbors: int = UMAP_MAX_NEIGHBORS):
-    """dm_umap_layout: epochs [first_epoch, last_epoch) enqueued back to back on the current stream; returns the new coordinates
+           last_epoch=None, work=None, n_neighbors: int = UMAP_MAX_NEIGHBORS, route: str = "auto"):
+    """dm_umap_layout / dm_umap_sparse_layout: epochs [first_epoch, last_epoch) enqueued back to back on the current stream; returns the new coordinates
     (Y0 is left alone).  The schedule lives in `work`: first_epoch = 0 starts it, a later first_epoch goes on from the same `work`."""
     import torch
     Y = _gpu_f32(Y0, "umapfit.layout").clone()
     dev = Y.device
     n, dim = Y.shape
     last_epoch = n_epochs if last_epoch is None else last_epoch
-    work = _work(work, workspace_bytes(n, 1, min(n_neighbors, max(n - 1, 2)), dim), dev)
+    route = pick_route(route, n)
+    name = _entry("layout", route)
+    work = _work(work, workspace_bytes(n, 1, min(n_neighbors, max(n - 1, 2)), dim, route), dev)
     with torch.cuda.device(dev):
-        rc = _lib().dm_umap_layout(_stream(dev), _p(row_ptr), _p(col), _p(weight), n, int(n_edges), dim, float(a), float(b),
+        rc = getattr(_lib(), name)(_stream(dev), _p(row_ptr), _p(col), _p(weight), n, int(n_edges), dim, float(a), float(b),
                                    int(n_epochs), int(seed) & 0x7FFFFFFF, int(first_epoch), int(last_epoch), _p(Y), _p(work), work.numel())
     if rc:
-        _fail("dm_umap_layout", rc)
+        _fail(name, rc)
     return Y
 
 
-def spectral_workspace_bytes(n: int, n_components: int) -> int:
+def spectral_workspace_bytes(n: int, n_components: int, route: str = "dense") -> int:
     out = C.c_size_t(0)
-    rc = _lib().dm_umap_spectral_workspace_bytes(int(n), int(n_components), C.byref(out))
+    name = _entry("spectral_workspace_bytes", pick_route(route, n))
+    rc = getattr(_lib(), name)(int(n), int(n_components), C.byref(out))
     if rc:
-        _fail("dm_umap_spectral_workspace_bytes", rc)
+        _fail(name, rc)
     return out.value
 
 
@@ -610,8 +736,8 @@ def spectral_status(status):
             "max_residual": s[4], "cut": s[5], "degree": int(s[6]), "block": int(s[7])}
 
 
-def spectral_init(G, dim: int, seed: int = 42, work=None, return_vectors: bool = False):
-    """dm_umap_spectral on the edge list of `fuzzy_graph` (G: 'row_ptr', 'col', 'weight' on the device): a dict of device tensors,
+def spectral_init(G, dim: int, seed: int = 42, work=None, return_vectors: bool = False, route: str = "auto"):
+    """dm_umap_spectral / dm_umap_sparse_spectral on the edge list of `fuzzy_graph` (G: 'row_ptr', 'col', 'weight' on the device): a dict of device tensors,
     'Y0' fp32 [n, dim], 'eigvals' float64 [dim + 1], 'eigvecs' float64 [n, dim + 1] (return_vectors) and 'status' float64 [8], read
     with `spectral_status`.  Nothing here waits for the device."""
     import torch
@@ -626,23 +752,28 @@ def spectral_init(G, dim: int, seed: int = 42, work=None, return_vectors: bool =
     out = {"Y0": torch.empty((n, dim), dtype=torch.float32, device=dev), "eigvals": torch.empty(dim + 1, dtype=torch.float64, device=dev),
            "eigvecs": torch.empty((n, dim + 1), dtype=torch.float64, device=dev) if return_vectors else None,
            "status": torch.empty(8, dtype=torch.float64, device=dev)}
-    work = _work(work, spectral_workspace_bytes(n, dim), dev)
+    route = pick_route(route, n)
+    name = _entry("spectral", route)
+    work = _work(work, spectral_workspace_bytes(n, dim, route), dev)
     with torch.cuda.device(dev):
-        rc = _lib().dm_umap_spectral(_stream(dev), _p(row_ptr), _p(G["col"]), _p(G["weight"]), n, int(dim), int(seed) & 0x7FFFFFFF, _p(noise),
-                                     _p(fallback), _p(work), work.numel(), _p(out["Y0"]), _p(out["eigvals"]),
-                                     _p(out["eigvecs"]) if return_vectors else None, _p(out["status"]))
+        rc = getattr(_lib(), name)(_stream(dev), _p(row_ptr), _p(G["col"]), _p(G["weight"]), n, int(dim), int(seed) & 0x7FFFFFFF, _p(noise),
+                                   _p(fallback), _p(work), work.numel(), _p(out["Y0"]), _p(out["eigvals"]),
+                                   _p(out["eigvecs"]) if return_vectors else None, _p(out["status"]))
     if rc:
-        _fail("dm_umap_spectral", rc)
+        _fail(name, rc)
     return out
 
 
 INIT_SOLVERS = ("host", "device")
 
 
-def umap_fit(X, n_components: int, n_neighbors: int = 15, seed: int = 42, n_epochs=None, work=None, times=None, init_solver: str = "host"):
+def umap_fit(X, n_components: int, n_neighbors: int = 15, seed: int = 42, n_epochs=None, work=None, times=None, init_solver: str = "host",
+             route: str = "auto"):
     """`umap.UMAP(n_components, n_neighbors).fit_transform(X)` by the rules of this module, on the device X lives on: {'embedding'
-    (device fp32 [n, c]), 'init_used', 'a', 'b', 'n_edges', 'init_solver', 'init_iters'}.  init_solver 'host': the graph comes to the
-    host once for the spectral initialisation (`spectral_init_host`).  'device': dm_umap_spectral; the only host read is its status
+    (device fp32 [n, c]), 'init_used', 'a', 'b', 'n_edges', 'init_solver', 'init_iters', 'route'}.  route: 'auto' (dense below 4096 rows,
+    sparse from there), 'dense' or 'sparse'; the same bits wherever both run with init_solver 'device'.  init_solver 'host': the graph
+    comes to the host once for the spectral initialisation (`spectral_init_host` of the dense P; on the sparse route
+    `spectral_init_sparse_host` of the edge list: the same eigh below 4096 rows, scipy's eigsh from there).  'device': dm_umap_spectral; the only host read is its status
     record, together with n_edges; a status of not converged takes the host's initialisation instead, and 'init_solver' says
     'host (device not converged)'.  The epochs run without a host round trip.  Bit-reproducible.  times: a dict that receives
     seconds per step (it synchronises)."""
@@ -655,7 +786,8 @@ def umap_fit(X, n_components: int, n_neighbors: int = 15, seed: int = 42, n_epoc
     n, d = X.shape
     dev = X.device
     n_epochs = default_epochs(n) if n_epochs is None else int(n_epochs)
-    work = _work(work, workspace_bytes(n, d, n_neighbors, n_components), dev)
+    route = pick_route(route, n)
+    work = _work(work, workspace_bytes(n, d, n_neighbors, n_components, route), dev)
 
     def mark():
         if times is not None:
@@ -664,15 +796,15 @@ def umap_fit(X, n_components: int, n_neighbors: int = 15, seed: int = 42, n_epoc
 
     a, b = find_ab_params()
     t = [mark()]
-    idx, dist = knn(X, n_neighbors, work)
+    idx, dist = knn(X, n_neighbors, work, route)
     t.append(mark())
-    G = fuzzy_graph(idx, dist, n_epochs, work)
+    G = fuzzy_graph(idx, dist, n_epochs, work, route)
     solver, iters = "host", 0
     if init_solver == "device":
         if times is not None:                              # timed: the graph's step ends before the solve is enqueued
             n_edges = int(G["n_edges"])
         t.append(mark())
-        S = spectral_init(G, n_components, seed)           # its own workspace; enqueued before anything is read
+        S = spectral_init(G, n_components, seed, route=route)       # its own workspace; enqueued before anything is read
         if times is not None:
             st = spectral_status(S["status"].cpu().numpy())
         else:
@@ -685,20 +817,25 @@ def umap_fit(X, n_components: int, n_neighbors: int = 15, seed: int = 42, n_epoc
         n_edges = int(G["n_edges"])
         t.append(mark())
     if solver != "device":
-        Y0, used = spectral_init_host(G["P"].cpu().numpy(), n_components, seed)
+        if route == "sparse":
+            Y0, used, _ = spectral_init_sparse_host(G["row_ptr"].cpu().numpy(), G["col"][:n_edges].cpu().numpy(),
+                                                    G["weight"][:n_edges].cpu().numpy(), n, n_components, seed)
+        else:
+            Y0, used = spectral_init_host(G["P"].cpu().numpy(), n_components, seed)
         Y0 = torch.from_numpy(Y0).to(dev)
     t.append(mark())
-    Y = layout(G["row_ptr"], G["col"], G["weight"], n_edges, Y0, a, b, n_epochs, seed, work=work, n_neighbors=n_neighbors)
+    Y = layout(G["row_ptr"], G["col"], G["weight"], n_edges, Y0, a, b, n_epochs, seed, work=work, n_neighbors=n_neighbors, route=route)
     t.append(mark())
     if times is not None:
         times.update(zip(("knn", "graph", "init", "layout"), np.diff(t)))
-    return {"embedding": Y, "init_used": used, "a": a, "b": b, "n_edges": n_edges, "init_solver": solver, "init_iters": iters}
+    return {"embedding": Y, "init_used": used, "a": a, "b": b, "n_edges": n_edges, "init_solver": solver, "init_iters": iters,
+            "route": route}
 
 
 def compress(X, n_groups: int, num_components: int = 32, n_neighbors: int = 15, seed: int = 42, n_epochs=None, init_solver: str = "host"):
     """`compress` of the parallel dataset (cluster.py:253-266): one fit per group of d // n_groups consecutive features (a country's
     block), the embeddings side by side.  A GPU tensor stays on the device (init_solver: `umap_fit`'s); a numpy array takes the
-    restatement."""
+    restatement.  From 4096 rows both take the sparse route by themselves (the reference's default is 10 000 rows)."""
     import torch
     on_gpu = isinstance(X, torch.Tensor) and X.is_cuda
     if isinstance(X, torch.Tensor) and not on_gpu:
@@ -712,5 +849,6 @@ def compress(X, n_groups: int, num_components: int = 32, n_neighbors: int = 15, 
         if on_gpu:
             parts.append(umap_fit(X[:, i:i + group], num_components, n_neighbors, seed, n_epochs, init_solver=init_solver)["embedding"])
         else:
-            parts.append(umap_fit_host(X[:, i:i + group], num_components, n_neighbors, seed, n_epochs)["embedding"])
+            parts.append(umap_fit_host(X[:, i:i + group], num_components, n_neighbors, seed, n_epochs,
+                                       route=pick_route("auto", X.shape[0]))["embedding"])
     return torch.cat(parts, dim=1) if on_gpu else np.hstack(parts)

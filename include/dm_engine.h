@@ -402,6 +402,33 @@ int dm_umap_spectral(void* stream, const int32_t* row_ptr, const int32_t* col, c
                      const float* noise, const float* fallback, void* work, size_t work_bytes, float* Y0_out, double* eigvals_out,
                      double* eigvecs_out, double* status_out);
 
+/* ---- UMAP above DM_UMAP_MAX_N - 1 rows: the route without the n x n graph (csrc/umap_sparse.hip) --------------------
+ * The same rules and error codes as dm_umap_*, for n < DM_UMAP_SPARSE_MAX_N; it takes smaller n too, and there every output is
+ * bit-equal to the dm_umap_* function of the same name.  (Above 4095 rows umap-learn itself turns to approximate, unseeded
+ * neighbours; these stay exact.)  `work`: at least dm_umap_sparse_workspace_bytes(n, d, n_neighbors, n_components) bytes, no n x n term.
+ *
+ * dm_umap_sparse_knn: a workgroup owns 32 rows and streams column tiles, merging each tile into a running top-k per row.
+ * dm_umap_sparse_graph: memberships per list slot; row i's edges are its out- and in-neighbours (found by a scan of idx, no atomics);
+ * there is no dense output; col_out / weight_out have room for 2 n n_neighbors entries.  A row may hold up to n - 1 edges.
+ * dm_umap_sparse_layout: dm_umap_layout's kernels; `work` needs the layout's part only.
+ * dm_umap_sparse_spectral: dm_umap_spectral's solver with the component labels in `work`
+ * (dm_umap_sparse_spectral_workspace_bytes(n, n_components) bytes).
+ * Refused without a launch: as dm_umap_*, with n >= DM_UMAP_SPARSE_MAX_N for DM_UMAP_E_N_LARGE. */
+#define DM_UMAP_SPARSE_MAX_N 65536
+int dm_umap_sparse_workspace_bytes(int n, int d, int n_neighbors, int n_components, size_t* bytes_out);
+int dm_umap_sparse_knn(void* stream, const void* X, int n, int d, int n_neighbors, void* work, size_t work_bytes, int32_t* idx_out,
+                       float* dist_out);
+int dm_umap_sparse_graph(void* stream, const int32_t* idx, const float* dist, int n, int n_neighbors, int n_epochs, void* work,
+                         size_t work_bytes, float* rho_out, float* sigma_out, int32_t* row_ptr_out, int32_t* col_out, float* weight_out,
+                         int32_t* n_edges_out);
+int dm_umap_sparse_layout(void* stream, const int32_t* row_ptr, const int32_t* col, const float* weight, int n, int n_edges,
+                          int n_components, float a, float b, int n_epochs, int seed, int first_epoch, int last_epoch, float* Y_inout,
+                          void* work, size_t work_bytes);
+int dm_umap_sparse_spectral_workspace_bytes(int n, int n_components, size_t* bytes_out);
+int dm_umap_sparse_spectral(void* stream, const int32_t* row_ptr, const int32_t* col, const float* weight, int n, int n_components, int seed,
+                            const float* noise, const float* fallback, void* work, size_t work_bytes, float* Y0_out, double* eigvals_out,
+                            double* eigvecs_out, double* status_out);
+
 /* ---- X-ray evaluation: threshold counts of a heat-map against a ground-truth box (csrc/xray_eval.hip) -------------
  * The device half of `aucpr` and `mean_typicallity` (applications/xray/compute.py:263-284).  A stream-plus-workspace function
  * (no engine handle).  Row r of the descriptor table names a map [H][W] fp32 at maps_dev + map_offset (floats, any value; two
