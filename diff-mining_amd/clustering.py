@@ -311,7 +311,7 @@ def rank_clusters(X, labels, centers, D, aggregate: str = "median", order_by: st
 
 def cluster_patches(features, D, num_clusters: int = 32, aggregate: str = "median", seed: int = 10, order_by: str = "centroid",
                     rank_features=None, max_iter: int = 300, tol: float = 1e-4, *, project=None, project_seed: int = 42,
-                    project_solver: str = "host"):
+                    project_solver: str = "host", project_disconnected: str = "random"):
     """`cluster()` of the reference as arrays: fit, then rank.  On a GPU tensor both run on the device and only the small result
     comes back; a numpy array (or a CPU tensor) takes the numpy restatement.  Returns a dict: 'clusters' = a list, best first, of
     {'cluster': id, 'rows': row ids in order (int32), 'aggregate': float}, plus 'labels', 'centers', 'seed_index', 'inertia',
@@ -321,7 +321,9 @@ def cluster_patches(features, D, num_clusters: int = 32, aggregate: str = "media
     314-317; the reference uses 5): k-means and the ranking both run on the embedding.  ('groups', G, c) = the parallel dataset's
     cluster() (cluster.py:268-289): k-means on `umapfit.compress(features, G, c)`, members ranked with order_by='farthest' on the
     original features.  project_seed seeds the projection (umap-learn is unseeded at both call sites).  project_solver: 'host' or 'device', `umapfit.umap_fit`'s
-    init_solver (where the spectral initialisation runs; a numpy input ignores it).  With a projection the dict also holds 'embedding'."""
+    init_solver (where the spectral initialisation runs; a numpy input ignores it).  project_disconnected: `umapfit.umap_fit`'s
+    disconnected ('random', the default, or 'components': a k-NN graph that falls into several components gets one spectral embedding
+    per component instead of a random start).  With a projection the dict also holds 'embedding'."""
     import torch
     embedding = None
     if project is not None:
@@ -329,16 +331,19 @@ def cluster_patches(features, D, num_clusters: int = 32, aggregate: str = "media
         if isinstance(project, (tuple, list)):
             if len(project) != 3 or project[0] != "groups":
                 raise ValueError(f"cluster_patches: project {project!r} (None, an int, or ('groups', G, n_components))")
-            embedding = umapfit.compress(features, int(project[1]), int(project[2]), seed=project_seed, init_solver=project_solver)
+            embedding = umapfit.compress(features, int(project[1]), int(project[2]), seed=project_seed, init_solver=project_solver,
+                                         disconnected=project_disconnected)
             features, rank_features, order_by = embedding, features if rank_features is None else rank_features, "farthest"
         else:
             on_dev = isinstance(features, torch.Tensor) and features.is_cuda
             if on_dev:
-                embedding = umapfit.umap_fit(features, int(project), seed=project_seed, init_solver=project_solver)["embedding"]
+                embedding = umapfit.umap_fit(features, int(project), seed=project_seed, init_solver=project_solver,
+                                             disconnected=project_disconnected)["embedding"]
             else:
                 embedding = umapfit.umap_fit_host(features.numpy() if isinstance(features, torch.Tensor) else np.asarray(features),
                                                   int(project), seed=project_seed,
-                                                  route=umapfit.pick_route("auto", len(features)))["embedding"]
+                                                  route=umapfit.pick_route("auto", len(features)),
+                                                  disconnected=project_disconnected)["embedding"]
             features = embedding
     on_gpu = isinstance(features, torch.Tensor) and features.is_cuda
     if on_gpu:

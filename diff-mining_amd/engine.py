@@ -64,6 +64,10 @@ SIGNATURES = {
     "dm_umap_sparse_layout": (_i32, [_vp] * 4 + [_i32] * 3 + [_f32, _f32] + [_i32] * 4 + [_vp, _vp, _sz]),
     "dm_umap_sparse_spectral_workspace_bytes": (_i32, [_i32, _i32, _psz]),
     "dm_umap_sparse_spectral": (_i32, [_vp] * 4 + [_i32] * 3 + [_vp] * 3 + [_sz] + [_vp] * 4),
+    "dm_umap_components_workspace_bytes": (_i32, [_i32, _psz]),
+    "dm_umap_components": (_i32, [_vp] * 5 + [_i32] * 3 + [_vp, _sz] + [_vp] * 9),
+    "dm_umap_multi_workspace_bytes": (_i32, [_i32, _i32, _psz]),
+    "dm_umap_multi_init": (_i32, [_vp] * 11 + [_i32] * 5 + [_vp] * 5 + [_sz] + [_vp] * 5),
     "dm_xray_eval_workspace_bytes": (_sz, [_i32, _i32, _i64]),
     "dm_xray_eval": (_i32, [_vp, _vp, _i32, _vp, _i32] + [_vp] * 6),
     "dm_dense_search_workspace_bytes": (_sz, [_i32, _i32, _i32]),
@@ -366,13 +370,14 @@ class _EngineBase:
             return clustering.rank_clusters(X, labels, centers, D, aggregate, order_by, rank_features, work)
 
     def umap_fit(self, X, n_components: int, n_neighbors: int = 15, seed: int = 42, n_epochs=None, work=None, init_solver: str = "host",
-                 route: str = "auto"):
+                 route: str = "auto", disconnected: str = "random"):
         """The UMAP projection of the clustering stage on this engine's device and current stream (dm_umap_knn / dm_umap_graph /
         dm_umap_layout, and dm_umap_spectral with init_solver='device', or their dm_umap_sparse_ forms by `route`; see `umapfit.umap_fit`;
         parity with umap-learn unpinned)."""
         from . import umapfit
         with self._torch.cuda.device(self.device):
-            return umapfit.umap_fit(X, n_components, n_neighbors, seed, n_epochs, work, init_solver=init_solver, route=route)
+            return umapfit.umap_fit(X, n_components, n_neighbors, seed, n_epochs, work, init_solver=init_solver, route=route,
+                                    disconnected=disconnected)
 
     def xray_eval(self, maps, boxes, thresholds=None, work=None):
         """The counts of the X-ray application's AUC-PR and the box sums for a batch of heat-maps on this engine's device and

@@ -700,17 +700,20 @@ class TypicalityScorer:
 
     @staticmethod
     def cluster_patches(features, D, num_clusters: int = 32, aggregate: str = "median", seed: int = 10, order_by: str = "centroid",
-                        rank_features=None, *, project=None, project_seed: int = 42, project_solver: str = "host"):
+                        rank_features=None, *, project=None, project_seed: int = 42, project_solver: str = "host",
+                        project_disconnected: str = "random"):
         """`Cluster.cluster` (cluster.py:312-328; parallel-dataset/cluster.py:268-289 with order_by='farthest'; ranking.py:131-149)
         as arrays: scikit-learn's `KMeans(n_clusters=num_clusters, random_state=seed)` fit of `features` [n, d], then per
         cluster the rows ordered by distance to its reference point and the clusters ranked by the median / mean of `D` [n].
         With device tensors (e.g. `dift.patch_features`' output left on the GPU) both steps run there.  Returns
         `clustering.cluster_patches`' dict; ids, paths and images stay the caller's, keyed by row.  project: None = the
         reference's default project=False; 5 = its project=True (UMAP to 5 dimensions, umapfit.py); ('groups', G, 32) = the parallel
-        dataset's per-country compress(); parity of the projection with umap-learn is unpinned; project_solver: `umap_fit`'s init_solver.  One category per call."""
+        dataset's per-country compress(); parity of the projection with umap-learn is unpinned; project_solver: `umap_fit`'s init_solver;
+        project_disconnected: its disconnected ('random', the default, or 'components').  One category per call."""
         from . import clustering
         return clustering.cluster_patches(features, D, num_clusters, aggregate, seed, order_by, rank_features, project=project,
-                                          project_seed=project_seed, project_solver=project_solver)
+                                          project_seed=project_seed, project_solver=project_solver,
+                                          project_disconnected=project_disconnected)
 
     def mine_parallel_patches(self, groups, image_sizes, set_names, origins, k_per_image: int = 5, kx: int = 64, ky: int = 64,
                               ascending: bool = False, randomized: bool = False, seed: int = 42, groups_per_call: int = 8):

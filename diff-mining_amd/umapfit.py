@@ -2,7 +2,7 @@
 (typicality/cluster.py:312-317 with c = 5; applications/parallel-dataset/cluster.py:253-270 with c = 32, k = 15, once per country's
 block of the features).  Kernels: csrc/umap.hip, csrc/umap_spectral.hip, csrc/umap_sparse.hip; C ABI: dm_umap_workspace_bytes /
 dm_umap_knn / dm_umap_graph / dm_umap_layout, dm_umap_spectral_workspace_bytes / dm_umap_spectral, and the same names after
-dm_umap_sparse_.
+dm_umap_sparse_; csrc/umap_multi.hip: dm_umap_components, dm_umap_multi_init and their workspace functions.
 
 Two routes, one set of rules.  `route='dense'` goes through the n x n graph and takes n < 4096 (UMAP_MAX_N).  `route='sparse'` works
 from the neighbour lists alone, takes n < 65536 (UMAP_SPARSE_MAX_N) and gives the same bits wherever both run; 'auto' (the device
@@ -10,7 +10,8 @@ functions' default) is dense below 4096 rows and sparse from there.  The paralle
 (cluster.py:391), which is why the sparse route exists.  Above 4095 rows umap-learn itself switches to approximate NN-descent
 neighbours, unseeded; this module stays exact there, so nothing of umap-learn's is bit-comparable above the limit, and parity
 stays unpinned on both routes.  Not measured: real DIFT features at 10 000 rows, whether real graphs of that size are connected (a
-disconnected one takes the random initialisation, as below), and quality against umap-learn.
+disconnected one takes the random initialisation, as below, unless disconnected='components' is asked for), and quality against
+umap-learn.
 
 PARITY UNPINNED.  The rules below restate umap-learn 0.5.6 (the reference's environment.yaml) at the two call sites' settings from
 the paper and from memory: umap-learn was not at hand to record its outputs.  tests/make_golden_umap.py records them wherever it is
@@ -36,8 +37,11 @@ negative_sample_rate 5, set_op_mix_ratio 1, local_connectivity 1, repulsion_stre
   schedule  fp32: eps_e = max(P) / P_e, epn_e = eps_e / 5, next_e = eps_e, next_neg_e = epn_e.
   init      (host; runs once, the graph is dense below 4096 rows) eigenvectors 1..dim of I - D^-1/2 P D^-1/2 (numpy eigh), sign
             fixed so the largest-magnitude entry is positive, scaled to 10 / max|.|, plus seeded N(0, 1e-4) noise.  A disconnected
-            graph or dim + 1 >= n: umap-learn's init='random', seeded uniform(-10, 10) (its multi-component spectral layout is out
-            of scope).  Either way each coordinate is then rescaled to [0, 10], as umap-learn does for every init.
+            graph or dim + 1 >= n: umap-learn's init='random', seeded uniform(-10, 10).  Either way each coordinate is then rescaled
+            to [0, 10], as umap-learn does for every init.  Opt-in, disconnected='components': umap-learn's multi-component
+            spectral layout instead of the random fallback -- one spectral embedding per connected component around a
+            meta-embedding of the components; the rules are above `multi_component_init_host`, the device runs them in
+            csrc/umap_multi.hip.  The default, 'random', is the behaviour and the bits as before.
             init_solver='device' finds the same eigenvectors from the edge list on the device instead (dm_umap_spectral; the rules
             are above `spectral_init_iter_host`); the default is the host.
   layout    SYNCHRONOUS within an epoch -- the departure.  umap-learn's numba loop updates coordinates in place from parallel
@@ -76,7 +80,7 @@ MIN_K_DIST_SCALE = 1e-3
 # dm_umap_* return codes (include/dm_engine.h)
 ERRORS = {1: "null argument", 2: f"n >= {UMAP_MAX_N} (dense route) or {UMAP_SPARSE_MAX_N} (sparse route)", 3: "n_neighbors >= n", 4: f"n_neighbors outside [2, {UMAP_MAX_NEIGHBORS}]",
           5: f"n_components outside [1, {UMAP_MAX_COMPONENTS}]", 6: "d < 1", 7: "bad epoch range", 8: "workspace too small",
-          9: "bad edge count", 10: "HIP error"}
+          9: "bad edge count", 10: "HIP error", 11: "component count outside [1, min(n, 1024)]"}
 
 
 def default_epochs(n: int) -> int:
@@ -315,12 +319,20 @@ def spectral_init_sparse_host(row_ptr, col, weight, n: int, dim: int, seed: int 
 def _spectral_tail(vec, noise):
     """The end of the spectral initialisation, shared by both solvers: eigenvectors 1..dim (float64 [n, dim]) -> Y0 fp32 [n, dim].
     Sign by the largest-magnitude entry, 10 / max|.|, the fp32 cast, the noise (fp32 [n, dim]), the rescale to [0, 10]."""
+    return _init_tail(_fix_signs(vec), noise)
+
+
+def _fix_signs(vec):
+    """float64 copy of `vec` with every column's largest-magnitude entry (the first on a tie) made positive"""
     Y = np.array(vec, dtype=np.float64)
-    dim = Y.shape[1]
     top = np.abs(Y).argmax(axis=0)
-    Y *= np.sign(Y[top, np.arange(dim)])[None, :]
-    Y = (Y * (10.0 / np.abs(Y).max())).astype(np.float32) + noise
-    return _rescale(Y)
+    Y *= np.sign(Y[top, np.arange(Y.shape[1])])[None, :]
+    return Y
+
+
+def _init_tail(R, noise):
+    """The last steps of every non-random initialisation: float64 [n, dim] -> 10 / max|.|, the fp32 cast, the noise, the rescale."""
+    return _rescale((R * (10.0 / np.abs(R).max())).astype(np.float32) + noise)
 
 
 # ---- the iterative solver of the spectral initialisation: what csrc/umap_spectral.hip runs, stated in numpy --------------------------
@@ -492,6 +504,234 @@ def spectral_init_iter_host(row_ptr, col, weight, n: int, dim: int, seed: int = 
     return _spectral_tail(info["eigvecs"][:, 1:], noise), "spectral", info
 
 
+# ---- a disconnected graph: one spectral embedding per component (opt-in: disconnected='components') -----------------------------------
+# PARITY UNPINNED, like the rest of this module: umap-learn 0.5.6's `multi_component_layout` / `component_layout`, restated from
+# memory.  Deliberate departures are marked (+).  What csrc/umap_multi.hip runs, stated in numpy:
+#   components  labels by min-label propagation; ids 0 .. c - 1 ascend with each component's smallest vertex (scipy's
+#               connected_components order).  c = 1: the spectral initialisation as before; dim + 1 >= n: the random one as before;
+#               c > MULTI_MAX_COMP: the random one (+: a cap on the host eigh of the meta-embedding; a k-NN component holds at least k
+#               rows, so 10 000 rows at k = 15 cannot reach it).
+#   grouping    vertices grouped by component, ascending index inside (the stable permutation); each component's sub-graph keeps that
+#               order, so the column renumbering is monotone and every row's edge order survives.
+#   centroids   only when c > 2 dim: the fp64 sum of double(X[i]) over the component's rows in ascending row index, separate adds,
+#               divided by the size.
+#   meta        `meta_embedding_host`.  c <= 2 dim: the table vstack([I_k | 0], -[I_k | 0])[:c], k = ceil(c / 2).  Otherwise the
+#               spectral embedding of A = exp(-|cent_l - cent_m|^2) (zero diagonal): eigenvectors 1 .. dim of I - D^-1/2 A D^-1/2,
+#               rows divided by sqrt(deg) (scikit-learn SpectralEmbedding's recovery), sign by each column's largest-magnitude entry
+#               (+: scikit-learn's flip rule differs), the whole divided by its largest entry.  Degenerate -- a zero row sum of A, a
+#               disconnected A > 0, or two coinciding meta rows -- means the random initialisation with the reason 'meta degenerate'
+#               (+: umap-learn has no defined behaviour once exp(-d^2) underflows).
+#   range       range_l = half the smallest positive distance from meta[l] to another meta row.
+#   component   size < 2 dim or size <= dim + 1: R[i] = meta[l] + range_l unit[i], unit = RandomState(seed).uniform(-1, 1, (n, dim))
+#               drawn up front and indexed by the vertex's own row (+: umap-learn draws per component in sequence; here the draw does
+#               not depend on the graph, so the device takes it as an upload).  Otherwise E = eigenvectors 1 .. dim of the component's
+#               own normalised Laplacian, signs as `_spectral_tail`, R[i] = E[i] (range_l / max|E|) + meta[l].
+#   tail        `_init_tail`: Y0 = _rescale(fp32(R (10 / max|R|)) + noise), the noise of the spectral initialisation.
+MULTI_MAX_COMP = 1024        # DM_UMAP_MULTI_MAX_COMP
+DISCONNECTED = ("random", "components")
+MULTI_SOLVERS = ("host", "iter")
+
+
+def component_labels_host(row_ptr, col, n: int):
+    """int64 [n]: every vertex's smallest reachable vertex, by the min-label propagation of `components_host`"""
+    row_ptr = np.asarray(row_ptr, np.int64)
+    col = np.asarray(col, np.int64)[:row_ptr[-1]]
+    head = np.repeat(np.arange(n), np.diff(row_ptr))
+    label = np.arange(n)
+    while True:
+        new = label.copy()
+        np.minimum.at(new, head, label[col])
+        if np.array_equal(new, label):
+            return label
+        label = new
+
+
+def component_groups_host(row_ptr, col, weight, n: int, X=None):
+    """The components step of the rule above, as dm_umap_components lays it out.  A dict: 'comp' int32 [n], 'n_comp', 'offsets' int32
+    [c + 1], 'perm' int32 [n] (the vertex at each grouped position), 'edge_offsets' int32 [c + 1], 'sub_row_ptr' int32 [n + c]
+    (component l's own row pointer, size_l + 1 entries from index offsets[l] + l, starting at 0), 'sub_col' (positions inside the
+    component), 'sub_weight', and with X 'centroids' float64 [c, d]."""
+    row_ptr = np.asarray(row_ptr, np.int64)
+    E = int(row_ptr[-1])
+    col = np.asarray(col, np.int64)[:E]
+    weight = np.asarray(weight, np.float32)[:E]
+    label = component_labels_host(row_ptr, col, n)
+    roots = np.flatnonzero(label == np.arange(n))                     # ascending: the order of the ids
+    c = len(roots)
+    rank = np.zeros(n, np.int64)
+    rank[roots] = np.arange(c)
+    comp = rank[label]
+    perm = np.argsort(comp, kind="stable")
+    offsets = np.zeros(c + 1, np.int64)
+    offsets[1:] = np.cumsum(np.bincount(comp, minlength=c))
+    inv = np.empty(n, np.int64)
+    inv[perm] = np.arange(n)
+    head = np.repeat(np.arange(n), np.diff(row_ptr))
+    keep = comp[col] == comp[head]                                    # all of them on a symmetric list
+    e_order = np.argsort(inv[head], kind="stable")                    # edges by grouped row, each row's order kept
+    e_order = e_order[keep[e_order]]
+    g_head = inv[head[e_order]]
+    sub_col = inv[col[e_order]] - offsets[comp[col[e_order]]]
+    gp = np.zeros(n + 1, np.int64)
+    gp[1:] = np.cumsum(np.bincount(g_head, minlength=n))
+    edge_offsets = gp[offsets]
+    sub_row_ptr = np.zeros(n + c, np.int64)
+    for l in range(c):
+        lo, hi = offsets[l], offsets[l + 1]
+        sub_row_ptr[lo + l:hi + l + 1] = gp[lo:hi + 1] - gp[lo]
+    out = {"comp": comp.astype(np.int32), "n_comp": c, "offsets": offsets.astype(np.int32), "perm": perm.astype(np.int32),
+           "edge_offsets": edge_offsets.astype(np.int32), "sub_row_ptr": sub_row_ptr.astype(np.int32), "sub_col": sub_col.astype(np.int32),
+           "sub_weight": weight[e_order].copy()}
+    if X is not None:
+        Xd = np.ascontiguousarray(X, dtype=np.float32).astype(np.float64)
+        cent = np.zeros((c, Xd.shape[1]), np.float64)
+        for l in range(c):
+            s = np.zeros(Xd.shape[1], np.float64)
+            for i in perm[offsets[l]:offsets[l + 1]]:                 # ascending row index, one add per row
+                s = s + Xd[i]
+            cent[l] = s / float(offsets[l + 1] - offsets[l])
+        out["centroids"] = cent
+    return out
+
+
+def sub_graph(groups, l: int):
+    """(row_ptr, col, weight, size) of component l from `component_groups_host`'s (or, brought to the host, `components`') dict"""
+    off, end = int(groups["offsets"][l]), int(groups["offsets"][l + 1])
+    e0, e1 = int(groups["edge_offsets"][l]), int(groups["edge_offsets"][l + 1])
+    return groups["sub_row_ptr"][off + l:end + l + 1], groups["sub_col"][e0:e1], groups["sub_weight"][e0:e1], end - off
+
+
+def meta_embedding_host(cent, c: int, dim: int):
+    """Where the components go, by the rule above: a dict with 'meta' float64 [c, dim], 'range' float64 [c], 'kind' ('table' |
+    'affinity') and 'reason' (None, or 'meta degenerate' with 'detail': 'zero row sum' | 'disconnected' | 'coincident rows'; then
+    there is no 'meta').  cent: float64 [c, d], read only when c > 2 dim."""
+    out = {"kind": "table" if c <= 2 * dim else "affinity", "reason": None, "detail": None}
+
+    def degenerate(detail):
+        out.update(reason="meta degenerate", detail=detail)
+        return out
+
+    if c <= 2 * dim:
+        k = (c + 1) // 2
+        base = np.hstack([np.eye(k), np.zeros((k, dim - k))])
+        meta = np.vstack([base, -base])[:c]
+    else:
+        from scipy.sparse.csgraph import connected_components
+        cent = np.asarray(cent, np.float64)[:c]
+        diff = cent[:, None, :] - cent[None, :, :]
+        A = np.exp(-(diff * diff).sum(axis=2))
+        np.fill_diagonal(A, 0.0)
+        deg = A.sum(axis=1)
+        if not np.all(deg > 0):
+            return degenerate("zero row sum")
+        if connected_components(A > 0, directed=False)[0] != 1:
+            return degenerate("disconnected")
+        isd = 1.0 / np.sqrt(deg)
+        L = np.eye(c) - isd[:, None] * A * isd[None, :]
+        _, vec = np.linalg.eigh((L + L.T) * 0.5)
+        meta = _fix_signs(vec[:, 1:dim + 1] * isd[:, None])
+        meta = meta / meta.max()
+        if not np.all(np.isfinite(meta)):
+            return degenerate("coincident rows")
+    rng = meta_range_host(meta)
+    if rng is None:
+        return degenerate("coincident rows")
+    out.update(meta=meta, range=rng)
+    return out
+
+
+def meta_range_host(meta):
+    """float64 [c]: half the smallest positive Euclidean distance from each meta row to another; None if two rows coincide"""
+    meta = np.asarray(meta, np.float64)
+    c = len(meta)
+    dist = np.sqrt(((meta[:, None, :] - meta[None, :, :]) ** 2).sum(axis=2))
+    dist[np.arange(c), np.arange(c)] = np.inf
+    if not np.all(dist > 0):
+        return None
+    return dist.min(axis=1) / 2.0
+
+
+def multi_component_plan(sizes, dim: int):
+    """int32 [c]: 1 where a component gets its own spectral embedding, 0 where it is placed uniformly around its meta row"""
+    sizes = np.asarray(sizes)
+    return (~((sizes < 2 * dim) | (sizes <= dim + 1))).astype(np.int32)
+
+
+def multi_host_arrays(n: int, dim: int, seed: int = 42):
+    """unit float64 [n, dim]: the uniform(-1, 1) draw of the uniformly placed components, by the vertex's own row"""
+    return np.random.RandomState(seed).uniform(low=-1.0, high=1.0, size=(n, dim))
+
+
+def place_components_host(groups, meta, plan, eigvecs, dim: int, seed: int = 42):
+    """Steps 5 and 6 of the rule above from given eigenvectors (float64 [n, dim + 1], rows in grouped order; read where plan is 1):
+    (Y0 fp32 [n, dim], R float64 [n, dim]).  The device's eigenvectors go through this in the GPU tests."""
+    offsets, perm = np.asarray(groups["offsets"], np.int64), np.asarray(groups["perm"], np.int64)
+    n = len(perm)
+    unit = multi_host_arrays(n, dim, seed)
+    R = np.zeros((n, dim), np.float64)
+    for l in range(len(offsets) - 1):
+        rows = perm[offsets[l]:offsets[l + 1]]
+        if plan[l]:
+            E = _fix_signs(np.asarray(eigvecs, np.float64)[offsets[l]:offsets[l + 1], 1:dim + 1])
+            R[rows] = E * (meta["range"][l] / np.abs(E).max()) + meta["meta"][l]
+        else:
+            R[rows] = meta["meta"][l] + meta["range"][l] * unit[rows]
+    noise = np.random.RandomState(seed).normal(scale=0.0001, size=(n, dim)).astype(np.float32)
+    return _init_tail(R, noise), R
+
+
+def multi_component_init_host(row_ptr, col, weight, X, dim: int, seed: int = 42, solver: str = "host", dense_below: int = UMAP_MAX_N):
+    """(Y0 fp32 [n, dim], 'components' | 'spectral' | 'random', info) from the edge list and X fp32 [n, d], by the rule above.
+    PARITY UNPINNED (a restatement of umap-learn's multi_component_layout from memory; the departures are marked there).
+    solver 'host': per component the eigh / eigsh choice `spectral_init_sparse_host` makes at that component's size; 'iter':
+    `spectral_init_iter_host` per component, which is what the device runs.  One component, or dim + 1 >= n, is today's function of
+    that solver, bit for bit; so is every fallback ('reason' says why: 'more than 1024 components' | 'meta degenerate').  info:
+    'n_comp', 'sizes', 'plan' (1 solved / 0 uniform), 'meta_kind', 'reason', 'iters' and 'status' per component, 'groups', 'meta',
+    'R', 'eigvecs' (float64 [n, dim + 1], grouped order) and 'eigvals' (float64 [c, dim + 1])."""
+    if solver not in MULTI_SOLVERS:
+        raise ValueError(f"multi_component_init_host: solver {solver!r} is not one of {MULTI_SOLVERS}")
+    X = np.ascontiguousarray(X, dtype=np.float32)
+    n = X.shape[0]
+    row_ptr = np.asarray(row_ptr, np.int64)
+    E = int(row_ptr[-1])
+    col, weight = np.asarray(col)[:E], np.asarray(weight, np.float32)[:E]
+
+    def single(rp, cl, w, rows):
+        if solver == "iter":
+            return spectral_init_iter_host(rp, cl, w, rows, dim, seed)
+        return spectral_init_sparse_host(rp, cl, w, rows, dim, seed, dense_below)
+
+    n_comp = components_host(row_ptr, col, n) if n else 0
+    info = {"n_comp": int(n_comp), "sizes": None, "plan": None, "meta_kind": None, "reason": None, "iters": [], "status": []}
+    if n_comp == 1 or dim + 1 >= n or n_comp > MULTI_MAX_COMP:
+        Y0, used, inner = single(row_ptr, col, weight, n)
+        info.update(inner=inner, reason=None if n_comp == 1 else "n_components + 1 >= n" if dim + 1 >= n else f"more than {MULTI_MAX_COMP} components")
+        return Y0, used, info
+    groups = component_groups_host(row_ptr, col, weight, n, X if n_comp > 2 * dim else None)
+    sizes = np.diff(groups["offsets"])
+    meta = meta_embedding_host(groups.get("centroids"), n_comp, dim)
+    info.update(sizes=sizes, meta_kind=meta["kind"], groups=groups, meta=meta)
+    if meta["reason"]:
+        info.update(reason=meta["reason"], detail=meta["detail"])
+        return _rescale(np.random.RandomState(seed).uniform(low=-10.0, high=10.0, size=(n, dim))), "random", info
+    plan = multi_component_plan(sizes, dim)
+    vecs, vals = np.zeros((n, dim + 1), np.float64), np.zeros((n_comp, dim + 1), np.float64)
+    for l in range(n_comp):
+        if not plan[l]:
+            info["iters"].append(0)
+            info["status"].append("uniform")
+            continue
+        rp, cl, w, rows = sub_graph(groups, l)
+        _, _, inner = single(rp, cl, w, rows)
+        vecs[groups["offsets"][l]:groups["offsets"][l + 1]] = inner["eigvecs"]
+        vals[l] = inner["eigvals"]
+        info["iters"].append(int(inner.get("iters", 0)))
+        info["status"].append(inner.get("status", "converged"))
+    Y0, R = place_components_host(groups, meta, plan, vecs, dim, seed)
+    info.update(plan=plan, R=R, eigvecs=vecs, eigvals=vals)
+    return Y0, "components", info
+
+
 _M32 = np.uint64(0xFFFFFFFF)
 
 
@@ -579,11 +819,19 @@ def layout_host(row_ptr, col, weight, Y0, a, b, n_epochs: int = 500, seed: int =
     return Y, (eps, epn, nxt, nneg)
 
 
+def _check_disconnected(disconnected):
+    if disconnected not in DISCONNECTED:
+        raise ValueError(f"umap: disconnected {disconnected!r} is not one of {DISCONNECTED}")
+
+
 def umap_fit_host(X, n_components: int, n_neighbors: int = 15, seed: int = 42, n_epochs=None, dtype=np.float32, times=None,
-                  route: str = "dense"):
+                  route: str = "dense", disconnected: str = "random"):
     """The whole restatement on a numpy array: {'embedding' fp32 [n, c], 'init_used', 'a', 'b', 'n_edges', 'route'}.  times: a dict
     that receives seconds per step.  route: 'dense' (the default: n < 4096) or 'sparse' (n < 65536, no n x n array; the initialisation
-    is `spectral_init_sparse_host`) -- the restatement does not choose by itself."""
+    is `spectral_init_sparse_host`) -- the restatement does not choose by itself.  disconnected: 'random' (the default: a graph of
+    several components takes the random initialisation) or 'components' (`multi_component_init_host`; 'init_used' may then be
+    'components' and 'init_info' holds its info)."""
+    _check_disconnected(disconnected)
     X = np.ascontiguousarray(X, dtype=np.float32)
     n, d = X.shape
     _check(n, d, n_neighbors, n_components, route)
@@ -594,7 +842,10 @@ def umap_fit_host(X, n_components: int, n_neighbors: int = 15, seed: int = 42, n
     t.append(time.perf_counter())
     G = fuzzy_graph_host(idx, dist, n_epochs, route=route)
     t.append(time.perf_counter())
-    if route == "sparse":
+    init_info = None
+    if disconnected == "components":
+        Y0, used, init_info = multi_component_init_host(G["row_ptr"], G["col"], G["weight"], X, n_components, seed)
+    elif route == "sparse":
         Y0, used, _ = spectral_init_sparse_host(G["row_ptr"], G["col"], G["weight"], n, n_components, seed)
     else:
         Y0, used = spectral_init_host(G["P"], n_components, seed)
@@ -603,7 +854,10 @@ def umap_fit_host(X, n_components: int, n_neighbors: int = 15, seed: int = 42, n
     t.append(time.perf_counter())
     if times is not None:
         times.update(zip(("knn", "graph", "init", "layout"), np.diff(t)))
-    return {"embedding": Y.astype(np.float32), "init_used": used, "a": a, "b": b, "n_edges": int(len(G["col"])), "init": Y0, "route": route}
+    out = {"embedding": Y.astype(np.float32), "init_used": used, "a": a, "b": b, "n_edges": int(len(G["col"])), "init": Y0, "route": route}
+    if init_info is not None:
+        out["init_info"] = init_info
+    return out
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -764,11 +1018,149 @@ def spectral_init(G, dim: int, seed: int = 42, work=None, return_vectors: bool =
     return out
 
 
+def components(G, X=None, work=None):
+    """dm_umap_components on the edge list of `fuzzy_graph` (G: 'row_ptr', 'col', 'weight' on the device; either route's): a dict of
+    device tensors laid out as `component_groups_host` lays them out, sized for any component count -- 'comp' int32 [n], 'count' int32
+    [1], 'offsets' and 'edge_offsets' int32 [n + 1] (c + 1 entries count), 'perm' int32 [n], 'sub_row_ptr' int32 [2 n + 1] (n + c
+    count), 'sub_col' / 'sub_weight' (as many slots as G's; edge_offsets[c] count), and with X (fp32 [n, d] on the device)
+    'centroids' float64 [min(n, 1024), d].  Nothing here waits for the device."""
+    import torch
+    row_ptr = G["row_ptr"]
+    if not (isinstance(row_ptr, torch.Tensor) and row_ptr.is_cuda):
+        raise EngineError("umapfit.components: the graph must be on the GPU (component_groups_host is the numpy restatement)")
+    dev = row_ptr.device
+    n = row_ptr.numel() - 1
+    cap = int(min(G["col"].numel(), G["weight"].numel()))
+    d = 1
+    if X is not None:
+        X = _gpu_f32(X, "umapfit.components")
+        if X.dim() != 2 or X.shape[0] != n:
+            raise EngineError(f"umapfit.components: X must be [{n}, d], got {tuple(X.shape)}")
+        d = X.shape[1]
+    i32 = dict(dtype=torch.int32, device=dev)
+    out = {"comp": torch.empty(max(n, 0), **i32), "count": torch.empty(1, **i32), "offsets": torch.empty(max(n, 0) + 1, **i32),
+           "perm": torch.empty(max(n, 0), **i32), "edge_offsets": torch.empty(max(n, 0) + 1, **i32),
+           "sub_row_ptr": torch.empty(2 * max(n, 0) + 1, **i32), "sub_col": torch.empty(cap, **i32),
+           "sub_weight": torch.empty(cap, dtype=torch.float32, device=dev),
+           "centroids": torch.empty((min(max(n, 0), MULTI_MAX_COMP), d), dtype=torch.float64, device=dev) if X is not None else None}
+    need = C.c_size_t(0)
+    rc = _lib().dm_umap_components_workspace_bytes(n, C.byref(need))
+    if rc:
+        _fail("dm_umap_components_workspace_bytes", rc)
+    work = _work(work, need.value, dev)
+    with torch.cuda.device(dev):
+        rc = _lib().dm_umap_components(_stream(dev), _p(row_ptr), _p(G["col"]), _p(G["weight"]), _p(X) if X is not None else None, n, d, cap,
+                                       _p(work), work.numel(), _p(out["comp"]), _p(out["count"]), _p(out["offsets"]), _p(out["perm"]),
+                                       _p(out["edge_offsets"]), _p(out["sub_row_ptr"]), _p(out["sub_col"]), _p(out["sub_weight"]),
+                                       _p(out["centroids"]) if X is not None else None)
+    if rc:
+        _fail("dm_umap_components", rc)
+    return out
+
+
+def components_to_host(comps, centroids: bool = False):
+    """`components`' dict on the host in `component_groups_host`'s form, trimmed to the component count.  Two reads at most: the
+    integers first (c decides how much of the rest counts), the centroids if asked."""
+    import torch
+    n = comps["comp"].numel()
+    ints = torch.cat([comps["count"], comps["offsets"], comps["edge_offsets"], comps["comp"], comps["perm"], comps["sub_row_ptr"]]).cpu().numpy()
+    c = int(ints[0])
+    cut = np.cumsum([1, n + 1, n + 1, n, n, 2 * n + 1])
+    offsets, edge_offsets, comp, perm, srp = (ints[a:b] for a, b in zip(cut[:-1], cut[1:]))
+    total = int(edge_offsets[c])
+    out = {"comp": comp.copy(), "n_comp": c, "offsets": offsets[:c + 1].copy(), "perm": perm.copy(), "edge_offsets": edge_offsets[:c + 1].copy(),
+           "sub_row_ptr": srp[:n + c].copy(), "sub_col": comps["sub_col"][:total].cpu().numpy(), "sub_weight": comps["sub_weight"][:total].cpu().numpy()}
+    if centroids and comps["centroids"] is not None:
+        out["centroids"] = comps["centroids"][:min(c, MULTI_MAX_COMP)].cpu().numpy()
+    return out
+
+
+def multi_workspace_bytes(n: int, n_components: int) -> int:
+    out = C.c_size_t(0)
+    rc = _lib().dm_umap_multi_workspace_bytes(int(n), int(n_components), C.byref(out))
+    if rc:
+        _fail("dm_umap_multi_workspace_bytes", rc)
+    return out.value
+
+
+def multi_status(status):
+    """The status records of dm_umap_multi_init (float64 [c, 8], on the host), one dict per component as `spectral_status` reads
+    them; 'status' is 'uniform' for a component that was placed, not solved."""
+    out = []
+    for rec in np.asarray(status, np.float64).reshape(-1, 8):
+        st = spectral_status(rec)
+        if rec[0] == 2.0:
+            st.update(init_used="uniform", status="uniform")
+        out.append(st)
+    return out
+
+
+def multi_component_init(G, X, dim: int, seed: int = 42, work=None, route: str = "auto", comps=None):
+    """The device's initialisation with disconnected='components' (dm_umap_components, dm_umap_multi_init; `multi_component_init_host`
+    with solver='iter' is the restatement).  G: `fuzzy_graph`'s dict, X: fp32 [n, d], both on the device.  The component count, the
+    offsets and the edge offsets are read once (a second read takes the centroids when there are more than 2 dim components); the host
+    makes the meta-embedding (`meta_embedding_host`) and the plan, uploads them, and everything else is enqueued without waiting.
+    One component takes `spectral_init` (dm_umap_spectral on `route`) and every fallback its random Y0, bit for bit as before.
+    Returns a dict: 'Y0' (device fp32 [n, dim]), 'status' (device float64 [c, 8]; read with `multi_status`, or `spectral_status` when
+    'mode' is 'single'), 'mode' ('multi' | 'single' | 'random'), 'info' ('n_comp', 'sizes', 'plan', 'meta_kind', 'reason', 'meta') and
+    for 'multi' also 'R', 'eigvals', 'eigvecs' (grouped order) and 'comps'."""
+    import torch
+    row_ptr = G["row_ptr"]
+    if not (isinstance(row_ptr, torch.Tensor) and row_ptr.is_cuda):
+        raise EngineError("umapfit.multi_component_init: the graph must be on the GPU (multi_component_init_host is the numpy restatement)")
+    dev = row_ptr.device
+    n = row_ptr.numel() - 1
+    if dim < 1 or dim > UMAP_MAX_COMPONENTS:
+        raise EngineError(f"umapfit.multi_component_init: n_components {dim} outside [1, {UMAP_MAX_COMPONENTS}]")
+    X = _gpu_f32(X, "umapfit.multi_component_init")
+    # The centroids are computed whether or not c > 2 dim will need them: c is not known before the read below, the pass over X is
+    # inside the 1.2 ms the whole step takes at 10 000 x 128, and a second call after the read would cost a launch round more.
+    comps = components(G, X) if comps is None else comps
+    head = torch.cat([comps["count"], comps["offsets"], comps["edge_offsets"]]).cpu().numpy()          # the added host read
+    c = int(head[0])
+    offsets, edge_offsets = np.ascontiguousarray(head[1:c + 2]), np.ascontiguousarray(head[n + 2:n + c + 3])
+    sizes = np.diff(offsets)
+    info = {"n_comp": c, "sizes": sizes, "plan": None, "meta_kind": None, "reason": None, "meta": None}
+    if c == 1 or dim + 1 >= n or c > MULTI_MAX_COMP:
+        S = spectral_init(G, dim, seed, route=route)
+        info["reason"] = None if c == 1 else "n_components + 1 >= n" if dim + 1 >= n else f"more than {MULTI_MAX_COMP} components"
+        return {"Y0": S["Y0"], "status": S["status"], "mode": "single", "info": info}
+    if c > 2 * dim and comps.get("centroids") is None:
+        raise EngineError(f"umapfit.multi_component_init: {c} components > 2 x {dim} need the centroids: call components(G, X) with X")
+    cent = comps["centroids"][:c].cpu().numpy() if c > 2 * dim else None
+    meta = meta_embedding_host(cent, c, dim)
+    info.update(meta_kind=meta["kind"], meta=meta)
+    noise, fallback = spectral_host_arrays(n, dim, seed)
+    if meta["reason"]:
+        info.update(reason=meta["reason"], detail=meta["detail"])
+        return {"Y0": torch.from_numpy(fallback).to(dev), "status": None, "mode": "random", "info": info}
+    plan = multi_component_plan(sizes, dim)
+    info["plan"] = plan
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)        # noqa: E731
+    d_plan, d_meta, d_range, d_unit, d_noise = up(plan), up(meta["meta"]), up(meta["range"]), up(multi_host_arrays(n, dim, seed)), up(noise)
+    m = dim + 1
+    out = {"Y0": torch.empty((n, dim), dtype=torch.float32, device=dev), "R": torch.empty((n, dim), dtype=torch.float64, device=dev),
+           "eigvals": torch.empty((c, m), dtype=torch.float64, device=dev), "eigvecs": torch.empty((n, m), dtype=torch.float64, device=dev),
+           "status": torch.empty((c, 8), dtype=torch.float64, device=dev), "mode": "multi", "info": info, "comps": comps}
+    work = _work(work, multi_workspace_bytes(n, dim), dev)
+    h_off, h_eoff, h_plan = (np.ascontiguousarray(a, dtype=np.int32) for a in (offsets, edge_offsets, plan))
+    hp = lambda a: a.ctypes.data_as(C.c_void_p)                               # noqa: E731
+    with torch.cuda.device(dev):
+        rc = _lib().dm_umap_multi_init(_stream(dev), _p(comps["sub_row_ptr"]), _p(comps["sub_col"]), _p(comps["sub_weight"]), _p(comps["perm"]),
+                                       _p(comps["comp"]), _p(comps["offsets"]), _p(d_plan), hp(h_off), hp(h_eoff), hp(h_plan), n, c,
+                                       comps["sub_col"].numel(), int(dim), int(seed) & 0x7FFFFFFF, _p(d_meta), _p(d_range), _p(d_unit),
+                                       _p(d_noise), _p(work), work.numel(), _p(out["Y0"]), _p(out["R"]), _p(out["eigvals"]),
+                                       _p(out["eigvecs"]), _p(out["status"]))
+    if rc:
+        _fail("dm_umap_multi_init", rc)
+    return out
+
+
 INIT_SOLVERS = ("host", "device")
 
 
 def umap_fit(X, n_components: int, n_neighbors: int = 15, seed: int = 42, n_epochs=None, work=None, times=None, init_solver: str = "host",
-             route: str = "auto"):
+             route: str = "auto", disconnected: str = "random"):
     """`umap.UMAP(n_components, n_neighbors).fit_transform(X)` by the rules of this module, on the device X lives on: {'embedding'
     (device fp32 [n, c]), 'init_used', 'a', 'b', 'n_edges', 'init_solver', 'init_iters', 'route'}.  route: 'auto' (dense below 4096 rows,
     sparse from there), 'dense' or 'sparse'; the same bits wherever both run with init_solver 'device'.  init_solver 'host': the graph
@@ -776,10 +1168,15 @@ def umap_fit(X, n_components: int, n_neighbors: int = 15, seed: int = 42, n_epoc
     `spectral_init_sparse_host` of the edge list: the same eigh below 4096 rows, scipy's eigsh from there).  'device': dm_umap_spectral; the only host read is its status
     record, together with n_edges; a status of not converged takes the host's initialisation instead, and 'init_solver' says
     'host (device not converged)'.  The epochs run without a host round trip.  Bit-reproducible.  times: a dict that receives
-    seconds per step (it synchronises)."""
+    seconds per step (it synchronises).  disconnected: 'random' (the default: a graph of several components takes the random
+    initialisation, as above) or 'components': every component gets its own spectral embedding around a meta-embedding of the
+    components (`multi_component_init_host` states the rule).  With init_solver 'host' the graph comes to the host as before and the
+    restatement runs; with 'device', `multi_component_init` (one more host read: the component count and offsets); 'init_used' is
+    then 'components', or 'spectral' / 'random' where the rule falls back to them, and 'init_reason' says why."""
     import torch
     if init_solver not in INIT_SOLVERS:
         raise ValueError(f"umap_fit: init_solver {init_solver!r} is not one of {INIT_SOLVERS}")
+    _check_disconnected(disconnected)
     X = _gpu_f32(X, "umapfit.umap_fit")
     if X.dim() != 2:
         raise EngineError(f"umapfit.umap_fit: X must be [n, d], got {tuple(X.shape)}")
@@ -799,8 +1196,33 @@ def umap_fit(X, n_components: int, n_neighbors: int = 15, seed: int = 42, n_epoc
     idx, dist = knn(X, n_neighbors, work, route)
     t.append(mark())
     G = fuzzy_graph(idx, dist, n_epochs, work, route)
-    solver, iters = "host", 0
-    if init_solver == "device":
+    solver, iters, reason = "host", 0, None
+    multi = disconnected == "components"
+    if init_solver == "device" and multi:
+        if times is not None:
+            n_edges = int(G["n_edges"])
+        t.append(mark())
+        M = multi_component_init(G, X, n_components, seed, route=route)
+        reason = M["info"]["reason"]
+        if M["status"] is None:                            # a fallback the host decided: nothing of the device's to read
+            if times is None:
+                n_edges = int(G["n_edges"])
+            Y0, used, solver = M["Y0"], "random", "device"
+        else:
+            if times is not None:
+                flat = M["status"].reshape(-1).cpu().numpy()
+            else:
+                both = torch.cat([G["n_edges"].to(torch.float64).reshape(1), M["status"].reshape(-1)]).cpu().numpy()   # the fit's last read
+                n_edges, flat = int(both[0]), both[1:]
+            if M["mode"] == "single":
+                st = spectral_status(flat)
+                used, iters, bad = st["init_used"], st["iters"], st["status"] == "not_converged"
+            else:
+                sts = multi_status(flat)
+                used, iters = "components", max(s["iters"] for s in sts)
+                bad = any(s["status"] not in ("converged", "uniform") for s in sts)
+            Y0, solver = M["Y0"], "host (device not converged)" if bad else "device"
+    elif init_solver == "device":
         if times is not None:                              # timed: the graph's step ends before the solve is enqueued
             n_edges = int(G["n_edges"])
         t.append(mark())
@@ -816,7 +1238,12 @@ def umap_fit(X, n_components: int, n_neighbors: int = 15, seed: int = 42, n_epoc
     else:
         n_edges = int(G["n_edges"])
         t.append(mark())
-    if solver != "device":
+    if solver != "device" and multi:
+        Y0, used, hinfo = multi_component_init_host(G["row_ptr"].cpu().numpy(), G["col"][:n_edges].cpu().numpy(),
+                                                    G["weight"][:n_edges].cpu().numpy(), X.cpu().numpy(), n_components, seed)
+        reason = hinfo["reason"]
+        Y0 = torch.from_numpy(Y0).to(dev)
+    elif solver != "device":
         if route == "sparse":
             Y0, used, _ = spectral_init_sparse_host(G["row_ptr"].cpu().numpy(), G["col"][:n_edges].cpu().numpy(),
                                                     G["weight"][:n_edges].cpu().numpy(), n, n_components, seed)
@@ -828,15 +1255,21 @@ def umap_fit(X, n_components: int, n_neighbors: int = 15, seed: int = 42, n_epoc
     t.append(mark())
     if times is not None:
         times.update(zip(("knn", "graph", "init", "layout"), np.diff(t)))
-    return {"embedding": Y, "init_used": used, "a": a, "b": b, "n_edges": n_edges, "init_solver": solver, "init_iters": iters,
-            "route": route}
+    out = {"embedding": Y, "init_used": used, "a": a, "b": b, "n_edges": n_edges, "init_solver": solver, "init_iters": iters,
+           "route": route}
+    if multi:
+        out["init_reason"] = reason
+    return out
 
 
-def compress(X, n_groups: int, num_components: int = 32, n_neighbors: int = 15, seed: int = 42, n_epochs=None, init_solver: str = "host"):
+def compress(X, n_groups: int, num_components: int = 32, n_neighbors: int = 15, seed: int = 42, n_epochs=None, init_solver: str = "host",
+             disconnected: str = "random"):
     """`compress` of the parallel dataset (cluster.py:253-266): one fit per group of d // n_groups consecutive features (a country's
     block), the embeddings side by side.  A GPU tensor stays on the device (init_solver: `umap_fit`'s); a numpy array takes the
-    restatement.  From 4096 rows both take the sparse route by themselves (the reference's default is 10 000 rows)."""
+    restatement.  From 4096 rows both take the sparse route by themselves (the reference's default is 10 000 rows).  disconnected:
+    `umap_fit`'s ('random', the default, or 'components')."""
     import torch
+    _check_disconnected(disconnected)
     on_gpu = isinstance(X, torch.Tensor) and X.is_cuda
     if isinstance(X, torch.Tensor) and not on_gpu:
         X = X.numpy()
@@ -847,8 +1280,9 @@ def compress(X, n_groups: int, num_components: int = 32, n_neighbors: int = 15, 
     parts = []
     for i in range(0, d, group):
         if on_gpu:
-            parts.append(umap_fit(X[:, i:i + group], num_components, n_neighbors, seed, n_epochs, init_solver=init_solver)["embedding"])
+            parts.append(umap_fit(X[:, i:i + group], num_components, n_neighbors, seed, n_epochs, init_solver=init_solver,
+                                  disconnected=disconnected)["embedding"])
         else:
             parts.append(umap_fit_host(X[:, i:i + group], num_components, n_neighbors, seed, n_epochs,
-                                       route=pick_route("auto", X.shape[0]))["embedding"])
+                                       route=pick_route("auto", X.shape[0]), disconnected=disconnected)["embedding"])
     return torch.cat(parts, dim=1) if on_gpu else np.hstack(parts)

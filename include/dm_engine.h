@@ -429,6 +429,52 @@ int dm_umap_sparse_spectral(void* stream, const int32_t* row_ptr, const int32_t*
                             const float* noise, const float* fallback, void* work, size_t work_bytes, float* Y0_out, double* eigvals_out,
                             double* eigvecs_out, double* status_out);
 
+/* ---- UMAP on a disconnected graph: per-component spectral initialisation (csrc/umap_multi.hip) ----------------------
+ * Opt-in (umapfit's disconnected='components'); the rules: `multi_component_init_host` in umapfit.py, a restatement of umap-learn's
+ * multi_component_layout, PARITY UNPINNED.  One set of entries for both routes: n < DM_UMAP_SPARSE_MAX_N, no n x n buffer.  No
+ * floating-point atomics, fixed summation orders: bit-reproducible.
+ *
+ * dm_umap_components: the connected components of the edge list (row_ptr int32 [n + 1], col, weight: `edge_capacity` slots each).
+ *   X                  fp32 [n][d] or NULL (then d is ignored and centroids_out may be NULL)
+ *   comp_out           int32 [n]: the component of every vertex; ids ascend with each component's smallest vertex
+ *   count_out          int32 [1]: c
+ *   offsets_out        int32 [n + 1]: component l owns grouped positions [offsets[l], offsets[l + 1]); entries past c hold n
+ *   perm_out           int32 [n]: the vertex at each grouped position (grouped by component, ascending vertex inside: stable)
+ *   edge_offsets_out   int32 [n + 1]: component l's edges are slots [edge_offsets[l], edge_offsets[l + 1]) of sub_col_out /
+ *                      sub_weight_out (edge_capacity slots each); entries past c hold the total
+ *   sub_row_ptr_out    int32 [2 n + 1]: component l's own CSR row pointer, offsets[l + 1] - offsets[l] + 1 entries from index
+ *                      offsets[l] + l, starting at 0; entries from n + c hold 0
+ *   sub_col_out        a vertex's position inside its component (grouped position - offsets[l]); rows and each row's edges keep
+ *                      their order.  An edge into another component (an asymmetric list) is dropped.
+ *   centroids_out      fp64 [min(n, DM_UMAP_MULTI_MAX_COMP)][d]: the mean of each component's rows, added in ascending row index in
+ *                      fp64; rows past c hold 0
+ * dm_umap_multi_init: Y0 from the sub-graph.  offsets_host / edge_offsets_host (int32 [c + 1]) and plan_host (int32 [c]: 1 = solve,
+ * 0 = uniform) are HOST arrays, read before the call returns; the others are device memory.  Every component with plan 1 (it must
+ * have more than n_components + 1 rows) runs dm_umap_sparse_spectral's launches on its slice; then new kernels take each
+ * component's signs and max|E|, place R = E (range / max|E|) + meta (or meta + range unit for plan 0) through perm, take max|R|,
+ * and finish as dm_umap_spectral does (10 / max|R|, the fp32 cast, + noise, each coordinate rescaled to [0, 10]).
+ *   meta               fp64 [c][n_components]; range fp64 [c]; unit fp64 [n][n_components]; noise fp32 [n][n_components]
+ *   Y0_out             fp32 [n][n_components];  R_out fp64 [n][n_components]
+ *   eigvals_out        fp64 [c][n_components + 1];  eigvecs_out fp64 [n][n_components + 1], rows in grouped order
+ *   status_out         fp64 [c][8]: dm_umap_spectral's record per component; a uniform one reads 2, 1, 0, 0, NaN, 0, 0, 0
+ * Refused without a launch: a NULL pointer, n >= DM_UMAP_SPARSE_MAX_N, n < 1, d < 1 (with X), n_components outside
+ * [1, DM_UMAP_MAX_COMPONENTS], edge_capacity outside [0, 2 n DM_UMAP_MAX_NEIGHBORS], a small workspace, c outside
+ * [1, min(n, DM_UMAP_MULTI_MAX_COMP)] (DM_UMAP_E_COUNT), offsets that do not ascend from 0 to n or edge offsets that do not ascend
+ * within edge_capacity (DM_UMAP_E_EDGES), a plan of 1 for a component of n_components + 1 rows or fewer (DM_UMAP_E_NEIGHBORS_GE_N). */
+#define DM_UMAP_MULTI_MAX_COMP 1024
+#define DM_UMAP_E_COUNT 11
+int dm_umap_components_workspace_bytes(int n, size_t* bytes_out);
+int dm_umap_components(void* stream, const int32_t* row_ptr, const int32_t* col, const float* weight, const float* X, int n, int d,
+                       int edge_capacity, void* work, size_t work_bytes, int32_t* comp_out, int32_t* count_out, int32_t* offsets_out,
+                       int32_t* perm_out, int32_t* edge_offsets_out, int32_t* sub_row_ptr_out, int32_t* sub_col_out,
+                       float* sub_weight_out, double* centroids_out);
+int dm_umap_multi_workspace_bytes(int n, int n_components, size_t* bytes_out);
+int dm_umap_multi_init(void* stream, const int32_t* sub_row_ptr, const int32_t* sub_col, const float* sub_weight, const int32_t* perm,
+                       const int32_t* comp, const int32_t* offsets, const int32_t* plan, const int32_t* offsets_host,
+                       const int32_t* edge_offsets_host, const int32_t* plan_host, int n, int n_comp, int edge_capacity, int n_components,
+                       int seed, const double* meta, const double* range, const double* unit, const float* noise, void* work,
+                       size_t work_bytes, float* Y0_out, double* R_out, double* eigvals_out, double* eigvecs_out, double* status_out);
+
 /* ---- X-ray evaluation: threshold counts of a heat-map against a ground-truth box (csrc/xray_eval.hip) -------------
  * The device half of `aucpr` and `mean_typicallity` (applications/xray/compute.py:263-284).  A stream-plus-workspace function
  * (no engine handle).  Row r of the descriptor table names a map [H][W] fp32 at maps_dev + map_offset (floats, any value; two
