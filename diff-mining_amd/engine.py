@@ -70,6 +70,9 @@ SIGNATURES = {
     "dm_umap_multi_init": (_i32, [_vp] * 11 + [_i32] * 5 + [_vp] * 5 + [_sz] + [_vp] * 5),
     "dm_xray_eval_workspace_bytes": (_sz, [_i32, _i32, _i64]),
     "dm_xray_eval": (_i32, [_vp, _vp, _i32, _vp, _i32] + [_vp] * 6),
+    "dm_overlay_workspace_bytes": (_sz, [_i32, _i64, _i32, _i32]),
+    "dm_gaussian_filter_maps": (_i32, [_vp, _vp, _i32, _f64, _vp, _i32, _i32, _vp, _sz, _vp, _vp, _vp]),
+    "dm_overlay_blend": (_i32, [_vp, _i64, _vp, _i64, _vp, _i32, _vp, _i32, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
     "dm_dense_search_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "dm_dense_search_winners": (_i32, [_vp] * 4 + [_i32] * 6 + [_vp, _sz, _vp, _vp]),
     "dm_dense_search_topk": (_i32, [_vp] * 3 + [_i32] * 5 + [_vp] * 4),
@@ -385,6 +388,20 @@ class _EngineBase:
         from . import xray
         with self._torch.cuda.device(self.device):
             return xray.xray_eval(maps, boxes, thresholds, work)
+
+    def gaussian_filter(self, maps, sigma, post_op: str = "none", work=None, return_max: bool = False):
+        """scipy's `gaussian_filter(a, sigma)` on a list of fp32 maps of mixed sizes, bit for bit, on this engine's device and current
+        stream (dm_gaussian_filter_maps; see `overlay.gaussian_filter`)."""
+        from . import overlay
+        with self._torch.cuda.device(self.device):
+            return overlay.gaussian_filter(maps, sigma, post_op, work, return_max)
+
+    def overlay_rows(self, images, maps, rows, variant: str = "image", sigma=10, want_alpha: bool = False):
+        """The reference's three alpha-blend variants and `filter_patch` for a table of boxes on this engine's device and current
+        stream (dm_gaussian_filter_maps + dm_overlay_blend; see `overlay.overlay_rows`)."""
+        from . import overlay
+        with self._torch.cuda.device(self.device):
+            return overlay.overlay_rows(images, maps, rows, variant, sigma, want_alpha)
 
     def close(self):
         if getattr(self, "_h", None):

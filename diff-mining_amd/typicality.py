@@ -661,6 +661,49 @@ class TypicalityScorer:
         rows["origin"] = np.array(["real"] * len(rows["D"]), dtype=object)
         return rows
 
+    # -- overlays: `load_and_apply_alpha_bbox` (cluster.py:93-110), `apply_alpha` (utils.py:165-214), `filter_patch` (utils.py:104-109)
+    def overlay_patches(self, grids_or_paths, images, image_sizes, rows, variant: str = "image", sigma=10, images_per_call: int = 64,
+                        want_alpha: bool = False):
+        """The mined patches faded to white wherever they are not typical, on the GPU.  grids_or_paths, image_sizes: as
+        `mine_patches` takes them; images: per image a uint8 [H', W', 3] tensor (H' >= H, W' >= W: a map smaller than its image
+        leaves zeros, cluster.py:104-107); rows: the columns `mine_patches` returns (`image`, `x_start`, `y_start`, `x_end`, `y_end`).
+        For every DISTINCT image a row names, the per-pixel map is built once (`typicality_image_batched(..., 1, 1)`, in calls of
+        `images_per_call`) and normalised once (`normalize_map`): "signed" for variant='image' (`load_typicality_norm`), "maxabs"
+        for variant='crop' (`d_compute`, cropped per row).  The filter runs once per image ('image', sigma 10, then `T*(T>0)`) or
+        once per crop ('crop', then `/ max` and the clamp) in ONE `dm_gaussian_filter_maps`, and ONE `dm_overlay_blend` blends every
+        row: see `overlay.overlay_rows`, whose dict this returns (blended and plain uint8 crops, the alpha crops with want_alpha,
+        the `filter_patch` sums and verdicts, the `degenerate` flags), plus `maps`: per input image its normalised map on the GPU
+        (None for an image no row names).  Nothing but the results leaves the device.  numpy images take the restatements of
+        `overlay` on the host, fed with the device's maps, and return numpy arrays."""
+        from . import overlay
+        if variant not in ("image", "crop"):
+            raise ValueError(f"overlay_patches: variant {variant!r} (the stored-T blend needs no grid: overlay.overlay_rows)")
+        n = len(grids_or_paths)
+        if n != len(images) or n != len(image_sizes):
+            raise ValueError(f"{n} grids but {len(images)} images and {len(image_sizes)} image sizes")
+        cols, n_rows = overlay._row_columns(rows, n)
+        if n_rows < 1:
+            raise ValueError("overlay_patches: no rows")
+        used = sorted(set(int(i) for i in cols["image"]))
+        mode = "signed" if variant == "image" else "maxabs"
+        maps = [None] * n
+        for c0 in range(0, len(used), images_per_call):
+            idx = used[c0:c0 + images_per_call]
+            grids = [self(g) if isinstance(g, (str, os.PathLike)) else g for g in (grids_or_paths[i] for i in idx)]
+            grids = [torch.from_numpy(g) if isinstance(g, np.ndarray) else g for g in grids]
+            for i, m in zip(idx, self.engine.typicality_image_batched(grids, [image_sizes[i] for i in idx], 1, 1)):
+                maps[i] = self.engine.normalize_map(m, mode)
+        at = {i: j for j, i in enumerate(used)}
+        sub = {k: cols[k] for k in ("x_start", "y_start", "x_end", "y_end")}
+        sub["image"] = np.array([at[int(i)] for i in cols["image"]], dtype=np.int64)
+        if all(isinstance(images[i], np.ndarray) for i in used):
+            out = overlay.overlay_rows([images[i] for i in used], [maps[i].cpu().numpy() for i in used], sub, variant, sigma, want_alpha)
+        else:
+            imgs = [torch.as_tensor(images[i]).to(self.engine.device) for i in used]
+            out = self.engine.overlay_rows(imgs, [maps[i] for i in used], sub, variant, sigma, want_alpha)
+        out["maps"] = maps
+        return out
+
     @staticmethod
     def permutation_priority(perm) -> np.ndarray:
         """fp32 sort keys that make a descending selection visit the candidates in the order `perm` (perm[r] = flat index of the

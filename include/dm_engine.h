@@ -505,6 +505,66 @@ int dm_xray_eval(const void* maps_dev, const dm_xray_desc* desc_dev, int n_rows,
                  void* work_dev, int32_t* tp_out_dev /*[n_rows][T]*/, int32_t* fp_out_dev /*[n_rows][T]*/,
                  int32_t* n_in_out_dev /*[n_rows]*/, double* box_sum_out_dev /*[n_rows]*/, void* stream);
 
+/* ---- Typicality overlays: Gaussian-filtered alpha blend per patch (csrc/overlay.hip) -------------------------------
+ * The device half of `Cluster.load_and_apply_alpha_bbox` (typicality/cluster.py:93-110), `utils.apply_alpha` (typicality/utils.py:
+ * 165-214), `Cluster.apply_alpha_` (applications/parallel-dataset/cluster.py:132-141) and `filter_patch` (utils.py:104-109).
+ * Stream-plus-workspace functions (no engine handle).  Both read their descriptor table back once, so they synchronise `stream`
+ * before they launch; both return 0, 1 (a bad argument: nothing was launched) or 2 (a HIP error).  No floating-point atomic.
+ *
+ * dm_gaussian_filter_maps: scipy.ndimage.gaussian_filter(a, sigma) (truncate 4, mode 'reflect') of n_maps fp32 maps of mixed sizes.
+ * Map b is [H][W] at maps_dev + map_offset (floats); its result goes to out_dev + out_offset, its fp32 intermediate to the workspace
+ * at work_offset (floats, into the intermediate region; regions of different maps must not overlap).  weights_dev: the 2 radius + 1
+ * fp64 weights exp(-0.5/sigma^2 x^2) / sum, built by the caller with numpy so that the bits are numpy's; radius = (int)(4 sigma +
+ * 0.5).  Axis 0, then axis 1; each pass stages a DM_GAUSS_TILE^2 output tile with its halo in LDS, resolving `reflect` (a mirror of
+ * period 2n, as often as the halo wraps) at load time, starts from the centre tap a[i] w[0], adds the pairs (a[i-j] + a[i+j]) w[j] in
+ * fp64 from j = radius inward to j = 1 (no fused multiply-add) and rounds to fp32 once: bit-equal to scipy.  post_op: DM_GAUSS_POST_
+ * NONE; _CLAMP = T * (T > 0) in fp32 (a negative value becomes -0, NaN stays); _UNIT = T / max(T) in fp32, then the clamp, where
+ * max is numpy's (NaN if any element is NaN) from per-tile partials reduced in a fixed order, written to max_out_dev[b] when that is
+ * not NULL; a maximum of 0 or NaN makes the map all +0 (the `degenerate` rule of dm_overlay_blend).
+ * work_dev: work_bytes >= dm_overlay_workspace_bytes(n_maps, sum_b H_b W_b, max_b H_b, max_b W_b) bytes (0 = bad arguments) whose
+ * contents do not matter.  Bad arguments: a null pointer (max_out_dev may be NULL), n_maps < 1, sigma <= 0 or NaN, a radius that is
+ * not sigma's or exceeds DM_GAUSS_MAX_RADIUS, n_maps > 65535, an unknown post_op, H or W outside [1, 2^24], H W >= 2^31, a negative offset, an
+ * intermediate that leaves the workspace.
+ *
+ * dm_overlay_blend: one workgroup per row of the table.  A row names an image [img_h][img_w][3] uint8 at images_dev + image_offset
+ * (bytes), a map [map_h][map_w] fp32 at maps_dev + map_offset (floats) - ALREADY filtered and clamped - placed with its first element
+ * at image pixel (map_x0, map_y0) (T = 0 outside it: "a map smaller than its image" and "a map that is already the crop" are both
+ * placements; map_h = 0 or map_w = 0 is "no map"), a box (x_start, y_start, x_end, y_end) with x = ROWS, and the dtype flow:
+ *   DM_OVERLAY_IMAGE / DM_OVERLAY_STORED   t = (double)T;  R = 0.05 I + 0.95 (t I + (1.0 - t))          (all float64)
+ *   DM_OVERLAY_CROP                         R = 0.05 I + 0.95 ((double)T I + (double)(1.0f - T))          (`1 - T` is fp32)
+ * with I = (double)u8 / 255.0, no fused multiply-add; the byte is R * 255.0 truncated toward zero to int32 (saturating), modulo 256.
+ * Per row: blended_out_dev + out_offset and plain_out_dev + out_offset (bytes) get the blended and the untouched crop [bh][bw][3];
+ * alpha_out_dev (or NULL) + alpha_offset (floats) gets T [bh][bw]; lum_out_dev[r] = the sum over the plain crop of PIL's 'L' value
+ * (19595 R + 38470 G + 7471 B + 0x8000) >> 16; verdict_out_dev[r] = 30 < sum / count < 225 in float64 (0 for an empty crop);
+ * degenerate_out_dev[r] = 1 when the row is DM_OVERLAY_CROP, map_index >= 0 and map_max_dev[map_index] is 0 or NaN (its T is then
+ * taken as 0).  A zero-area box writes no pixel.  Bad arguments: a null pointer (alpha_out_dev may be NULL, map_max_dev too when no
+ * row has map_index >= 0), n_rows < 1, an unknown variant, an image of no pixels or one that leaves images_dev, a box outside its
+ * image, a map that leaves maps_dev or overhangs its image, map_index outside [-1, n_map_max), a crop that leaves out_bytes /
+ * alpha_elements. */
+#define DM_GAUSS_TILE 32
+#define DM_GAUSS_MAX_RADIUS 200
+#define DM_GAUSS_POST_NONE 0
+#define DM_GAUSS_POST_CLAMP 1
+#define DM_GAUSS_POST_UNIT 2
+#define DM_OVERLAY_IMAGE 0
+#define DM_OVERLAY_CROP 1
+#define DM_OVERLAY_STORED 2
+typedef struct dm_gauss_desc { int64_t map_offset, out_offset, work_offset; int32_t H, W; } dm_gauss_desc;
+typedef struct dm_overlay_row {
+    int64_t image_offset, map_offset, out_offset, alpha_offset;
+    int32_t img_h, img_w, map_h, map_w, map_x0, map_y0;
+    int32_t x_start, y_start, x_end, y_end;
+    int32_t variant, map_index;
+} dm_overlay_row;
+size_t dm_overlay_workspace_bytes(int n_maps, int64_t total_elements, int max_h, int max_w);
+int dm_gaussian_filter_maps(const void* maps_dev, const dm_gauss_desc* desc_dev, int n_maps, double sigma, const double* weights_dev,
+                            int radius, int post_op, void* work_dev, size_t work_bytes, void* out_dev, float* max_out_dev /*[n_maps]*/,
+                            void* stream);
+int dm_overlay_blend(const void* images_dev, int64_t image_bytes, const void* maps_dev, int64_t map_elements, const float* map_max_dev,
+                     int n_map_max, const dm_overlay_row* rows_dev, int n_rows, void* blended_out_dev, void* plain_out_dev,
+                     int64_t out_bytes, float* alpha_out_dev, int64_t alpha_elements, int64_t* lum_out_dev /*[n_rows]*/,
+                     int32_t* verdict_out_dev /*[n_rows]*/, int32_t* degenerate_out_dev /*[n_rows]*/, void* stream);
+
 /* ---- Doersch baseline: dense detector search, winners and top-k (csrc/dense_search.hip) --------------------------
  * The device half of `dense_search_cuda` (doersch/hog.py:124-185): every detector against every cell of every image, of which only
  * the best cell per (detector, image) and then the best images per detector are kept.  Stream-plus-workspace functions (no engine
