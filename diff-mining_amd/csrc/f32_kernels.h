@@ -102,4 +102,24 @@ hipError_t launch_decoder_head(const float* lat, const float* w, const float* b,
 hipError_t launch_decoder_tail(const float* X, const float* stats, const float* gamma, const float* beta, const float* Wp, const float* bias, int B,
                                int H, int W, int C, int raw, float* out_f32, uint8_t* out_u8, hipStream_t s);
 
+// The gradient kernels of the convolutional blocks (f32_train.hip).  wgrad: dWp [Cout][taps*Cin] (gemm32's weight layout) = sum over the M
+// output pixels of dY [M][Cout] (x) im2col(X | X2), modes 0 .. 3 as launch_gemm; the pixels are cut into wgrad_slabs(M) slabs whose partials
+// go to `work` (wgrad_workspace_bytes) and are added in ascending order; accumulate: dWp += the finished gradient (one addition per element)
+int wgrad_slabs(long long M, int* slab_len);
+size_t wgrad_workspace_bytes(long long M, int Cout, int Cin, int mode);
+hipError_t launch_wgrad(const float* X, const float* X2, const float* dY, int M, int H, int W, int OH, int OW, int Cin, int C1, int Cout, int mode,
+                        int accumulate, float* work, size_t work_bytes, float* dWp, hipStream_t s);
+// out [N][C] = the column sums of each sample's HW rows of dY [N*HW][C] (N = 1: dbias), fp64 accumulators in a fixed order
+hipError_t launch_colsum(const float* dY, int N, int HW, int C, int accumulate, float* out, hipStream_t s);
+// GroupNorm (+ SiLU) backward over cat([X, X2]) from the forward pass's stats [N*G][2]: dX [.., C1], dX2 [.., C - C1], dgamma / dbeta [C];
+// work: gn_bwd_workspace_bytes, 8-byte aligned
+size_t gn_bwd_workspace_bytes(int N, int C, int G);
+hipError_t launch_gn_bwd(const float* X, const float* X2, const float* dY, int N, int HW, int C, int C1, int G, const float* gamma, const float* beta,
+                         const float* stats, int silu, void* work, size_t work_bytes, float* dX, float* dX2, float* dgamma, float* dbeta, hipStream_t s);
+hipError_t launch_silu_bwd(const float* x, const float* dy, float* dx, long long n, hipStream_t s);           // dx = dy * silu'(x)
+// Z [N,H,W,C]: Z[2 oy][2 ox] = dY[oy][ox] of dY [N,(H+1)/2,(W+1)/2,C], zero elsewhere (the stride-2 data gradient as a mode-1 convolution)
+hipError_t launch_zero_insert2(const float* dY, int N, int H, int W, int C, float* Z, hipStream_t s);
+// dS [N,H,W,C]: every source pixel sums its pre-image of dU [N,OH,OW,C] under mode 3's nearest rule, ascending destination order
+hipError_t launch_nearest_bwd(const float* dU, int N, int H, int W, int OH, int OW, int C, float* dS, hipStream_t s);
+
 }  // namespace dm32

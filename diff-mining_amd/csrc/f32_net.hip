@@ -199,4 +199,50 @@ int dm_f32_op_posterior(void* stream, const void* Hm, const void* qw, const void
                             (float*)moments, (hipStream_t)stream) == hipSuccess ? 0 : 1;
 }
 
+/* the gradient operators of the convolutional blocks (f32_train.hip; tests/test_gpu_train_ops.py): a null required pointer, a channel count
+ * the kernel cannot take, a workspace that is too small or a mode outside 0 .. 3 returns 1 before anything is launched */
+static long long wgrad_rows(int N, int H, int W, int OH, int OW, int mode) {
+    if (N <= 0 || H <= 0 || W <= 0 || (mode != 0 && (OH <= 0 || OW <= 0))) return 0;
+    return mode == 0 ? (long long)N * H * W : (long long)N * OH * OW;
+}
+
+size_t dm_f32_op_gemm_wgrad_workspace(int N, int H, int W, int OH, int OW, int Cin, int Cout, int mode) {
+    if (mode < 0 || mode > 3) return 0;
+    return wgrad_workspace_bytes(wgrad_rows(N, H, W, OH, OW, mode), Cout, Cin, mode);
+}
+
+int dm_f32_op_gemm_wgrad(void* stream, const void* X, const void* X2, const void* dY, void* dWp, void* work, size_t work_bytes, int N, int H, int W,
+                         int OH, int OW, int Cin, int C1, int Cout, int mode, int accumulate) {
+    if (mode < 0 || mode > 3) return 1;
+    const long long M = wgrad_rows(N, H, W, OH, OW, mode);
+    if (M <= 0 || M > 0x7fffffffLL - 4096) return 1;
+    if (mode == 2 && (OH != (H + 1) / 2 || OW != (W + 1) / 2)) return 1;
+    if (mode == 1 && (OH != H || OW != W)) return 1;
+    return launch_wgrad((const float*)X, (const float*)X2, (const float*)dY, (int)M, mode == 0 ? 1 : H, mode == 0 ? (int)M : W, mode == 0 ? 1 : OH,
+                        mode == 0 ? (int)M : OW, Cin, C1, Cout, mode, accumulate != 0, (float*)work, work_bytes, (float*)dWp, (hipStream_t)stream) == hipSuccess ? 0 : 1;
+}
+
+int dm_f32_op_colsum(void* stream, const void* dY, int N, int HW, int C, int accumulate, void* out) {
+    return launch_colsum((const float*)dY, N, HW, C, accumulate != 0, (float*)out, (hipStream_t)stream) == hipSuccess ? 0 : 1;
+}
+
+int dm_f32_op_groupnorm_bwd(void* stream, const void* X, const void* X2, const void* dY, int N, int HW, int C, int C1, int G, const float* gamma,
+                            const float* beta, const void* stats, int silu, void* work, size_t work_bytes, void* dX, void* dX2, void* dgamma,
+                            void* dbeta) {
+    return launch_gn_bwd((const float*)X, (const float*)X2, (const float*)dY, N, HW, C, C1, G, gamma, beta, (const float*)stats, silu != 0, work, work_bytes,
+                         (float*)dX, (float*)dX2, (float*)dgamma, (float*)dbeta, (hipStream_t)stream) == hipSuccess ? 0 : 1;
+}
+
+int dm_f32_op_silu_bwd(void* stream, const void* x, const void* dy, void* dx, int64_t n) {
+    return launch_silu_bwd((const float*)x, (const float*)dy, (float*)dx, (long long)n, (hipStream_t)stream) == hipSuccess ? 0 : 1;
+}
+
+int dm_f32_op_zero_insert2(void* stream, const void* dY, int N, int H, int W, int C, void* Z) {
+    return launch_zero_insert2((const float*)dY, N, H, W, C, (float*)Z, (hipStream_t)stream) == hipSuccess ? 0 : 1;
+}
+
+int dm_f32_op_nearest_bwd(void* stream, const void* dU, int N, int H, int W, int OH, int OW, int C, void* dS) {
+    return launch_nearest_bwd((const float*)dU, N, H, W, OH, OW, C, (float*)dS, (hipStream_t)stream) == hipSuccess ? 0 : 1;
+}
+
 }  // extern "C"

@@ -202,6 +202,13 @@ SIGNATURES = {
     "dm_f32_op_nhwc_to_nchw": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp]),
     "dm_f32_op_ensemble_mean": (_i32, [_vp, _vp] + [_i32] * 4 + [_vp]),
     "dm_f32_op_posterior": (_i32, [_vp] * 5 + [_i32] * 3 + [_f32, _vp, _vp]),
+    "dm_f32_op_gemm_wgrad_workspace": (_sz, [_i32] * 8),
+    "dm_f32_op_gemm_wgrad": (_i32, [_vp] * 6 + [_sz] + [_i32] * 10),
+    "dm_f32_op_colsum": (_i32, [_vp, _vp] + [_i32] * 4 + [_vp]),
+    "dm_f32_op_groupnorm_bwd": (_i32, [_vp] * 4 + [_i32] * 5 + [_vp, _vp, _vp, _i32, _vp, _sz] + [_vp] * 4),
+    "dm_f32_op_silu_bwd": (_i32, [_vp] * 4 + [_i64]),
+    "dm_f32_op_zero_insert2": (_i32, [_vp, _vp] + [_i32] * 4 + [_vp]),
+    "dm_f32_op_nearest_bwd": (_i32, [_vp, _vp] + [_i32] * 6 + [_vp]),
 }
 SYMBOLS = list(SIGNATURES)
 

@@ -1280,6 +1280,35 @@ int dm_f32_op_nhwc_to_nchw(void* stream, const void* X, int N, int HW, int C, vo
 int dm_f32_op_ensemble_mean(void* stream, const void* X, int groups, int ens, int HW, int C, void* Y);
 int dm_f32_op_posterior(void* stream, const void* Hm, const void* qw, const void* qb, const void* noise, int B, int draws, int HW, float scaling,
                         void* latent, void* moments);
+/* Gradient operators of the fp32 net's convolutional blocks (ResnetBlock2D, Downsample2D, Upsample2D), all tensors fp32 NHWC, no
+ * floating-point atomics: the same call gives the same bits.  The DATA gradient of a convolution is dm_f32_op_gemm itself on repacked
+ * weights (train.py dgrad_weights); these are the rest.  Every entry returns 1 without launching on: a null required pointer, a
+ * non-positive extent, a mode outside 0 .. 3, a channel count its kernel cannot take (named per entry), a workspace that is too small.
+ *   gemm_wgrad   dWp [Cout][taps*Cin], k = (tap, cin) (the layout dm_f32_op_gemm reads) = sum over output pixels of dY [N,OH,OW,Cout] (x)
+ *                im2col(X [N,H,W,C1] | X2 [N,H,W,Cin-C1]); modes 0 .. 3 and the (N, H, W, OH, OW) convention of dm_f32_op_gemm (mode 0:
+ *                N*H*W rows, OH / OW ignored; mode 1 needs OH = H, OW = W; mode 2 OH = (H+1)/2, OW = (W+1)/2).  Cin % 32, C1 % 32, Cout % 4,
+ *                X2 required when C1 < Cin.  The pixels are cut into slabs (a function of the pixel count alone); work receives one partial
+ *                dWp per slab, work_bytes >= dm_f32_op_gemm_wgrad_workspace(...) (0 for arguments the kernel refuses); the partials are
+ *                added in ascending slab order.  accumulate = 1: dWp += the finished gradient, one fp32 addition per element.
+ *   colsum       out [N][C] = the sum of each sample's HW rows of dY [N*HW][C] (N = 1, HW = rows: dbias; per sample: the gradient into
+ *                time_emb_proj), fp64 accumulators in a fixed order; C % 4; accumulate as above
+ *   groupnorm_bwd  GroupNorm (+ SiLU when silu) backward over cat([X (C1), X2 (C - C1)]); stats [N*G][2] = the (mean, rstd) of
+ *                dm_f32_op_groupnorm's stats_work; dY [N*HW][C]; writes dX [N*HW][C1], dX2 [N*HW][C-C1] (required when C1 < C),
+ *                dgamma [C], dbeta [C]; work: 16 (N C + N G) bytes, 8-byte aligned; C % G == 0, C / G <= 256
+ *   silu_bwd     dx = dy * silu'(x) on n elements
+ *   zero_insert2 Z [N,H,W,C]: Z[2 oy][2 ox] = dY[oy][ox] of dY [N,(H+1)/2,(W+1)/2,C], zero elsewhere; C % 4
+ *   nearest_bwd  dS [N,H,W,C]: every source pixel sums the pixels of dU [N,OH,OW,C] that mode 3's nearest rule maps to it
+ *                (src = min(floor(dst * (float)H / (float)OH), H - 1)), in ascending destination order; C % 4 */
+size_t dm_f32_op_gemm_wgrad_workspace(int N, int H, int W, int OH, int OW, int Cin, int Cout, int mode);
+int dm_f32_op_gemm_wgrad(void* stream, const void* X, const void* X2, const void* dY, void* dWp, void* work, size_t work_bytes,
+                         int N, int H, int W, int OH, int OW, int Cin, int C1, int Cout, int mode, int accumulate);
+int dm_f32_op_colsum(void* stream, const void* dY, int N, int HW, int C, int accumulate, void* out);
+int dm_f32_op_groupnorm_bwd(void* stream, const void* X, const void* X2, const void* dY, int N, int HW, int C, int C1, int G,
+                            const float* gamma, const float* beta, const void* stats, int silu, void* work, size_t work_bytes,
+                            void* dX, void* dX2, void* dgamma, void* dbeta);
+int dm_f32_op_silu_bwd(void* stream, const void* x, const void* dy, void* dx, int64_t n);
+int dm_f32_op_zero_insert2(void* stream, const void* dY, int N, int H, int W, int C, void* Z);
+int dm_f32_op_nearest_bwd(void* stream, const void* dU, int N, int H, int W, int OH, int OW, int C, void* dS);
 
 #ifdef __cplusplus
 }
