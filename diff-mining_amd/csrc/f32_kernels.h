@@ -122,4 +122,32 @@ hipError_t launch_zero_insert2(const float* dY, int N, int H, int W, int C, floa
 // dS [N,H,W,C]: every source pixel sums its pre-image of dU [N,OH,OW,C] under mode 3's nearest rule, ascending destination order
 hipError_t launch_nearest_bwd(const float* dU, int N, int H, int W, int OH, int OW, int C, float* dS, hipStream_t s);
 
+// The gradient kernels of the transformer blocks.  Attention backward (f32_train_attn.hip): Q, K, V, O, dO and dQ, dK, dV with row strides ld*
+// and batch strides bs* as AttnParams (stacked q|k|v and k|v rows work in place), D in {40, 80, 160}.  `work` (16-byte aligned,
+// attn_bwd_workspace_bytes) starts with the statistics [B][heads][Tq][2] = (L, Delta): L = log2 sum_k 2^(s scale log2e), Delta = dO . O;
+// behind them (rounded up to 16 bytes) the dK | dV partials [slabs][B][heads][Tk][2 D] of attn_bwd_slabs(Tq, Tk) query slabs, which a reduce
+// kernel adds in ascending slab order.  No floating-point atomics.
+struct AttnBwdParams {
+    const float* Q; const float* K; const float* V; const float* O; const float* dO;
+    float* dQ; float* dK; float* dV;
+    int ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv;
+    long long bsq, bsk, bsv, bso, bsdo, bsdq, bsdk, bsdv;
+    int B, heads, Tq, Tk, D;
+    float scale;
+    void* work; size_t work_bytes;
+    int phases = 15;      // bit 0 statistics, 1 dQ, 2 dK / dV partials, 3 their sum: the rate tool times them one by one (after one full run)
+};
+int attn_bwd_slabs(int Tq, int Tk, int* slab_len);
+size_t attn_bwd_workspace_bytes(int B, int heads, int Tq, int Tk, int D);
+hipError_t launch_attention_bwd(const AttnBwdParams& p, hipStream_t s);
+// LayerNorm backward (f32_train.hip): mean / rstd recomputed per row as ln32_kernel does; dgamma / dbeta over ln_bwd_slabs(rows) row slabs in
+// fp64, added in ascending order.  work: ln_bwd_workspace_bytes, 8-byte aligned (doubles [slabs][2][C], then floats [rows][2] = (mean, rstd))
+int ln_bwd_slabs(int rows, int* slab_len);
+size_t ln_bwd_workspace_bytes(int rows, int C);
+hipError_t launch_layernorm_bwd(const float* X, const float* dY, int rows, int C, const float* gamma, float eps, void* work, size_t work_bytes,
+                                float* dX, float* dgamma, float* dbeta, hipStream_t s);
+// GEGLU on P [M][2F] = (h | g): Y [M][F] = h gelu(g) with the GEMM epilogue's expression; dP = (dY gelu(g) | dY h gelu'(g)); F % 4 == 0
+hipError_t launch_geglu(const float* P, int M, int F, float* Y, hipStream_t s);
+hipError_t launch_geglu_bwd(const float* P, const float* dY, int M, int F, float* dP, hipStream_t s);
+
 }  // namespace dm32

@@ -245,4 +245,44 @@ int dm_f32_op_nearest_bwd(void* stream, const void* dU, int N, int H, int W, int
     return launch_nearest_bwd((const float*)dU, N, H, W, OH, OW, C, (float*)dS, (hipStream_t)stream) == hipSuccess ? 0 : 1;
 }
 
+/* the gradient operators of the transformer blocks (f32_train_attn.hip, f32_train.hip; tests/test_gpu_train_tfm_ops.py) */
+size_t dm_f32_op_attention_bwd_workspace(int B, int heads, int Tq, int Tk, int D) { return attn_bwd_workspace_bytes(B, heads, Tq, Tk, D); }
+
+int dm_f32_op_attention_bwd_slabs(int Tq, int Tk) { return Tq > 0 && Tk > 0 ? attn_bwd_slabs(Tq, Tk, nullptr) : 0; }
+
+int dm_f32_op_attention_bwd_phases(void* stream, const void* Q, const void* K, const void* V, const void* O, const void* dO, void* dQ, void* dK, void* dV,
+                                   const int32_t* ld8, const int64_t* bs8, const int32_t* kv_slot, int B, int heads, int Tq, int Tk, int D, float scale,
+                                   void* work, size_t work_bytes, int phases) {
+    if (!ld8 || !bs8 || kv_slot) return 1;
+    AttnBwdParams a;
+    a.Q = (const float*)Q; a.K = (const float*)K; a.V = (const float*)V; a.O = (const float*)O; a.dO = (const float*)dO;
+    a.dQ = (float*)dQ; a.dK = (float*)dK; a.dV = (float*)dV;
+    a.ldq = ld8[0]; a.ldk = ld8[1]; a.ldv = ld8[2]; a.ldo = ld8[3]; a.lddo = ld8[4]; a.lddq = ld8[5]; a.lddk = ld8[6]; a.lddv = ld8[7];
+    a.bsq = bs8[0]; a.bsk = bs8[1]; a.bsv = bs8[2]; a.bso = bs8[3]; a.bsdo = bs8[4]; a.bsdq = bs8[5]; a.bsdk = bs8[6]; a.bsdv = bs8[7];
+    a.B = B; a.heads = heads; a.Tq = Tq; a.Tk = Tk; a.D = D; a.scale = scale; a.work = work; a.work_bytes = work_bytes; a.phases = phases;
+    return launch_attention_bwd(a, (hipStream_t)stream) == hipSuccess ? 0 : 1;
+}
+
+int dm_f32_op_attention_bwd(void* stream, const void* Q, const void* K, const void* V, const void* O, const void* dO, void* dQ, void* dK, void* dV,
+                            const int32_t* ld8, const int64_t* bs8, const int32_t* kv_slot, int B, int heads, int Tq, int Tk, int D, float scale,
+                            void* work, size_t work_bytes) {
+    return dm_f32_op_attention_bwd_phases(stream, Q, K, V, O, dO, dQ, dK, dV, ld8, bs8, kv_slot, B, heads, Tq, Tk, D, scale, work, work_bytes, 15);
+}
+
+size_t dm_f32_op_layernorm_bwd_workspace(int rows, int C) { return ln_bwd_workspace_bytes(rows, C); }
+
+int dm_f32_op_layernorm_bwd(void* stream, const void* X, const void* dY, int rows, int C, const float* gamma, float eps, void* work, size_t work_bytes,
+                            void* dX, void* dgamma, void* dbeta) {
+    return launch_layernorm_bwd((const float*)X, (const float*)dY, rows, C, gamma, eps, work, work_bytes, (float*)dX, (float*)dgamma, (float*)dbeta,
+                                (hipStream_t)stream) == hipSuccess ? 0 : 1;
+}
+
+int dm_f32_op_geglu(void* stream, const void* P, int M, int F, void* Y) {
+    return launch_geglu((const float*)P, M, F, (float*)Y, (hipStream_t)stream) == hipSuccess ? 0 : 1;
+}
+
+int dm_f32_op_geglu_bwd(void* stream, const void* P, const void* dY, int M, int F, void* dP) {
+    return launch_geglu_bwd((const float*)P, (const float*)dY, M, F, (float*)dP, (hipStream_t)stream) == hipSuccess ? 0 : 1;
+}
+
 }  // extern "C"

@@ -6,6 +6,9 @@
 //   colsum32       dbias / the per-sample sums that flow into time_emb_proj
 //   gn32_bwd_*     GroupNorm (+ SiLU) backward over one or two concatenated sources, from the forward pass's (mean, rstd)
 //   silu_bwd, zero_insert2 (stride-2 data gradient -> a mode-1 convolution), nearest_bwd (up-sampler's data gradient)
+// and, for the transformer blocks (whose attention backward is f32_train_attn.hip),
+//   ln32_bwd_*     LayerNorm backward, mean / rstd recomputed per row; dgamma / dbeta over row slabs in fp64
+//   geglu32, geglu32_bwd   the unfused GEGLU of the training forward pass and its gradient
 // Every sum has a fixed order: no floating-point atomics, the same bits from run to run.
 //
 // wgrad32.  The reduction runs over PIXELS; both operands lie pixel-major in NHWC (dY [pixel][Cout], X [pixel][Cin]), so one LDS
@@ -284,6 +287,109 @@ __global__ void nearest_bwd_kernel(const float* dU, int N, int H, int W, int OH,
     }
 }
 
+// ---- LayerNorm backward ------------------------------------------------------------------------------------------------------------
+// one wave per row: mean and rstd by ln32_kernel's own expressions (f32_ops.hip: two passes, fp32, the same lane order and shuffles), kept
+// in rowstats [rows][2] for the parameter sums; dx = rstd (dy gamma - mean(dy gamma) - xhat mean(dy gamma xhat)), the two means from fp64
+// lane sums.  A row of zero variance has rstd = eps^-1/2 and xhat = 0.
+__global__ __launch_bounds__(256) void ln32_bwd_dx_kernel(const float* X, const float* dY, int rows, int C, const float* gamma, float eps, float* rowstats,
+                                                          float* dX) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= rows) return;
+    const float* x = X + (long long)row * C;
+    const float* dy = dY + (long long)row * C;
+    float s = 0.f;
+    for (int i = lane; i < C; i += 64) s += x[i];
+    for (int w = 32; w > 0; w >>= 1) s += __shfl_xor(s, w);
+    const float mean = s / (float)C;
+    float q = 0.f;
+    for (int i = lane; i < C; i += 64) { const float d = x[i] - mean; q += d * d; }
+    for (int w = 32; w > 0; w >>= 1) q += __shfl_xor(q, w);
+    const float rstd = 1.0f / sqrtf(q / (float)C + eps);
+    double a = 0.0, b = 0.0;
+    for (int i = lane; i < C; i += 64) {
+        const float dg = dy[i] * gamma[i], xh = (x[i] - mean) * rstd;
+        a += (double)dg; b += (double)dg * (double)xh;
+    }
+    for (int w = 32; w > 0; w >>= 1) { a += __shfl_xor(a, w); b += __shfl_xor(b, w); }
+    const float m1 = (float)(a / (double)C), m2 = (float)(b / (double)C);
+    float* dx = dX + (long long)row * C;
+    for (int i = lane; i < C; i += 64) {
+        const float xh = (x[i] - mean) * rstd;
+        dx[i] = rstd * (dy[i] * gamma[i] - m1 - xh * m2);
+    }
+    if (lane == 0) { rowstats[2 * (long long)row] = mean; rowstats[2 * (long long)row + 1] = rstd; }
+}
+
+// block = (64-channel chunk, row slab): thread (r = tid / 64, j = tid % 64) adds rows r, r + 4, ... of the slab for channel j in fp64; the four
+// row lanes are added 0 .. 3 -> part[slab][0][c] = sum dy xhat, part[slab][1][c] = sum dy
+__global__ __launch_bounds__(256) void ln32_bwd_params_kernel(const float* X, const float* dY, int rows, int C, int slab_len, const float* rowstats,
+                                                              double* part) {
+    __shared__ double sa[256], sb[256];
+    const int j = threadIdx.x & 63, r = threadIdx.x >> 6, ch = blockIdx.x * 64 + j;
+    const int r0 = blockIdx.y * slab_len, r1 = rows < r0 + slab_len ? rows : r0 + slab_len;
+    double a = 0.0, b = 0.0;
+    if (ch < C)
+        for (int row = r0 + r; row < r1; row += 4) {
+            const float mean = rowstats[2 * (long long)row], rstd = rowstats[2 * (long long)row + 1];
+            const float xh = (X[(long long)row * C + ch] - mean) * rstd, d = dY[(long long)row * C + ch];
+            a += (double)d * (double)xh; b += (double)d;
+        }
+    sa[threadIdx.x] = a; sb[threadIdx.x] = b;
+    __syncthreads();
+    if (r == 0 && ch < C) {
+        double ta = 0.0, tb = 0.0;
+        for (int k = 0; k < 4; ++k) { ta += sa[64 * k + j]; tb += sb[64 * k + j]; }
+        part[((long long)blockIdx.y * 2) * C + ch] = ta;
+        part[((long long)blockIdx.y * 2 + 1) * C + ch] = tb;
+    }
+}
+
+__global__ void ln32_bwd_reduce_kernel(const double* part, int slabs, int C, float* dgamma, float* dbeta) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    double a = 0.0, b = 0.0;
+    for (int k = 0; k < slabs; ++k) { a += part[((long long)k * 2) * C + c]; b += part[((long long)k * 2 + 1) * C + c]; }
+    dgamma[c] = (float)a; dbeta[c] = (float)b;
+}
+
+// ---- GEGLU on P [M][2F] = (h | g), 16-byte accesses ----------------------------------------------------------------------------------
+// gelu(g) in the GEMM epilogue's expression (f32_gemm.hip, epi = 1); gelu'(g) = Phi(g) + g phi(g), Phi = 0.5 (1 + erf(g / sqrt 2)),
+// phi = exp(-g^2 / 2) / sqrt(2 pi)
+__device__ inline float gelu_fwd(float g) { return 0.5f * g * (1.0f + erff(g * 0.70710678118654752440f)); }
+__device__ inline float gelu_grad(float g) {
+    return 0.5f * (1.0f + erff(g * 0.70710678118654752440f)) + g * (0.39894228040143267794f * expf(-0.5f * g * g));
+}
+
+__global__ void geglu32_kernel(const float* P, long long M, int F, float* Y) {
+    const int f4 = F / 4;
+    const long long total = M * f4;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const long long row = i / f4;
+        const int c = 4 * (int)(i - row * f4);
+        const v4f h = *reinterpret_cast<const v4f*>(P + row * 2 * F + c), g = *reinterpret_cast<const v4f*>(P + row * 2 * F + F + c);
+        v4f y;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) y[j] = h[j] * gelu_fwd(g[j]);
+        *reinterpret_cast<v4f*>(Y + row * F + c) = y;
+    }
+}
+
+__global__ void geglu32_bwd_kernel(const float* P, const float* dY, long long M, int F, float* dP) {
+    const int f4 = F / 4;
+    const long long total = M * f4;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const long long row = i / f4;
+        const int c = 4 * (int)(i - row * f4);
+        const v4f h = *reinterpret_cast<const v4f*>(P + row * 2 * F + c), g = *reinterpret_cast<const v4f*>(P + row * 2 * F + F + c);
+        const v4f dy = *reinterpret_cast<const v4f*>(dY + row * F + c);
+        v4f dh, dg;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { dh[j] = dy[j] * gelu_fwd(g[j]); dg[j] = dy[j] * h[j] * gelu_grad(g[j]); }
+        *reinterpret_cast<v4f*>(dP + row * 2 * F + c) = dh;
+        *reinterpret_cast<v4f*>(dP + row * 2 * F + F + c) = dg;
+    }
+}
+
 inline unsigned grid_for(long long n, int block = 256) {
     long long g = (n + block - 1) / block;
     return (unsigned)(g < 1 ? 1 : (g > 65536 * 16 ? 65536 * 16 : g));
@@ -373,6 +479,51 @@ hipError_t launch_zero_insert2(const float* dY, int N, int H, int W, int C, floa
 hipError_t launch_nearest_bwd(const float* dU, int N, int H, int W, int OH, int OW, int C, float* dS, hipStream_t s) {
     if (!dU || !dS || N <= 0 || H <= 0 || W <= 0 || OH <= 0 || OW <= 0 || C <= 0 || C % 4 != 0) return hipErrorInvalidValue;
     hipLaunchKernelGGL(nearest_bwd_kernel, dim3(grid_for((long long)N * H * W * (C / 4))), dim3(256), 0, s, dU, N, H, W, OH, OW, C, dS);
+    return hipGetLastError();
+}
+
+// The row slabs of LayerNorm's parameter sums: a function of the row count alone, one slab per 256 rows, at most 64
+int ln_bwd_slabs(int rows, int* slab_len) {
+    int s = (rows + 255) / 256;
+    s = s < 1 ? 1 : (s > 64 ? 64 : s);
+    if (slab_len) *slab_len = (rows + s - 1) / s;
+    return s;
+}
+
+size_t ln_bwd_workspace_bytes(int rows, int C) {
+    if (rows <= 0 || C <= 0) return 0;
+    return (size_t)ln_bwd_slabs(rows, nullptr) * 2 * C * sizeof(double) + (size_t)rows * 2 * sizeof(float);
+}
+
+hipError_t launch_layernorm_bwd(const float* X, const float* dY, int rows, int C, const float* gamma, float eps, void* work, size_t work_bytes,
+                                float* dX, float* dgamma, float* dbeta, hipStream_t s) {
+    const size_t need = ln_bwd_workspace_bytes(rows, C);
+    if (!X || !dY || !gamma || !work || !dX || !dgamma || !dbeta || need == 0 || work_bytes < need || ((uintptr_t)work & 7) != 0 || !(eps >= 0.f))
+        return hipErrorInvalidValue;
+    int slab_len = 0;
+    const int slabs = ln_bwd_slabs(rows, &slab_len);
+    double* part = (double*)work;
+    float* rowstats = (float*)(part + (size_t)slabs * 2 * C);
+    hipLaunchKernelGGL(ln32_bwd_dx_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, X, dY, rows, C, gamma, eps, rowstats, dX);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(ln32_bwd_params_kernel, dim3((unsigned)((C + 63) / 64), (unsigned)slabs), dim3(256), 0, s, X, dY, rows, C, slab_len,
+                       (const float*)rowstats, part);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(ln32_bwd_reduce_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, s, (const double*)part, slabs, C, dgamma, dbeta);
+    return hipGetLastError();
+}
+
+hipError_t launch_geglu(const float* P, int M, int F, float* Y, hipStream_t s) {
+    if (!P || !Y || M <= 0 || F <= 0 || F % 4 != 0 || (((uintptr_t)P | (uintptr_t)Y) & 15) != 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(geglu32_kernel, dim3(grid_for((long long)M * (F / 4))), dim3(256), 0, s, P, (long long)M, F, Y);
+    return hipGetLastError();
+}
+
+hipError_t launch_geglu_bwd(const float* P, const float* dY, int M, int F, float* dP, hipStream_t s) {
+    if (!P || !dY || !dP || M <= 0 || F <= 0 || F % 4 != 0 || (((uintptr_t)P | (uintptr_t)dY | (uintptr_t)dP) & 15) != 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(geglu32_bwd_kernel, dim3(grid_for((long long)M * (F / 4))), dim3(256), 0, s, P, dY, (long long)M, F, dP);
     return hipGetLastError();
 }
 

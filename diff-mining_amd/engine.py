@@ -209,6 +209,14 @@ SIGNATURES = {
     "dm_f32_op_silu_bwd": (_i32, [_vp] * 4 + [_i64]),
     "dm_f32_op_zero_insert2": (_i32, [_vp, _vp] + [_i32] * 4 + [_vp]),
     "dm_f32_op_nearest_bwd": (_i32, [_vp, _vp] + [_i32] * 6 + [_vp]),
+    "dm_f32_op_attention_bwd_workspace": (_sz, [_i32] * 5),
+    "dm_f32_op_attention_bwd_slabs": (_i32, [_i32, _i32]),
+    "dm_f32_op_attention_bwd": (_i32, [_vp] * 12 + [_i32] * 5 + [_f32, _vp, _sz]),
+    "dm_f32_op_attention_bwd_phases": (_i32, [_vp] * 12 + [_i32] * 5 + [_f32, _vp, _sz, _i32]),
+    "dm_f32_op_layernorm_bwd_workspace": (_sz, [_i32, _i32]),
+    "dm_f32_op_layernorm_bwd": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _f32, _vp, _sz, _vp, _vp, _vp]),
+    "dm_f32_op_geglu": (_i32, [_vp, _vp, _i32, _i32, _vp]),
+    "dm_f32_op_geglu_bwd": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp]),
 }
 SYMBOLS = list(SIGNATURES)
 

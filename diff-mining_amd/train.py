@@ -1,4 +1,5 @@
-"""Differentiable convolutional blocks of the fp32 net: ResnetBlock2D, Downsample2D, Upsample2D with gradients.
+"""Differentiable blocks of the fp32 net: ResnetBlock2D, Downsample2D, Upsample2D (part 1) and, further down, the transformer blocks
+(part 2: LayerNorm, self- and cross-attention, GEGLU, proj_in / proj_out; BasicTransformerBlock32, Transformer2D32), with gradients.
 
 PyTorch does the plumbing — autograd orders the calls, allocates the tensors and adds into `.grad` —, every FLOP runs in the library:
 the forward pass is the inference operators (dm_f32_op_gemm, dm_f32_op_groupnorm, dm_f32_op_silu: the same bits), the backward pass
@@ -459,3 +460,365 @@ class Upsample32(_Block32):
 
     def forward(self, x, out_hw: Optional[Tuple[int, int]] = None):
         return conv32(x, None, self.conv_weight, self.conv_bias, None, None, 3, out_hw)
+
+
+# =======================================================================================================================================
+# part 2: the transformer blocks — LayerNorm, self- and cross-attention, GEGLU, proj_in / proj_out
+# =======================================================================================================================================
+# The linear layers are linear32 (conv32 in mode 0): forward dm_f32_op_gemm, weight gradient dm_f32_op_gemm_wgrad, data gradient
+# dm_f32_op_gemm on W^T, bias dm_f32_op_colsum.  Three gradients have kernels of their own:
+#   attention  dm_f32_op_attention_bwd: dQ, dK, dV on the stacked q|k|v rows [tokens][3C] (self) or q [tokens][C] and k|v [B Tk][2C] (cross)
+#              in place, so one weight-gradient call serves a stacked projection
+#   LayerNorm  dm_f32_op_layernorm_bwd (mean / rstd recomputed: the forward pass saves nothing)
+#   GEGLU      the training forward pass of ff.net.0 is the plain GEMM on the [2F][C] weight (P = h | g, kept for the backward pass), then
+#              dm_f32_op_geglu; dm_f32_op_geglu_bwd gives dP
+LOG2E = 1.4426950408889634
+
+
+def attention_host(q, k, v, heads: int):
+    """softmax(q k^T / sqrt(D)) v per head with plain torch ops: q [B,Tq,C], k, v [B,Tk,C] -> [B,Tq,C]"""
+    B, Tq, Cc = q.shape
+    D = Cc // heads
+    qh, kh, vh = (t.reshape(B, t.shape[1], heads, D).transpose(1, 2) for t in (q, k, v))
+    p = torch.softmax(qh @ kh.transpose(-1, -2) * D ** -0.5, dim=-1)
+    return (p @ vh).transpose(1, 2).reshape(B, Tq, Cc)
+
+
+def attention_bwd_host(q, k, v, do, heads: int):
+    """The device kernels' rule without autograd, on any device and float dtype: (dq, dk, dv, L, delta) with
+    L [B,heads,Tq] = log2 sum_k 2^(s scale log2 e), delta = sum_d dO O, P = 2^(s' - L), dS = P (dP - delta), dQ = dS K scale,
+    dK = dS^T Q scale, dV = P^T dO"""
+    B, Tq, Cc = q.shape
+    D = Cc // heads
+    scale = D ** -0.5
+    qh, kh, vh, doh = (t.reshape(B, t.shape[1], heads, D).transpose(1, 2) for t in (q, k, v, do))
+    s2 = qh @ kh.transpose(-1, -2) * (scale * LOG2E)
+    L = torch.logsumexp(s2 / LOG2E, dim=-1) * LOG2E
+    p = torch.exp2(s2 - L[..., None])
+    o = p @ vh
+    delta = (doh * o).sum(-1)
+    ds = p * (doh @ vh.transpose(-1, -2) - delta[..., None])
+    dq, dk, dv = ds @ kh * scale, ds.transpose(-1, -2) @ qh * scale, p.transpose(-1, -2) @ doh
+    back = lambda t: t.transpose(1, 2).reshape(B, t.shape[2], Cc)          # noqa: E731
+    return back(dq), back(dk), back(dv), L, delta
+
+
+def layernorm_bwd_host(x, dy, gamma, eps: float):
+    """LayerNorm backward over the last axis: dx = rstd (dy gamma - mean(dy gamma) - xhat mean(dy gamma xhat)), dgamma = sum dy xhat,
+    dbeta = sum dy over all rows"""
+    mean = x.mean(-1, keepdim=True)
+    rstd = (((x - mean) ** 2).mean(-1, keepdim=True) + eps).rsqrt()
+    xh = (x - mean) * rstd
+    dg = dy * gamma
+    dx = rstd * (dg - dg.mean(-1, keepdim=True) - xh * (dg * xh).mean(-1, keepdim=True))
+    rows = tuple(range(x.dim() - 1))
+    return dx, (dy * xh).sum(rows), dy.sum(rows)
+
+
+def _gelu_parts(g):
+    cdf = 0.5 * (1 + torch.erf(g * 0.7071067811865476))
+    return g * cdf, cdf + g * torch.exp(-0.5 * g * g) * 0.3989422804014327
+
+
+def geglu_host(p):
+    """P [..., 2F] = (h | g) -> h gelu(g) (erf GELU)"""
+    h, g = p.chunk(2, dim=-1)
+    return h * _gelu_parts(g)[0]
+
+
+def geglu_bwd_host(p, dy):
+    """dP = (dy gelu(g) | dy h (Phi(g) + g phi(g)))"""
+    h, g = p.chunk(2, dim=-1)
+    gelu, dgelu = _gelu_parts(g)
+    return torch.cat([dy * gelu, dy * h * dgelu], dim=-1)
+
+
+# ---- device operators ------------------------------------------------------------------------------------------------------------------
+def _attn_args(ts, B):
+    """row and batch strides (elements) of [B, T, width] views with a unit last stride"""
+    for t in ts:
+        if t.dim() != 3 or t.shape[0] != B or t.stride(2) != 1 or (B > 1 and t.stride(0) != t.shape[1] * t.stride(1)):
+            raise EngineError("attention32: operands must be [B, T, C] views of row-major rows")
+    return [t.stride(1) for t in ts], [t.shape[1] * t.stride(1) for t in ts]
+
+
+def attention_fwd32(q, k, v, heads: int) -> torch.Tensor:
+    """dm_f32_op_attention on [B,T,C] views (slices of stacked rows are read in place) -> O [B,Tq,C]"""
+    B, Tq, Cc = q.shape
+    Tk, D = k.shape[1], Cc // heads
+    o = torch.empty(B, Tq, Cc, dtype=torch.float32, device=q.device)
+    ld, bs = _attn_args((q, k, v, o), B)
+    _check(_lib().dm_f32_op_attention(_stream(), _p(q), _p(k), _p(v), _p(o), *ld, *bs, None, 0, B, heads, Tq, Tk, D, D ** -0.5), "dm_f32_op_attention")
+    return o
+
+
+def attention_bwd32(q, k, v, o, do, dq, dk, dv, heads: int, work: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dm_f32_op_attention_bwd into the views dq, dk, dv; returns the workspace (it starts with (L, delta) [B,heads,Tq,2])"""
+    lib = _lib()
+    B, Tq, Cc = q.shape
+    Tk, D = k.shape[1], Cc // heads
+    nbytes = lib.dm_f32_op_attention_bwd_workspace(B, heads, Tq, Tk, D)
+    if nbytes == 0:
+        raise EngineError("dm_f32_op_attention_bwd_workspace refused its arguments")
+    if work is None:
+        work = torch.empty(nbytes // 4, dtype=torch.float32, device=q.device)
+    ld, bs = _attn_args((q, k, v, o, do, dq, dk, dv), B)
+    _check(lib.dm_f32_op_attention_bwd(_stream(), _p(q), _p(k), _p(v), _p(o), _p(do), _p(dq), _p(dk), _p(dv), (C.c_int32 * 8)(*ld), (C.c_int64 * 8)(*bs), None,
+                                       B, heads, Tq, Tk, D, D ** -0.5, _p(work), work.numel() * work.element_size()), "dm_f32_op_attention_bwd")
+    return work
+
+
+class _Attention32(torch.autograd.Function):
+    """layout 0: (q, k, v) separate [B,T,C]; 1: a = stacked q|k|v [B,T,3C]; 2: a = q [B,Tq,C], b = stacked k|v [B,Tk,2C]"""
+    @staticmethod
+    def _views(layout, a, b, c):
+        if layout == 0:
+            return a, b, c
+        Cc = a.shape[-1] // 3 if layout == 1 else a.shape[-1]
+        if layout == 1:
+            return a[..., :Cc], a[..., Cc:2 * Cc], a[..., 2 * Cc:]
+        return a, b[..., :Cc], b[..., Cc:]
+
+    @staticmethod
+    def forward(ctx, a, b, c, heads, layout):
+        a, b, c = (_f32c(t, "attention32") for t in (a, b, c))
+        q, k, v = _Attention32._views(layout, a, b, c)
+        o = attention_fwd32(q, k, v, heads)
+        ctx.save_for_backward(a, b, c, o)
+        ctx.heads, ctx.layout = heads, layout
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        a, b, c, o = ctx.saved_tensors
+        do = do.contiguous()
+        da, db, dc = (None if t is None else torch.empty_like(t) for t in (a, b, c))
+        q, k, v = _Attention32._views(ctx.layout, a, b, c)
+        dq, dk, dv = _Attention32._views(ctx.layout, da, db, dc)
+        attention_bwd32(q, k, v, o, do, dq, dk, dv, ctx.heads)
+        return da, db, dc, None, None
+
+
+def attention32(q, k, v, heads: int) -> torch.Tensor:
+    """softmax(q k^T / sqrt(D)) v per head, q [B,Tq,C], k, v [B,Tk,C], C = heads * D, D in {40, 80, 160}; differentiable in q, k, v"""
+    return _Attention32.apply(q, k, v, heads, 0)
+
+
+def attention32_qkv(qkv, heads: int) -> torch.Tensor:
+    """self-attention on stacked rows q|k|v [B,T,3C], read in place; the gradient comes back stacked, one buffer for to_q|to_k|to_v"""
+    return _Attention32.apply(qkv, None, None, heads, 1)
+
+
+def attention32_q_kv(q, kv, heads: int) -> torch.Tensor:
+    """cross-attention of q [B,Tq,C] on stacked rows k|v [B,Tk,2C]"""
+    return _Attention32.apply(q, kv, None, heads, 2)
+
+
+class _LayerNorm32(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, gamma, beta, eps):
+        x, gamma, beta = (_f32c(t, "layernorm32") for t in (x, gamma, beta))
+        Cc = x.shape[-1]
+        y = torch.empty_like(x)
+        _check(_lib().dm_f32_op_layernorm(_stream(), _p(x), x.numel() // Cc, Cc, _p(gamma), _p(beta), eps, _p(y)), "dm_f32_op_layernorm")
+        ctx.save_for_backward(x, gamma)
+        ctx.eps = eps
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, gamma = ctx.saved_tensors
+        dy = dy.contiguous()
+        lib = _lib()
+        Cc = x.shape[-1]
+        rows = x.numel() // Cc
+        nbytes = lib.dm_f32_op_layernorm_bwd_workspace(rows, Cc)
+        if nbytes == 0:
+            raise EngineError("dm_f32_op_layernorm_bwd_workspace refused its arguments")
+        work = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=x.device)
+        dx, dg, db = torch.empty_like(x), torch.empty_like(gamma), torch.empty_like(gamma)
+        _check(lib.dm_f32_op_layernorm_bwd(_stream(), _p(x), _p(dy), rows, Cc, _p(gamma), ctx.eps, _p(work), work.numel() * 8, _p(dx), _p(dg), _p(db)),
+               "dm_f32_op_layernorm_bwd")
+        return dx, dg, db, None
+
+
+def layernorm32(x, gamma, beta, eps: float = 1e-5) -> torch.Tensor:
+    """LayerNorm over the last axis as dm_f32_op_layernorm; differentiable in x, gamma, beta"""
+    return _LayerNorm32.apply(x, gamma, beta, eps)
+
+
+class _Geglu32(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, p):
+        p = _f32c(p, "geglu32")
+        Fh = p.shape[-1] // 2
+        y = torch.empty(*p.shape[:-1], Fh, dtype=torch.float32, device=p.device)
+        _check(_lib().dm_f32_op_geglu(_stream(), _p(p), p.numel() // (2 * Fh), Fh, _p(y)), "dm_f32_op_geglu")
+        ctx.save_for_backward(p)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (p,) = ctx.saved_tensors
+        dy = dy.contiguous()
+        Fh = p.shape[-1] // 2
+        dp = torch.empty_like(p)
+        _check(_lib().dm_f32_op_geglu_bwd(_stream(), _p(p), _p(dy), p.numel() // (2 * Fh), Fh, _p(dp)), "dm_f32_op_geglu_bwd")
+        return dp
+
+
+def geglu32(p: torch.Tensor) -> torch.Tensor:
+    """P [..., 2F] = (h | g) -> h gelu(g) [..., F]; differentiable"""
+    return _Geglu32.apply(p)
+
+
+def _linear_res(x, w, bias, res):
+    """F.linear(x, w, bias) + res on rows [M, Cin]: one dm_f32_op_gemm with its residual epilogue"""
+    M, cin = x.shape
+    return conv32(x.reshape(1, 1, M, cin), None, w, bias, None, res.reshape(1, 1, M, w.shape[0]), 0).reshape(M, w.shape[0])
+
+
+# ---- modules ---------------------------------------------------------------------------------------------------------------------------
+class _Tfm32(nn.Module):
+    """_keys(): (diffusers key, owner module, parameter name, row range or None, as a 1x1 convolution).  A stacked parameter appears
+    under several keys, one row range each."""
+    def _keys(self):
+        raise NotImplementedError
+
+    @staticmethod
+    def _view(t, rows, conv):
+        t = t if rows is None else t[rows[0]:rows[1]]
+        return t[:, :, None, None] if conv else t
+
+    def state_dict(self, *args, destination=None, prefix="", keep_vars=False):
+        out = OrderedDict() if destination is None else destination
+        for key, mod, pname, rows, conv in self._keys():
+            t = self._view(getattr(mod, pname), rows, conv)
+            out[prefix + key] = t if keep_vars else t.detach().clone()
+        return out
+
+    def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
+        want = {key: rest for key, *rest in self._keys()}
+        missing, unexpected = sorted(set(want) - set(state_dict)), sorted(set(state_dict) - set(want))
+        if strict and (missing or unexpected):
+            raise RuntimeError(f"{type(self).__name__}.load_state_dict: missing {missing}, unexpected {unexpected}")
+        with torch.no_grad():
+            for key, (mod, pname, rows, conv) in want.items():
+                if key not in state_dict:
+                    continue
+                dst = self._view(getattr(mod, pname), rows, conv)
+                v = torch.as_tensor(state_dict[key])
+                if tuple(v.shape) != tuple(dst.shape):
+                    raise RuntimeError(f"{key}: shape {tuple(v.shape)} does not fit this block ({tuple(dst.shape)})")
+                dst.copy_(v.to(dst.dtype))
+        return torch.nn.modules.module._IncompatibleKeys(missing, unexpected)
+
+    def grad_dict(self) -> "OrderedDict[str, Optional[torch.Tensor]]":
+        """the parameters' `.grad` under the diffusers names and shapes"""
+        out = OrderedDict()
+        for key, mod, pname, rows, conv in self._keys():
+            g = getattr(mod, pname).grad
+            out[key] = None if g is None else self._view(g, rows, conv)
+        return out
+
+    def _linear_params(self, name: str, cout: int, cin: int, bias: bool) -> None:
+        w = torch.empty(cout, cin)
+        nn.init.kaiming_uniform_(w, a=5 ** 0.5)
+        self.register_parameter(f"{name}_weight", nn.Parameter(w))
+        if bias:
+            self.register_parameter(f"{name}_bias", nn.Parameter(torch.empty(cout).uniform_(-cin ** -0.5, cin ** -0.5)))
+
+    def _norm_params(self, name: str, c: int) -> None:
+        self.register_parameter(f"{name}_weight", nn.Parameter(torch.ones(c)))
+        self.register_parameter(f"{name}_bias", nn.Parameter(torch.zeros(c)))
+
+
+class BasicTransformerBlock32(_Tfm32):
+    """diffusers BasicTransformerBlock (SD 1.5: LayerNorm eps 1e-5, bias-free q/k/v, GEGLU feed-forward of 4 dim) on fp32 tokens:
+    forward(x [B,T,dim], context [B,Tk,ctx_dim]) -> [B,T,dim].  attn1's to_q | to_k | to_v live in one parameter [3 dim][dim], attn2's
+    to_k | to_v in one [2 dim][ctx_dim]; the state dict speaks the diffusers names (norm1.weight ... ff.net.2.bias)."""
+    def __init__(self, dim: int, heads: int, ctx_dim: int):
+        super().__init__()
+        if dim % heads or dim // heads not in (40, 80, 160):
+            raise EngineError(f"BasicTransformerBlock32: head_dim {dim / heads:g} is not 40, 80 or 160")
+        self.dim, self.heads, self.ctx_dim = dim, heads, ctx_dim
+        self._norm_params("norm1", dim)
+        self._linear_params("attn1_to_qkv", 3 * dim, dim, False)
+        self._linear_params("attn1_to_out", dim, dim, True)
+        self._norm_params("norm2", dim)
+        self._linear_params("attn2_to_q", dim, dim, False)
+        self._linear_params("attn2_to_kv", 2 * dim, ctx_dim, False)
+        self._linear_params("attn2_to_out", dim, dim, True)
+        self._norm_params("norm3", dim)
+        self._linear_params("ff_proj", 8 * dim, dim, True)
+        self._linear_params("ff_out", dim, 4 * dim, True)
+
+    def _keys(self):
+        d = self.dim
+        yield "norm1.weight", self, "norm1_weight", None, False
+        yield "norm1.bias", self, "norm1_bias", None, False
+        for i, n in enumerate("qkv"):
+            yield f"attn1.to_{n}.weight", self, "attn1_to_qkv_weight", (i * d, (i + 1) * d), False
+        yield "attn1.to_out.0.weight", self, "attn1_to_out_weight", None, False
+        yield "attn1.to_out.0.bias", self, "attn1_to_out_bias", None, False
+        yield "norm2.weight", self, "norm2_weight", None, False
+        yield "norm2.bias", self, "norm2_bias", None, False
+        yield "attn2.to_q.weight", self, "attn2_to_q_weight", None, False
+        for i, n in enumerate("kv"):
+            yield f"attn2.to_{n}.weight", self, "attn2_to_kv_weight", (i * d, (i + 1) * d), False
+        yield "attn2.to_out.0.weight", self, "attn2_to_out_weight", None, False
+        yield "attn2.to_out.0.bias", self, "attn2_to_out_bias", None, False
+        yield "norm3.weight", self, "norm3_weight", None, False
+        yield "norm3.bias", self, "norm3_bias", None, False
+        yield "ff.net.0.proj.weight", self, "ff_proj_weight", None, False
+        yield "ff.net.0.proj.bias", self, "ff_proj_bias", None, False
+        yield "ff.net.2.weight", self, "ff_out_weight", None, False
+        yield "ff.net.2.bias", self, "ff_out_bias", None, False
+
+    def forward(self, x, context):
+        B, Tq, d = x.shape
+        if d != self.dim or context.dim() != 3 or context.shape[0] != B or context.shape[2] != self.ctx_dim:
+            raise EngineError("BasicTransformerBlock32: x [B,T,dim] and context [B,Tk,ctx_dim] are expected")
+        Tk = context.shape[1]
+        x = x.reshape(B * Tq, d)
+        h = layernorm32(x, self.norm1_weight, self.norm1_bias)
+        a = attention32_qkv(linear32(h, self.attn1_to_qkv_weight, None).reshape(B, Tq, 3 * d), self.heads)
+        x = _linear_res(a.reshape(B * Tq, d), self.attn1_to_out_weight, self.attn1_to_out_bias, x)
+        h = layernorm32(x, self.norm2_weight, self.norm2_bias)
+        q = linear32(h, self.attn2_to_q_weight, None).reshape(B, Tq, d)
+        kv = linear32(context.reshape(B * Tk, self.ctx_dim), self.attn2_to_kv_weight, None).reshape(B, Tk, 2 * d)
+        a = attention32_q_kv(q, kv, self.heads)
+        x = _linear_res(a.reshape(B * Tq, d), self.attn2_to_out_weight, self.attn2_to_out_bias, x)
+        h = layernorm32(x, self.norm3_weight, self.norm3_bias)
+        y = geglu32(linear32(h, self.ff_proj_weight, self.ff_proj_bias))
+        return _linear_res(y, self.ff_out_weight, self.ff_out_bias, x).reshape(B, Tq, d)
+
+
+class Transformer2D32(_Tfm32):
+    """diffusers Transformer2DModel as SD 1.5 uses it (GroupNorm eps 1e-6, proj_in 1x1, one BasicTransformerBlock, proj_out 1x1 + the
+    input) on NHWC fp32: forward(x [N,H,W,C], context [N,Tk,ctx_dim]) -> [N,H,W,C]; state-dict keys norm.weight, proj_in.weight [C,C,1,1],
+    transformer_blocks.0.*, proj_out.*"""
+    def __init__(self, channels: int, heads: int, ctx_dim: int, groups: int = 32):
+        super().__init__()
+        self.channels, self.groups = channels, groups
+        self._norm_params("norm", channels)
+        self._linear_params("proj_in", channels, channels, True)
+        self.block = BasicTransformerBlock32(channels, heads, ctx_dim)
+        self._linear_params("proj_out", channels, channels, True)
+
+    def _keys(self):
+        yield "norm.weight", self, "norm_weight", None, False
+        yield "norm.bias", self, "norm_bias", None, False
+        yield "proj_in.weight", self, "proj_in_weight", None, True
+        yield "proj_in.bias", self, "proj_in_bias", None, False
+        for key, *rest in self.block._keys():
+            yield ("transformer_blocks.0." + key, *rest)
+        yield "proj_out.weight", self, "proj_out_weight", None, True
+        yield "proj_out.bias", self, "proj_out_bias", None, False
+
+    def forward(self, x, context):
+        N, H, W, Cc = x.shape
+        h = groupnorm_silu32(x, None, self.norm_weight, self.norm_bias, self.groups, 1e-6, False)
+        h = conv32(h, None, self.proj_in_weight, self.proj_in_bias, None, None, 0)
+        t = self.block(h.reshape(N, H * W, Cc), context)
+        return conv32(t.reshape(N, H, W, Cc), None, self.proj_out_weight, self.proj_out_bias, None, x, 0)

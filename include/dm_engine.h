@@ -1309,6 +1309,39 @@ int dm_f32_op_groupnorm_bwd(void* stream, const void* X, const void* X2, const v
 int dm_f32_op_silu_bwd(void* stream, const void* x, const void* dy, void* dx, int64_t n);
 int dm_f32_op_zero_insert2(void* stream, const void* dY, int N, int H, int W, int C, void* Z);
 int dm_f32_op_nearest_bwd(void* stream, const void* dU, int N, int H, int W, int OH, int OW, int C, void* dS);
+/* Gradient operators of the fp32 net's transformer blocks (LayerNorm, attention, GEGLU); the linear layers use dm_f32_op_gemm,
+ * dm_f32_op_gemm_wgrad (mode 0) and dm_f32_op_colsum.  No floating-point atomics; every entry returns 1 without launching on arguments it
+ * refuses.
+ *   attention_bwd  dQ, dK, dV of O = softmax(Q K^T scale) V from Q, K, V, O, dO; row strides ld* and batch strides bs* in elements as
+ *                dm_f32_op_attention, one per tensor in the HOST arrays ld8 / bs8 of eight entries each, in the order Q K V O dO dQ dK dV,
+ *                so stacked q|k|v rows [tokens][3C] and k|v rows [B*Tk][2C] are read and written in place.  D in {40, 80, 160}.  Refused: any other
+ *                D (64 and 512 included), a non-null kv_slot, a batch stride of 0, ld % 4 != 0 or bs % 4 != 0, ld < heads * D, a null or
+ *                not 16-byte aligned pointer, heads > 65535 / B, work_bytes < dm_f32_op_attention_bwd_workspace(...) (which returns 0 for
+ *                refused extents).  work starts with the statistics [B][heads][Tq][2] = (L, Delta), L = log2 sum_k 2^(s scale log2(e)),
+ *                Delta = dO . O; behind them (rounded up to 16 bytes) lie the dK | dV partials [slabs][B][heads][Tk][2 D] of
+ *                dm_f32_op_attention_bwd_slabs(Tq, Tk) query slabs (a function of Tq and Tk alone), added in ascending slab order.
+ *                Every byte that is read is written first: the result does not depend on what work held.
+ *   layernorm_bwd  dX [rows][C], dgamma [C], dbeta [C] of dm_f32_op_layernorm from X and dY; mean and rstd are recomputed per row with the
+ *                forward kernel's expressions.  work: dm_f32_op_layernorm_bwd_workspace(rows, C) bytes, 8-byte aligned (fp64 partial
+ *                sums per row slab, added in ascending order, then (mean, rstd) per row)
+ *   geglu        Y [M][F] = h * gelu(g) of P [M][2F] = (h | g), gelu(g) = 0.5f g (1 + erff(g * 0.70710678f)) as dm_f32's fused GEMM
+ *                epilogue computes it; F % 4 == 0
+ *   geglu_bwd    dP [M][2F] = (dY gelu(g) | dY h (Phi(g) + g phi(g))) */
+size_t dm_f32_op_attention_bwd_workspace(int B, int heads, int Tq, int Tk, int D);
+int dm_f32_op_attention_bwd_slabs(int Tq, int Tk);
+int dm_f32_op_attention_bwd(void* stream, const void* Q, const void* K, const void* V, const void* O, const void* dO, void* dQ, void* dK,
+                            void* dV, const int32_t* ld8, const int64_t* bs8, const int32_t* kv_slot, int B, int heads, int Tq, int Tk,
+                            int D, float scale, void* work, size_t work_bytes);
+/* measurement only (tools/train_tfm_rate.py): the same call restricted to the kernels named by `phases` (bit 0 statistics, 1 dQ, 2 dK / dV
+ * partials, 3 their sum; 1 .. 15), on a workspace that one full call has filled */
+int dm_f32_op_attention_bwd_phases(void* stream, const void* Q, const void* K, const void* V, const void* O, const void* dO, void* dQ,
+                                   void* dK, void* dV, const int32_t* ld8, const int64_t* bs8, const int32_t* kv_slot, int B, int heads,
+                                   int Tq, int Tk, int D, float scale, void* work, size_t work_bytes, int phases);
+size_t dm_f32_op_layernorm_bwd_workspace(int rows, int C);
+int dm_f32_op_layernorm_bwd(void* stream, const void* X, const void* dY, int rows, int C, const float* gamma, float eps, void* work,
+                            size_t work_bytes, void* dX, void* dgamma, void* dbeta);
+int dm_f32_op_geglu(void* stream, const void* P, int M, int F, void* Y);
+int dm_f32_op_geglu_bwd(void* stream, const void* P, const void* dY, int M, int F, void* dP);
 
 #ifdef __cplusplus
 }
