@@ -1,7 +1,8 @@
 """Guard bands around every operand of the gradient entries (tests/test_gpu_guards.py run3: a plain run, then all device operands —
 workspaces included — inside one allocation between guards filled with 0xFF, then 0x00): the guards and the inputs come back untouched,
 and the three results are equal bit for bit, so no load outside a tensor (or of workspace the call did not write) reaches a result.
-Shapes: the ragged cases of tests/test_gpu_train_ops.py; the plain result is checked against float64 there."""
+Shapes: the ragged cases of tests/test_gpu_train_ops.py, and the 16-slab weight gradient of tests/train_net_cases.py (the cap of the slab rule:
+sixteen partials in the workspace, the last slab ragged); the plain result is checked against float64 there."""
 import pytest
 import torch
 
@@ -11,6 +12,7 @@ from diff_mining_amd import engine as E  # noqa: E402
 from diff_mining_amd import train as T  # noqa: E402
 from tests import gpu_util as U  # noqa: E402
 from tests import train_cases as TC  # noqa: E402
+from tests import train_net_cases as TN  # noqa: E402
 from tests.test_gpu_guards import run3  # noqa: E402
 
 F32, F64 = torch.float32, torch.float64
@@ -21,7 +23,7 @@ def _need_gpu():
     assert torch.cuda.is_available(), "GPU tests need a GPU"
 
 
-@pytest.mark.parametrize("c", [TC.CONV_CASES[0], TC.CONV_CASES[1], TC.CONV_CASES[4], TC.CONV_CASES[6], TC.CONV_CASES[8]], ids=TC.case_id)
+@pytest.mark.parametrize("c", [TC.CONV_CASES[0], TC.CONV_CASES[1], TC.CONV_CASES[4], TC.CONV_CASES[6], TC.CONV_CASES[8], TN.CONV_16_SLABS], ids=TC.case_id)
 def test_wgrad32(c):
     lib = E.load_library()
     mode, N, H, W, C1, C2, Cout, out_hw = c
@@ -33,6 +35,8 @@ def test_wgrad32(c):
         inputs["x2"] = xn[..., C1:].contiguous()
     nbytes = lib.dm_f32_op_gemm_wgrad_workspace(N, H, W, OH, OW, C1 + C2, Cout, mode)
     assert nbytes > 0
+    if c == TN.CONV_16_SLABS:
+        assert nbytes == 16 * 4 * Cout * (C1 + C2) and TN.wgrad_slab_rule(N * OH * OW)[::2] == (16, [2080] * 15 + [1605])
 
     def launch(v):
         assert lib.dm_f32_op_gemm_wgrad(U.stream(), U.ptr(v["x"]), U.ptr(v.get("x2")), U.ptr(v["dy"]), U.ptr(v["dw"]), U.ptr(v["work"]), nbytes, N, H, W, OH, OW,

@@ -2,7 +2,9 @@
 _nearest_bwd, and the data gradient = dm_f32_op_gemm on dgrad_weights) against torch.autograd on the CPU in float64.
 
 Tolerance (tests/train_cases.py): device within max(2e-6, 4 x rel-L2(CPU fp32 autograd, float64)) of float64; every case prints its three
-figures (lines starting TRAIN_OPS; profiles/train_ops.txt is that table).  Shapes: the smallest that reach each hazard, see CONV_CASES.
+figures (lines starting TRAIN_OPS; profiles/train_ops.txt is that table).  Shapes: the smallest that reach each hazard, see CONV_CASES, and
+the shapes of tests/train_net_cases.py at which a real training step takes the slab branches (M >= 8192, the cap of 16) and the up
+blocks' GroupNorm geometry.
 Also: determinism (two runs, and a workspace pre-filled with 0xFF bytes, give the same bits), accumulate = 1 is one fp32 addition onto what
 the output holds, and every refusal of include/dm_engine.h returns 1 and leaves the output untouched."""
 import ctypes as C
@@ -17,6 +19,9 @@ from diff_mining_amd import engine as E  # noqa: E402
 from diff_mining_amd import train as T  # noqa: E402
 from tests import gpu_util as U  # noqa: E402
 from tests import train_cases as TC  # noqa: E402
+from tests import train_net_cases as TN  # noqa: E402
+
+CONV_CASES = TC.CONV_CASES + TN.NET_CONV_CASES
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -32,7 +37,7 @@ def _dev_case(c):
     return k, xa, xb, T.pack_conv(k["w"]).cuda(), TC.nhwc(k["dy"]).cuda()
 
 
-@pytest.mark.parametrize("c", TC.CONV_CASES, ids=TC.case_id)
+@pytest.mark.parametrize("c", CONV_CASES, ids=TC.case_id)
 def test_wgrad32(c):
     k, xa, xb, _, dy = _dev_case(c)
     got = T.wgrad32(xa, xb, dy, c[0], c[7])
@@ -42,7 +47,7 @@ def test_wgrad32(c):
     assert TC.rel_l2(T.wgrad_host(xa.cpu(), None if xb is None else xb.cpu(), dy.cpu(), c[0], c[7]), T.pack_conv(k["g64"][1])) < 1e-12
 
 
-@pytest.mark.parametrize("c", TC.CONV_CASES, ids=TC.case_id)
+@pytest.mark.parametrize("c", CONV_CASES, ids=TC.case_id)
 def test_data_gradient(c):
     mode, N, H, W, C1, C2, Cout, out_hw = c
     k, xa, xb, wp, dy = _dev_case(c)
@@ -78,6 +83,7 @@ GN_CASES = [(2, 9, 7, 64, 32, 32, True, False),       # HW = 63, three channels 
             (2, 1, 1, 64, 32, 32, True, False),       # HW = 1
             (2, 9, 7, 64, 32, 32, False, False),      # without SiLU
             (2, 4, 4, 32, 32, 4, True, True)]         # a constant-input group: var = 0
+GN_CASES += TN.NET_GN_CASES                           # 60, 30, 80 and 20 channels per group; a group across C1 | C2 at 60 and 30
 
 
 @pytest.mark.parametrize("N,H,W,C1,C2,G,silu,const", GN_CASES)
@@ -147,12 +153,16 @@ def _work_for(c, dy, fill):
     OH, OW = (H, W) if mode in (0, 1) else (dy.shape[1], dy.shape[2])
     nbytes = E.load_library().dm_f32_op_gemm_wgrad_workspace(N, H, W, OH, OW, C1 + C2, Cout, mode)
     assert nbytes > 0 and nbytes % (4 * Cout * T.taps_of(mode) * (C1 + C2)) == 0      # one partial dWp per slab
-    return torch.full((nbytes,), fill, dtype=torch.uint8, device="cuda"), nbytes // (4 * Cout * T.taps_of(mode) * (C1 + C2))
+    slabs = nbytes // (4 * Cout * T.taps_of(mode) * (C1 + C2))
+    assert slabs == TN.wgrad_slab_rule(N * OH * OW)[0]                                # the rule of DESIGN 4ab, restated on the host
+    return torch.full((nbytes,), fill, dtype=torch.uint8, device="cuda"), slabs
 
 
-@pytest.mark.parametrize("c", [TC.CONV_CASES[0], TC.CONV_CASES[2], TC.CONV_CASES[4], TC.CONV_CASES[6], TC.CONV_CASES[8]], ids=TC.case_id)
+@pytest.mark.parametrize("c", [TC.CONV_CASES[0], TC.CONV_CASES[2], TC.CONV_CASES[4], TC.CONV_CASES[6], TC.CONV_CASES[8]] + TN.NET_CONV_CASES, ids=TC.case_id)
 def test_wgrad32_is_deterministic_and_accumulates(c):
     _, xa, xb, _, dy = _dev_case(c)
+    if c in TN.NET_CONV_PARTITIONS:
+        assert _work_for(c, dy, 0)[1] == TN.NET_CONV_PARTITIONS[c][0]
     ref = T.wgrad32(xa, xb, dy, c[0], c[7])
     again = T.wgrad32(xa, xb, dy, c[0], c[7])
     torch.cuda.synchronize()
@@ -174,6 +184,10 @@ def test_slab_count_follows_the_pixel_count_alone():
     per = lambda N, H, W, Cin, Cout, mode: ws(N, H, W, H, W, Cin, Cout, mode) // (4 * Cout * T.taps_of(mode) * Cin)      # noqa: E731
     assert per(1, 1, 1, 32, 32, 1) == 1 and per(2, 16, 16, 320, 320, 1) == 4 and per(2, 16, 16, 32, 4, 1) == 4
     assert per(1, 1, 231, 768, 64, 0) == 2 and per(4, 64, 64, 320, 320, 1) == 8 and per(4, 64, 64, 960, 320, 1) == 8
+    for c, (slabs, _, _) in TN.NET_CONV_PARTITIONS.items():          # M = 8191 | 8197 ... 32 805: both sides of the branch at 8192, and the cap
+        mode, N, H, W, C1, C2, Cout, out_hw = c
+        OH, OW = (H, W) if mode in (0, 1) else ((H + 1) // 2, (W + 1) // 2) if mode == 2 else out_hw
+        assert ws(N, H, W, OH, OW, C1 + C2, Cout, mode) == slabs * 4 * Cout * T.taps_of(mode) * (C1 + C2), c
     assert ws(2, 16, 16, 16, 16, 320, 320, 4) == 0 and ws(2, 16, 16, 16, 16, 320, 320, -1) == 0 and ws(0, 16, 16, 16, 16, 320, 320, 1) == 0
 
 

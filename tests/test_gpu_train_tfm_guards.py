@@ -1,7 +1,9 @@
 """Guard bands around every operand of the transformer half's gradient entries (tests/test_gpu_guards.py run3: a plain run, then all
 device operands — workspaces included — inside one allocation between guards filled with 0xFF, then 0x00): the guards and the inputs come
 back untouched, and the three results are equal bit for bit, so no load outside a tensor (or of workspace the call did not write) reaches a
-result.  Shapes: the ragged cases of tests/test_gpu_train_tfm_ops.py; the plain result is checked against float64 here too."""
+result.  Shapes: the ragged cases of tests/test_gpu_train_tfm_ops.py, and the Tq = 8200 cross-attention of tests/train_net_cases.py (sixteen
+query slabs, the fifteenth ragged, the sixteenth empty: its zero partials are part of the compared workspace); the plain result is checked
+against float64 here too."""
 import ctypes as C
 
 import pytest
@@ -11,6 +13,7 @@ pytestmark = pytest.mark.gpu
 
 from diff_mining_amd import engine as E  # noqa: E402
 from tests import gpu_util as U  # noqa: E402
+from tests import train_net_cases as TN  # noqa: E402
 from tests import train_tfm_cases as TT  # noqa: E402
 from tests.test_gpu_guards import run3  # noqa: E402
 
@@ -22,7 +25,8 @@ def _need_gpu():
     assert torch.cuda.is_available(), "GPU tests need a GPU"
 
 
-@pytest.mark.parametrize("c", [TT.ATTN_CASES[0], TT.ATTN_CASES[1], TT.ATTN_CASES[2], TT.ATTN_CASES[4], TT.ATTN_CASES[5], TT.ATTN_CASES[6]], ids=TT.attn_id)
+@pytest.mark.parametrize("c", [TT.ATTN_CASES[0], TT.ATTN_CASES[1], TT.ATTN_CASES[2], TT.ATTN_CASES[4], TT.ATTN_CASES[5], TT.ATTN_CASES[6],
+                               TN.ATTN_EMPTY_SLAB], ids=TT.attn_id)
 def test_attention_forward_and_backward(c):
     """self-attention on stacked q|k|v rows with a stacked gradient, cross-attention on q and stacked k|v: the strided views end exactly at
     the tensors' ends, so a read or write past a row's head slice lands in a guard"""
@@ -33,6 +37,8 @@ def test_attention_forward_and_backward(c):
     self_attn = Tq == Tk
     nbytes = lib.dm_f32_op_attention_bwd_workspace(B, heads, Tq, Tk, D)
     assert nbytes > 0 and nbytes % 4 == 0
+    if c == TN.ATTN_EMPTY_SLAB:
+        assert nbytes == 4 * (2 * Tq + 16 * Tk * 2 * D) and TN.attn_slab_rule(Tq, Tk)[2][14:] == [136, 0]
     if self_attn:
         inputs = {"qkv": torch.cat([k["q"], k["k"], k["v"]], dim=-1), "do": k["do"]}
         outputs = {"o": ((B, Tq, Cc), F32), "dqkv": ((B, Tq, 3 * Cc), F32), "work": ((nbytes // 4,), F32)}

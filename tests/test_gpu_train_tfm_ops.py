@@ -4,7 +4,9 @@ f32_train.hip) against torch.autograd in float64 on the CPU.
 Rule (tests/train_tfm_cases.py): within max(floor, 4 x rel-L2(CPU fp32 autograd, float64)) of float64; floor 2e-6 for LayerNorm backward,
 GEGLU and the attention statistics (L, Delta), 2e-5 for the attention gradients.  Every check prints its three figures (lines starting
 TRAIN_OPS; profiles/train_tfm_ops.txt is that table).  Also: the slab rule, determinism (two runs, and a workspace pre-filled with 0xFF
-bytes, give the same bits) and every refusal of include/dm_engine.h (1, nothing launched)."""
+bytes, give the same bits) and every refusal of include/dm_engine.h (1, nothing launched).  The shapes of tests/train_net_cases.py add the
+partitions a real step takes: the cap of 16 query slabs with an empty trailing slab (it must write zeros), a slab of one query,
+B * heads = 32, and LayerNorm's cap of 64 row slabs."""
 import ctypes as C
 
 import pytest
@@ -15,7 +17,11 @@ pytestmark = pytest.mark.gpu
 from diff_mining_amd import engine as E  # noqa: E402
 from diff_mining_amd import train as T  # noqa: E402
 from tests import gpu_util as U  # noqa: E402
+from tests import train_net_cases as TN  # noqa: E402
 from tests import train_tfm_cases as TT  # noqa: E402
+
+ATTN_CASES = TT.ATTN_CASES + TN.NET_ATTN_CASES
+LN_CASES = TT.LN_CASES + TN.NET_LN_CASES
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -35,7 +41,7 @@ def _operands(c):
     return k, (q, kv, None), (q, kv[..., :Cc], kv[..., Cc:]), 2
 
 
-@pytest.mark.parametrize("c", TT.ATTN_CASES, ids=TT.attn_id)
+@pytest.mark.parametrize("c", ATTN_CASES, ids=TT.attn_id)
 def test_attention_gradients(c):
     B, heads, Tq, Tk, D, _ = c
     k, leaves, (q, kk, v), layout = _operands(c)
@@ -88,6 +94,10 @@ def test_slab_rule():
     # the workspace: (L, Delta) per (b, head, q), rounded up to 16 bytes, then slabs x [B heads][Tk][2 D] partials
     assert ws(1, 1, 1030, 77, 40) == 4 * (2 * 1030 + 3 * 77 * 80) and ws(1, 1, 1, 5, 40) == 4 * (4 + 5 * 80)
     assert ws(4, 8, 4096, 4096, 40) == 4 * (2 * 32 * 4096 + 32 * 4096 * 80) and ws(4, 8, 4096, 77, 40) == 4 * (2 * 32 * 4096 + 8 * 32 * 77 * 80)
+    for c, (n, _, _) in TN.NET_ATTN_PARTITIONS.items():          # and the host's restatement of the rule says the same
+        assert slabs(c[2], c[3]) == n == TN.attn_slab_rule(c[2], c[3])[0], c
+    for tq, tk in ((1030, 77), (200, 200), (4096, 77), (513, 128), (513, 129), (100000, 77), (8200, 77), (4097, 77), (1, 5)):
+        assert slabs(tq, tk) == TN.attn_slab_rule(tq, tk)[0], (tq, tk)
     for bad in ((1, 1, 64, 64, 64), (1, 1, 64, 64, 512), (0, 1, 64, 64, 40), (1, 0, 64, 64, 40), (1, 1, 0, 64, 40), (1, 1, 64, 0, 40), (1, 1, 64, 64, 0),
                 (256, 256, 64, 64, 40)):
         assert ws(*bad) == 0, bad
@@ -122,9 +132,9 @@ def _raw(c, **over):
     return rc, t
 
 
-@pytest.mark.parametrize("c", [TT.ATTN_CASES[1], TT.ATTN_CASES[6], TT.ATTN_CASES[0]], ids=TT.attn_id)
+@pytest.mark.parametrize("c", [TT.ATTN_CASES[1], TT.ATTN_CASES[6], TT.ATTN_CASES[0]] + TN.NET_ATTN_CASES, ids=TT.attn_id)
 def test_attention_backward_is_deterministic(c):
-    """two runs, and a workspace pre-filled with 0xFF bytes: the same bits"""
+    """two runs, and a workspace pre-filled with 0xFF bytes: the same bits; a query slab that holds no query leaves zero partials"""
     lib = E.load_library()
     B, heads, Tq, Tk, D, _ = c
     if c == TT.ATTN_CASES[6]:
@@ -143,7 +153,20 @@ def test_attention_backward_is_deterministic(c):
     for i, n in enumerate(("dq", "dk", "dv")):
         assert torch.equal(a[n], b[n]), n
         assert torch.equal(a[n], outs[i]), n
-    assert torch.equal(a["work"].view(torch.int32), b["work"].view(torch.int32)) and torch.equal(a["work"].view(torch.int32), work.view(torch.int32))
+    # the workspace: the statistics, up to 3 floats of padding to 16 bytes that nothing writes or reads (they keep their fill), the partials
+    n_st = 2 * B * heads * Tq
+    wa, wb, wc = (w.view(torch.int32) for w in (a["work"], b["work"], work))
+    for sl in (slice(0, n_st), slice((n_st + 3) // 4 * 4, None)):
+        assert torch.equal(wa[sl], wb[sl]) and torch.equal(wa[sl], wc[sl])
+    assert (a["work"][4 * n_st:4 * ((n_st + 3) // 4 * 4)] == 0x5A).all().item() and (wc[n_st:(n_st + 3) // 4 * 4] == -1).all().item()
+    # the partials behind the statistics, [slabs][B heads][Tk][2 D]: an empty slab wrote zeros over the 0xFF bytes, a populated one did not
+    slabs, _, pop = TN.attn_slab_rule(Tq, Tk)
+    assert slabs == lib.dm_f32_op_attention_bwd_slabs(Tq, Tk)
+    part = work[(2 * B * heads * Tq + 3) // 4 * 4:].reshape(slabs, -1)
+    for s in range(slabs):
+        assert torch.isfinite(part[s]).all().item() and (not part[s].any().item()) == (pop[s] == 0), (s, pop[s])
+    if c == TN.ATTN_EMPTY_SLAB:
+        assert pop[15] == 0 and pop[14] == 136
 
 
 def test_phases_one_by_one_equal_the_full_call():
@@ -205,13 +228,14 @@ def test_attention_refusals_launch_nothing():
 # ---------------------------------------------------------------------------------------------------------------------------------------
 # LayerNorm, GEGLU
 # ---------------------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("rows,Cc,const", TT.LN_CASES, ids=lambda v: str(v))
+@pytest.mark.parametrize("rows,Cc,const", LN_CASES, ids=lambda v: str(v))
 def test_layernorm_gradients(rows, Cc, const):
     lib = E.load_library()
     k = TT.ln_case(rows, Cc, const)
     what = f"layernorm {rows}x{Cc}" + (" const" if const else "")
-    if rows == 600:
-        assert lib.dm_f32_op_layernorm_bwd_workspace(rows, Cc) == 3 * 2 * Cc * 8 + rows * 8          # three row slabs
+    slabs = TN.ln_slab_rule(rows)[0]                                                                # min(64, ceil(rows / 256)), restated on the host
+    assert lib.dm_f32_op_layernorm_bwd_workspace(rows, Cc) == slabs * 2 * Cc * 8 + rows * 8
+    assert slabs == {600: 3, 16391: 64}.get(rows, 1)                                                # three row slabs at 600, the cap at 16 391
     x, gamma, beta = (k[n].cuda().requires_grad_() for n in ("x", "gamma", "beta"))
     y = T.layernorm32(x, gamma, beta, 1e-5)
     y.backward(k["dy"].cuda())
